@@ -21,7 +21,12 @@ Workloads (``--config``):
 
 Before the W warm-up steps every workload runs a time-based GPU pre-roll of the SAME step (>= ``--preroll-ms``,
 default 100 ms, disclosed in the line as ``preroll_ms`` / ``preroll_steps``): a fresh box's first milliseconds are
-spent at idle clocks and on first-touch page faults, and W = 5 steps of 1.3 ms do not get past them.
+spent at idle clocks and on first-touch page faults, and W = 5 steps of 1.3 ms do not get past them.  The pre-roll
+trains on a copy of the training state: the warm-up and timed steps start from the same parameters in every run.
+
+A plain run does only what the headline figure needs.  ``--full`` adds what takes runs of its own: the filterbank
+HBM roofline (``roofline_hbm``), the BASELINE config 3 and config 5 legs (``also``, default workload only) and the
+CPU baseline (``cpu_baseline``).  ``--dump-outputs DIR`` writes what the last timed step computed as DIR/*.npy.
 
 Rank 0 prints ONE JSON line (see DESIGN.md "Measurement" for every field).
 """
@@ -229,20 +234,71 @@ def filterbank_hbm_roofline(fx, x, nb, groups=8, per_group=4):
             "shader_clock_mhz": clk, "trials_per_pass": Bs, "algorithmic_bytes_per_pass": by}
 
 
+def train_state(trainer):
+    """Everything a training step reads and updates: the flat parameters, AdamW's moments and step count, the
+    BatchNorm buffers and the dropout call counters (``load_train_state`` puts them back)."""
+    m = trainer.model
+    return {"flat": trainer.flat.clone(), "opt": trainer.optimizer_state(), "buffers": [b.clone() for b in m.buffers()],
+            "calls": [(mod, mod._calls) for mod in m.modules() if "_calls" in vars(mod)]}
+
+
+def load_train_state(trainer, state):
+    trainer.flat.copy_(state["flat"])
+    trainer.load_optimizer_state(state["opt"])
+    for b, v in zip(trainer.model.buffers(), state["buffers"]):
+        b.copy_(v)
+    for mod, n in state["calls"]:
+        mod._calls = n
+
+
+DUMP_BYTES = 64 << 20            # --dump-outputs: at most this much in all
+DUMP_FEATURE_BYTES = 32 << 20    # of which the feature map (a fixed sample of its trials when it is larger)
+
+
+def step_outputs(out, feats, trainer):
+    """What a caller of the timed step receives: the feature map (a seeded sample of whole trials when it exceeds
+    DUMP_FEATURE_BYTES, with the trial indices), the loss, logits and predictions, and the parameters after AdamW."""
+    B = feats.shape[0]
+    per_trial = feats[0].numel() * 4
+    n = min(B, max(1, DUMP_FEATURE_BYTES // per_trial))
+    idx = np.arange(B) if n == B else np.sort(np.random.default_rng(0).choice(B, size=n, replace=False))
+    arrays = {"features": feats[torch.from_numpy(idx).to(feats.device)].float().cpu().numpy(),
+              "features_trial_index": idx.astype(np.float64),
+              "loss": out["loss"].float().cpu().numpy().reshape(1),
+              "logits": out["logits"].float().cpu().numpy(),
+              "pred": out["pred"].cpu().numpy().astype(np.float32),
+              "params": trainer.flat.float().cpu().numpy()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_BYTES} byte budget")
+    return arrays
+
+
+def write_outputs(dirname, arrays):
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
+
+
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--config", choices=sorted(CONFIGS), default="cfg2")
-    ap.add_argument("--steps", type=int, default=None)
-    ap.add_argument("--warmup", type=int, default=None)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default: the configuration's)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed warm-up steps after the pre-roll")
     ap.add_argument("--batch", type=int, default=None, help="trials per GPU (default: the configuration's batch)")
     ap.add_argument("--two-kernel", action="store_true", help="materialise the filtered signals (fb + bandpower)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-hbm-roofline", action="store_true", help="skip the filterbank-stage HBM measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the filterbank HBM roofline, the \"also\" legs of "
+                         "the default workload and the CPU baseline (a plain run times the headline steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-hbm-roofline", action="store_true", help="--full: skip the filterbank-stage HBM measurement")
     ap.add_argument("--bf16", action="store_true", help="config 3: bf16 activations/grads in the CNN, fp32 accumulate")
     ap.add_argument("--no-also", action="store_true",
-                    help="default invocation only: skip the BASELINE config 3 (bf16) and config 5 (stress) runs that are "
-                         "reported under \"also\" beside the cfg2 fp32 line")
+                    help="--full, default invocation only: skip the BASELINE config 3 (bf16) and config 5 (stress) runs "
+                         "that are reported under \"also\" beside the cfg2 fp32 line")
     ap.add_argument("--overlap", action="store_true",
                     help="extract the features of the next batch on a second HIP stream while the CNN trains on the "
                          "current one, the CNN stream at high priority (measured, round 3: 1.32 ms against 1.26 ms "
@@ -261,10 +317,10 @@ def parse_args():
 
 
 def run_workload(config, steps, warmup, batch, bf16, two_kernel, overlap_flag, no_pipeline, hbm_roofline, env,
-                 preroll_ms=100.0):
+                 preroll_ms=100.0, dump_dir=None):
     """One workload: a time-based pre-roll of the same step, W untimed warm-up steps, exactly K timed steps between
     barrier + synchronize pairs, the MAX of the ranks' wall times.  Returns the JSON line's fields on rank 0 (None
-    elsewhere)."""
+    elsewhere); with ``dump_dir`` rank 0 also writes the outputs of the last timed step there."""
     import torch.distributed as dist
     import isd_amd
     from isd_amd.classifier import _EEGNetFeatureModel, _FeatureModel
@@ -378,8 +434,11 @@ def run_workload(config, steps, warmup, batch, bf16, two_kernel, overlap_flag, n
 
     # Pre-roll: the same step, untimed, until >= preroll_ms of wall time have passed on EVERY rank (the ranks decide
     # on the all-reduced minimum, so they run the same number of steps and collectives).
+    # Its step count depends on the box's speed, so it trains on a copy of the state: the warm-up and timed steps
+    # start from the same parameters in every run (--dump-outputs compares runs and builds output for output).
     pre_steps, pre_ms = 0, 0.0
     if preroll_ms > 0:
+        state = train_state(trainer)
         chunk = 1 if config == "cfg5" else 8
         tp = time.perf_counter()
         while pre_ms < preroll_ms and pre_steps < 4096:
@@ -388,6 +447,9 @@ def run_workload(config, steps, warmup, batch, bf16, two_kernel, overlap_flag, n
             pre_steps += chunk
             torch.cuda.synchronize()
             pre_ms = over_ranks((time.perf_counter() - tp) * 1e3, dist.ReduceOp.MIN)
+        load_train_state(trainer, state)
+        del state
+        torch.cuda.synchronize()
     for i in range(warmup):
         one_step()
     clk_out, clk_fire = clock_probe_start()
@@ -411,6 +473,8 @@ def run_workload(config, steps, warmup, batch, bf16, two_kernel, overlap_flag, n
     loss = float(out["loss"])
     if rank != 0:
         return None
+    if dump_dir:
+        write_outputs(dump_dir, step_outputs(out, fbuf[(it - 1) % 2], trainer))
 
     ms = dt / steps * 1e3
     feat_i = [e[0].elapsed_time(e[1]) for e in ev]
@@ -578,6 +642,10 @@ def main():
         raise SystemExit("--bf16 / --two-kernel apply to cfg2")
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if args.stub and args.dump_outputs:
+        raise SystemExit("--dump-outputs needs the HIP workload (not --stub)")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # plain `python bench.py --gpus N`: this process becomes the launcher (it has not touched the GPU)
@@ -618,12 +686,13 @@ def main():
     env = dict(rank=rank, world=world, dev=dev, backend=backend)
 
     line = run_workload(args.config, args.steps, args.warmup, args.batch, args.bf16, args.two_kernel, args.overlap,
-                        args.no_pipeline, not args.no_hbm_roofline, env, preroll_ms=args.preroll_ms)
-    # The driver's plain `python bench.py` also times BASELINE config 3 (the same workload with bf16 activations and
+                        args.no_pipeline, args.full and not args.no_hbm_roofline, env, preroll_ms=args.preroll_ms,
+                        dump_dir=args.dump_outputs)
+    # `--full` on the default workload also times BASELINE config 3 (the same workload with bf16 activations and
     # gradients) and config 5 (the stress configuration at its own batch of 2048) after the cfg2 fp32 region: `value`
     # stays the cfg2 fp32 number, the other two ride along under "also" (VERDICT r2, item 3).  Each leg has its own
     # pre-roll; the host-only CPU baseline (14 s of scipy, the GPU idle) comes LAST so that no leg starts cold.
-    if world == 1 and (default_call or os.environ.get("ISD_BENCH_ALSO")) and not args.no_also:
+    if args.full and world == 1 and (default_call or os.environ.get("ISD_BENCH_ALSO")) and not args.no_also:
         also = {}
         keep = ("value", "ms_per_step", "stages_ms", "stages_ms_spread", "shader_clock_mhz_timed", "preroll_ms",
                 "preroll_steps", "dtype", "steps", "warmup", "final_loss")
@@ -639,7 +708,7 @@ def main():
         also["cfg5"] = {k: l5[k] for k in keep + ("roofline", "roofline_hbm") if k in l5}
         also["cfg5"]["workload"] = CONFIGS["cfg5"]["workload"]
         line["also"] = also
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(args.config, cfg)
     if rank == 0:
         print(json.dumps(line), flush=True)

@@ -65,6 +65,17 @@ def test_single_rank_needs_no_launcher():
     assert len(lines) == 1 and lines[0]["n_gpus"] == 1
 
 
+def test_steps_set_the_timed_steps_and_must_be_positive():
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "7", "--warmup", "2", "--stub"],
+                       env=_env(), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = _json_lines(r.stdout)[0]
+    assert line["steps"] == 7 and line["warmup"] == 2 and line["ms_per_step"] > 0
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "0", "--stub"], env=_env(),
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
 def test_rank_count_mismatch_is_an_error():
     env = dict(_env(), WORLD_SIZE="3", RANK="0", LOCAL_RANK="0")
     r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--stub"], env=env, capture_output=True, text=True,

@@ -4,11 +4,11 @@ set -e
 R=$PWD
 O=$R/gpurun_out/prof_r4
 mkdir -p $O
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_line_default.json 2> $O/default.err || true
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_line_default.json 2> $O/default.err || true
 cd /tmp && export TMPDIR=/tmp
 for v in "cfg2:" "cfg2_bf16:--bf16" "cfg5:--config cfg5"; do
   name=${v%%:*}; flags=${v#*:}
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/$name -- python3 $R/bench.py --no-cpu-baseline --no-also $flags > $O/${name}_line_profiled.json 2>> $O/${name}.err || true
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/$name -- python3 $R/bench.py --full --no-cpu-baseline --no-also $flags > $O/${name}_line_profiled.json 2>> $O/${name}.err || true
   f=$(ls $O/$name/*/*kernel_stats.csv | tail -1); cp $f $O/${name}_kernel_stats.csv
 done
 cd $R
