@@ -111,6 +111,7 @@ SIGNATURES = {
     "isd_cvblock_plan_create": (_i, [C.POINTER(_p), _i, _i, _i]),
     "isd_cvblock_flat_dim": (_i64, [_p]),
     "isd_eegnet_plan_set_seed_counter": (_i, [_p, _p]),
+    "isd_eegnet_plan_set_input_dtype": (_i, [_p, _i]),
     "isd_eegnet_plan_destroy": (_i, [_p]),
     "isd_eegnet_param_count": (_i64, [_p]),
     "isd_eegnet_buffer_count": (_i64, [_p]),

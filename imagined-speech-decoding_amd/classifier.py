@@ -133,7 +133,7 @@ class HotPath:
         if not isinstance(x, torch.Tensor):
             raise TypeError("x must be a torch tensor")
         if x.dtype == torch.bfloat16:
-            if getattr(self.model._conv(), "act_dtype", "f32") != "bf16":
+            if not self._takes_bf16():
                 raise TypeError("a bfloat16 feature map needs a model with act_dtype='bf16' (BASELINE config 3)")
         elif x.dtype != torch.float32:
             raise TypeError(f"x must be float32 (or bfloat16 for a bf16 model), got {x.dtype}")
@@ -153,6 +153,9 @@ class HotPath:
                 raise ValueError("labels must be a contiguous [batch] vector")
         if not x.is_cuda:
             raise TypeError("x must be a CUDA tensor (the product has no CPU path)")
+
+    def _takes_bf16(self):
+        return getattr(self.model._conv(), "act_dtype", "f32") == "bf16"
 
     def _forward(self, x, labels, global_batch, want_grad):
         m, L = self.model, _lib.lib()
@@ -276,7 +279,12 @@ class EEGNetPath(HotPath):
     """Autograd-free step of  EEGNet_Encoder -> Linear -> softmax-CE  (same contract as ``HotPath``).
 
     With ``want_grad`` the encoder runs in training mode (batch statistics, running buffers and
-    ``num_batches_tracked`` updated, dropout with the module's own counter-based stream); otherwise in eval mode."""
+    ``num_batches_tracked`` updated, dropout with the module's own counter-based stream); otherwise in eval mode.
+    ``x`` may be a bfloat16 map (the long-row extractor's ``out_dtype=torch.bfloat16``): the encoder widens it to fp32
+    on load, exactly, and the step is bit for bit the fp32 step on ``x.float()`` (no input gradient is formed)."""
+
+    def _takes_bf16(self):
+        return True
 
     def _forward(self, x, labels, global_batch, want_grad):
         m, L = self.model, _lib.lib()
@@ -285,7 +293,7 @@ class EEGNetPath(HotPath):
         gflat = m.flat_grads() if want_grad else None
         bufs = enc.flat_buffers()
         B, _, T = x.shape
-        plan = enc._plan_for(T)
+        plan = enc._plan_for(T, x.dtype)
         dev, st = x.device, _stream()
         n_enc = plan.n_params
         F_, n_cls = fc.in_features, fc.out_features
@@ -664,6 +672,10 @@ class FilterbankCNNClassifier(_Estimator):
     def _n_classes(self):
         return int(self.n_classes)
 
+    def _cache_dtype(self):
+        """Element type of the cached training-set features (``_prepare_fit``)."""
+        return torch.float32
+
     def _build(self, X):
         fx = self._extractor(X.shape[-1])
         return _FeatureModel(fx.n_bands * X.shape[1], self.feature_dim, self.n_classes, self.n_layers,
@@ -678,11 +690,12 @@ class FilterbankCNNClassifier(_Estimator):
         batches, resident in HBM: 39 KB per trial at the default shape) and the epochs run on the cached tensor."""
         fx = self._extractor(X.shape[-1])
         n = X.shape[0]
-        need = n * fx.n_bands * X.shape[1] * fx.n_frames * 4
+        dt = self._cache_dtype()
+        need = n * fx.n_bands * X.shape[1] * fx.n_frames * (torch.finfo(dt).bits // 8)
         free = torch.cuda.mem_get_info(X.device)[0]
         if not self.cache_features or self.max_epochs < 2 or need > free // 2:
             return X, self._inputs
-        feats = torch.empty((n, fx.n_bands * X.shape[1], fx.n_frames), dtype=torch.float32, device=X.device)
+        feats = torch.empty((n, fx.n_bands * X.shape[1], fx.n_frames), dtype=dt, device=X.device)
         for i in range(0, n, 4096):
             feats[i:i + 4096] = self._inputs(X[i:i + 4096].contiguous())
         return feats, (lambda fb: fb)
@@ -691,15 +704,28 @@ class FilterbankCNNClassifier(_Estimator):
 class FilterbankEEGNetClassifier(FilterbankCNNClassifier):
     """extract_features -> ``EEGNet_Encoder(nb*C, feature_dim)`` (fast.py:122-167, through the head contract
     fast.py:203-210) -> ``Linear(feature_dim, n_classes)``: BASELINE config 5, the high-resolution stress
-    configuration (128 ch, 4 s @ 1024 Hz, 40 two-hertz bands, 1024-point STFT with hop 64 -> 65 frames)."""
+    configuration (128 ch, 4 s @ 1024 Hz, 40 two-hertz bands, 1024-point STFT with hop 64 -> 65 frames).
+
+    ``precision='bf16'``: the fused extractor writes the feature map as bf16 (the fp32 map rounded to nearest even)
+    and the training-set cache holds it at 2 bytes per value.  The head widens the map to fp32 on load and computes in
+    fp32 throughout, so a step is bit for bit the fp32 step on the rounded map.  This is not the reference's autocast:
+    only the head's input is rounded."""
 
     _param_names = FilterbankCNNClassifier._param_names + ("kernel_length", "dropout")
 
     def __init__(self, fs=1024.0, bands=BANDS_40, nperseg=1024, noverlap=960, kernel_length=64, dropout=0.25, **kw):
         super().__init__(fs=fs, bands=bands, nperseg=nperseg, noverlap=noverlap, **kw)
-        if self.precision != "fp32":
-            raise ValueError("the EEGNet head computes in fp32")
         self.kernel_length, self.dropout = kernel_length, dropout
+
+    def extract_features(self, trials):
+        """trials f32 CUDA [B, C, T] -> [B, nb, C, J], float32 or (``precision='bf16'``) bfloat16 from the fused
+        extractor."""
+        if self.precision != "bf16":
+            return super().extract_features(trials)
+        return self._extractor(trials.shape[-1])(trials, fused=self.fused, out_dtype=torch.bfloat16)
+
+    def _cache_dtype(self):
+        return torch.bfloat16 if self.precision == "bf16" else torch.float32
 
     def _build(self, X):
         fx = self._extractor(X.shape[-1])

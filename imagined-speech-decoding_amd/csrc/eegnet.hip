@@ -24,6 +24,7 @@
 #include <math.h>
 #include <stddef.h>
 #include <string.h>
+#include <type_traits>
 #include <vector>
 
 namespace isd {
@@ -112,6 +113,11 @@ __device__ __forceinline__ float drop_scale(uint64_t seed, uint64_t idx, float p
 __device__ __forceinline__ float elu_f(float y) { return y > 0.f ? y : expm1f(y); }
 __device__ __forceinline__ float elu_grad_f(float y) { return y > 0.f ? 1.f : expf(y); }
 
+// One input element as fp32.  A bf16 input map (isd_eegnet_plan_set_input_dtype) is widened on load, which is exact:
+// the kernels that read x are templated on its element type and everything after the load is the fp32 arithmetic.
+__device__ __forceinline__ float ldx(const float* p) { return *p; }
+__device__ __forceinline__ float ldx(const uint16_t* p) { return __uint_as_float((unsigned)*p << 16); }
+
 // block-wide sum of one float per thread, result valid on thread 0
 __device__ __forceinline__ float block_sum(float v, float* red) {
   v = wave_sum(v);
@@ -145,7 +151,8 @@ constexpr int kStatWaves = 4;                          // waves per workgroup
 //  bulk: D_q and the sum of all samples;  edge: Qh, Qt, Sh, St.
 // The waves of a workgroup meet in LDS (fp32) before ONE set of fp64 global atomics per workgroup: 2048 waves
 // sending 85 atomics per lane to the same ~5 k addresses took 0.15 ms on their own.
-__device__ __forceinline__ void eeg_stats_kernel_body(const float* __restrict__ x,
+template <typename XT>
+__device__ __forceinline__ void eeg_stats_kernel_body(const XT* __restrict__ x,
                                                                     EegStats* __restrict__ st, int64_t rows, int T,
     unsigned zgx, unsigned zgy, unsigned zbz, unsigned zgz) {   // this zone's own gridDim.x/.y, blockIdx.z, gridDim.z
   __shared__ float tot[21][64];
@@ -160,17 +167,17 @@ __device__ __forceinline__ void eeg_stats_kernel_body(const float* __restrict__ 
   // 20 MFMAs run.  Two rows are in flight at once: short rows (the feature classifier's T = 65) are one step each.
   const int64_t stride = (int64_t)zgx * kStatWaves;
   for (int64_t r = (int64_t)blockIdx.x * kStatWaves + wave; r < rows; r += 2 * stride) {
-    const float* srcA = x + r * (int64_t)T;
+    const XT* srcA = x + r * (int64_t)T;
     const bool two = r + stride < rows;                           // wave-uniform
-    const float* srcB = x + (two ? r + stride : r) * (int64_t)T;
+    const XT* srcB = x + (two ? r + stride : r) * (int64_t)T;
     for (int s0 = 0; s0 < T; s0 += 256) {
       float vA[17], vB[17];
 #pragma unroll
       for (int j = 0; j < 17; ++j) {                                // clamped addresses: no test around a load ...
         const int idx = s0 + lane + 16 * j;
         const int ic = idx < T ? idx : T - 1;
-        vA[j] = srcA[ic];
-        vB[j] = srcB[ic];
+        vA[j] = ldx(srcA + ic);
+        vB[j] = ldx(srcB + ic);
       }
 #pragma unroll
       for (int j = 0; j < 17; ++j) {                                // ... the 34 loads are in flight together, then selects
@@ -217,6 +224,12 @@ __global__ __launch_bounds__(64 * kStatWaves) void eeg_stats_kernel(const float*
       gridDim.x, gridDim.y, blockIdx.z, gridDim.z);
 }
 ISD_ZONE_REGISTER(eeg_stats_kernel)
+__global__ __launch_bounds__(64 * kStatWaves) void eeg_stats_kernel_bf16(const uint16_t* __restrict__ x,
+                                                                         EegStats* __restrict__ st, int64_t rows, int T) {
+  eeg_stats_kernel_body(x, st, rows, T,
+      gridDim.x, gridDim.y, blockIdx.z, gridDim.z);
+}
+ISD_ZONE_REGISTER_AS(eeg_stats_kernel_bf16, eeg_stats_kernel)
 
 // Edge sums on the matrix cores.  Per row let y[0..95) be its head window x[0..95) (blockIdx.y = 0) or its tail
 // window x[T-31 .. T+64) (blockIdx.y = 1), zero outside the row.  Everything the zero padding needs is inside the
@@ -225,7 +238,8 @@ ISD_ZONE_REGISTER(eeg_stats_kernel)
 // The contraction runs over ROWS: one MFMA step takes 4 rows (k = lane >> 4), A = y[16 mt + i] (2 tiles),
 // B = y[16 nt + i] (6 tiles), 6 loads and 12 MFMAs per 4 rows, 48 accumulator registers.  (The per-lane form --
 // 62 lag products per lane and row behind an LDS window -- held 200+ VGPRs and paid a memory latency per row.)
-__device__ __forceinline__ void eeg_stats_edge_kernel_body(const float* __restrict__ x,
+template <typename XT>
+__device__ __forceinline__ void eeg_stats_edge_kernel_body(const XT* __restrict__ x,
                                                                          EegStats* __restrict__ st, int64_t rows,
                                                                          int T,
     unsigned zgx, unsigned zgy, unsigned zbz, unsigned zgz) {   // this zone's own gridDim.x/.y, blockIdx.z, gridDim.z
@@ -248,11 +262,11 @@ __device__ __forceinline__ void eeg_stats_edge_kernel_body(const float* __restri
     for (int h = 0; h < 2; ++h) {
       const int64_t r = (g + h * stride) * 4 + q;
       live[h] = g + h * stride < n_grp && r < rows;
-      const float* src = x + (live[h] ? r : 0) * (int64_t)T;
+      const XT* src = x + (live[h] ? r : 0) * (int64_t)T;
 #pragma unroll
       for (int nt = 0; nt < 6; ++nt) {                              // clamped addresses, selects below: no test around a load
         const int t = base + 16 * nt + i;
-        b[h][nt] = src[t < 0 ? 0 : (t < T ? t : T - 1)];
+        b[h][nt] = ldx(src + (t < 0 ? 0 : (t < T ? t : T - 1)));
       }
     }
 #pragma unroll
@@ -296,14 +310,21 @@ __global__ __launch_bounds__(64 * kStatWaves) void eeg_stats_edge_kernel(const f
       gridDim.x, gridDim.y, blockIdx.z, gridDim.z);
 }
 ISD_ZONE_REGISTER(eeg_stats_edge_kernel)
+__global__ __launch_bounds__(64 * kStatWaves) void eeg_stats_edge_kernel_bf16(const uint16_t* __restrict__ x,
+                                                                              EegStats* __restrict__ st, int64_t rows,
+                                                                              int T) {
+  eeg_stats_edge_kernel_body(x, st, rows, T,
+      gridDim.x, gridDim.y, blockIdx.z, gridDim.z);
+}
+ISD_ZONE_REGISTER_AS(eeg_stats_edge_kernel_bf16, eeg_stats_edge_kernel)
 
 // Short rows (T <= 79, e.g. the 65 frames of the stress features): the whole row fits one Gram matrix.  With
 // y = (x[0..T), 1, 0, ...) padded to 16 MT entries, G[a][j] = sum_rows y[a] y[j] holds every lag product
 // (x[s] x[s+d] = G[s][s+d]) and, in column T, the per-sample sums.  Contracted over rows like the edge blocks: MT
 // loads and MT (MT + 1) / 2 MFMAs (upper-triangular tiles) per 4 rows -- 15 at T = 65 against 64 for the bulk + edge
 // pair, one pass over x instead of two.
-template <int MT>
-__device__ __forceinline__ void eeg_stats_gram_kernel_body(const float* __restrict__ x,
+template <int MT, typename XT>
+__device__ __forceinline__ void eeg_stats_gram_kernel_body(const XT* __restrict__ x,
                                                                          EegStats* __restrict__ st, int64_t rows,
                                                                          int T,
     unsigned zgx, unsigned zgy, unsigned zbz, unsigned zgz) {   // this zone's own gridDim.x/.y, blockIdx.z, gridDim.z
@@ -323,11 +344,11 @@ __device__ __forceinline__ void eeg_stats_gram_kernel_body(const float* __restri
     for (int h = 0; h < 2; ++h) {
       const int64_t r = (g + h * stride) * 4 + q;
       const bool live = g + h * stride < n_grp && r < rows;
-      const float* src = x + (live ? r : 0) * (int64_t)T;
+      const XT* src = x + (live ? r : 0) * (int64_t)T;
 #pragma unroll
       for (int t = 0; t < MT; ++t) {                            // clamped address, then selects: no test around a load
         const int idx = 16 * t + i;
-        y[h][t] = src[idx < T ? idx : T - 1];
+        y[h][t] = ldx(src + (idx < T ? idx : T - 1));
       }
 #pragma unroll
       for (int t = 0; t < MT; ++t) {
@@ -373,6 +394,18 @@ ISD_ZONE_REGISTER_T(eeg_stats_gram_kernel, 2)
 ISD_ZONE_REGISTER_T(eeg_stats_gram_kernel, 3)
 ISD_ZONE_REGISTER_T(eeg_stats_gram_kernel, 4)
 ISD_ZONE_REGISTER_T(eeg_stats_gram_kernel, 5)
+template <int MT>
+__global__ __launch_bounds__(64 * kStatWaves) void eeg_stats_gram_kernel_bf16(const uint16_t* __restrict__ x,
+                                                                              EegStats* __restrict__ st, int64_t rows,
+                                                                              int T) {
+  eeg_stats_gram_kernel_body<MT>(x, st, rows, T,
+      gridDim.x, gridDim.y, blockIdx.z, gridDim.z);
+}
+ISD_ZONE_REGISTER_T_AS(eeg_stats_gram_kernel_bf16, eeg_stats_gram_kernel, 1)
+ISD_ZONE_REGISTER_T_AS(eeg_stats_gram_kernel_bf16, eeg_stats_gram_kernel, 2)
+ISD_ZONE_REGISTER_T_AS(eeg_stats_gram_kernel_bf16, eeg_stats_gram_kernel, 3)
+ISD_ZONE_REGISTER_T_AS(eeg_stats_gram_kernel_bf16, eeg_stats_gram_kernel, 4)
+ISD_ZONE_REGISTER_T_AS(eeg_stats_gram_kernel_bf16, eeg_stats_gram_kernel, 5)
 
 // Gs -> the quantities eeg_finalize1_kernel consumes (same definitions as eeg_stats_derive_kernel: samples outside
 // the row are zero).  One block of 64 threads (thread = lag d).
@@ -548,7 +581,8 @@ ISD_ZONE_REGISTER(eeg_finalize1_kernel)
 // MFMA.  One workgroup per (trial, time tile); its four waves take a quarter of the channels each (16 channels =
 // 8 loads and 4 independent MFMA chains per step) and meet in LDS in a fixed order.  (One wave per tile walking
 // all channels left 640 waves on the chip at C = 5120, T = 65: 0.29 ms; the scalar version before it 2.3 ms.)
-__device__ __forceinline__ void eeg_spatial_kernel_body(const float* __restrict__ x, const float* __restrict__ Ws,
+template <typename XT>
+__device__ __forceinline__ void eeg_spatial_kernel_body(const XT* __restrict__ x, const float* __restrict__ Ws,
                                                           float* __restrict__ z, int C, int T, int n_tiles,
     unsigned zgx, unsigned zgy, unsigned zbz, unsigned zgz) {   // this zone's own gridDim.x/.y, blockIdx.z, gridDim.z
   __shared__ float red[3][4][64];
@@ -557,7 +591,7 @@ __device__ __forceinline__ void eeg_spatial_kernel_body(const float* __restrict_
   const int b = blockIdx.y;
   const int t = tile * 16 + jl;
   const bool tv = t < T;
-  const float* xb = x + (int64_t)b * C * T + (tv ? t : 0);
+  const XT* xb = x + (int64_t)b * C * T + (tv ? t : 0);
   const float* wr = Ws + jl * C;
   const int cq = ((C + 15) / 16) * 4;                           // channels per wave, a multiple of 4
   const int c_lo = wave * cq, c_hi = c_lo + cq < C ? c_lo + cq : C;
@@ -574,7 +608,7 @@ __device__ __forceinline__ void eeg_spatial_kernel_body(const float* __restrict_
     for (int k = 0; k < 16; ++k) {
       const int c = c0 + 4 * k + q;
       av[k] = wr[c];
-      bv[k] = xb[(int64_t)c * T];
+      bv[k] = ldx(xb + (int64_t)c * T);
     }
 #pragma unroll
     for (int k = 0; k < 16; ++k)
@@ -586,7 +620,7 @@ __device__ __forceinline__ void eeg_spatial_kernel_body(const float* __restrict_
     for (int k = 0; k < 4; ++k) {
       const int c = c0 + 4 * k + q;
       av[k] = wr[c];
-      bv[k] = xb[(int64_t)c * T];
+      bv[k] = ldx(xb + (int64_t)c * T);
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) acc[k] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[k], tv ? bv[k] : 0.f, acc[k], 0, 0, 0);
@@ -595,7 +629,7 @@ __device__ __forceinline__ void eeg_spatial_kernel_body(const float* __restrict_
     const int c = c0 + q;
     const bool cv = c < c_hi;
     const float a0 = cv ? wr[c] : 0.f;
-    const float b0 = (cv && tv) ? xb[(int64_t)c * T] : 0.f;
+    const float b0 = (cv && tv) ? ldx(xb + (int64_t)c * T) : 0.f;
     acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, acc[0], 0, 0, 0);
   }
   f32x4 sum;
@@ -619,20 +653,27 @@ __global__ __launch_bounds__(256) void eeg_spatial_kernel(const float* __restric
       gridDim.x, gridDim.y, blockIdx.z, gridDim.z);
 }
 ISD_ZONE_REGISTER(eeg_spatial_kernel)
+__global__ __launch_bounds__(256) void eeg_spatial_kernel_bf16(const uint16_t* __restrict__ x,
+                                                               const float* __restrict__ Ws, float* __restrict__ z,
+                                                               int C, int T, int n_tiles) {
+  eeg_spatial_kernel_body(x, Ws, z, C, T, n_tiles,
+      gridDim.x, gridDim.y, blockIdx.z, gridDim.z);
+}
+ISD_ZONE_REGISTER_AS(eeg_spatial_kernel_bf16, eeg_spatial_kernel)
 
 // The same product for wide inputs (hundreds of channels: the stress configuration's 5120 x 65 feature maps): one
 // workgroup takes NTG consecutive time tiles of a trial, so every x row is read whole by ONE workgroup (with a
 // workgroup per tile the five 64-byte pieces of a 260-byte row went to five workgroups on five XCDs, each pulling the
 // row's cache lines into its own L2) and a Ws fragment serves NTG MFMAs instead of one.
-template <int NTG>
-__device__ __forceinline__ void eeg_spatial_rows_kernel_body(const float* __restrict__ x, const float* __restrict__ Ws,
+template <int NTG, typename XT>
+__device__ __forceinline__ void eeg_spatial_rows_kernel_body(const XT* __restrict__ x, const float* __restrict__ Ws,
                                                                float* __restrict__ z, int C, int T,
     unsigned zgx, unsigned zgy, unsigned zbz, unsigned zgz) {   // this zone's own gridDim.x/.y, blockIdx.z, gridDim.z
   __shared__ float red[3][NTG][4][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane >> 4, jl = lane & 15;
   const int b = blockIdx.y;
   bool tv[NTG];
-  const float* xb[NTG];
+  const XT* xb[NTG];
 #pragma unroll
   for (int j = 0; j < NTG; ++j) {
     const int t = (blockIdx.x * NTG + j) * 16 + jl;
@@ -653,7 +694,7 @@ __device__ __forceinline__ void eeg_spatial_rows_kernel_body(const float* __rest
       const int c = c0 + 4 * k + q;
       av[k] = wr[c];
 #pragma unroll
-      for (int j = 0; j < NTG; ++j) bv[k][j] = xb[j][(int64_t)c * T];
+      for (int j = 0; j < NTG; ++j) bv[k][j] = ldx(xb[j] + (int64_t)c * T);
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k)
@@ -668,7 +709,7 @@ __device__ __forceinline__ void eeg_spatial_rows_kernel_body(const float* __rest
     const float a0 = cv ? wr[cc] : 0.f;
 #pragma unroll
     for (int j = 0; j < NTG; ++j) {
-      const float b0 = xb[j][(int64_t)cc * T];
+      const float b0 = ldx(xb[j] + (int64_t)cc * T);
       acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, (cv && tv[j]) ? b0 : 0.f, acc[j], 0, 0, 0);
     }
   }
@@ -700,6 +741,14 @@ __global__ __launch_bounds__(256) void eeg_spatial_rows_kernel(const float* __re
       gridDim.x, gridDim.y, blockIdx.z, gridDim.z);
 }
 ISD_ZONE_REGISTER_T(eeg_spatial_rows_kernel, 5)
+template <int NTG>
+__global__ __launch_bounds__(256) void eeg_spatial_rows_kernel_bf16(const uint16_t* __restrict__ x,
+                                                                    const float* __restrict__ Ws,
+                                                                    float* __restrict__ z, int C, int T) {
+  eeg_spatial_rows_kernel_body<NTG>(x, Ws, z, C, T,
+      gridDim.x, gridDim.y, blockIdx.z, gridDim.z);
+}
+ISD_ZONE_REGISTER_T_AS(eeg_spatial_rows_kernel_bf16, eeg_spatial_rows_kernel, 5)
 
 // u[b,g,t'] = sum_k Wt[f,k] zpad[b,g,t'+k]; per-g sums of u and u^2 (fp64 atomics).  grid (ceil(Tp/256), B*16)
 // KT: the filter length as a compile-time constant (16 / 32 / 64: fully unrolled tap loops without a test per tap -- a
@@ -1405,18 +1454,26 @@ ISD_ZONE_REGISTER_T(eeg_bwd_corr_kernel, 0)
 // the pass outermost a row's lines were revisited ~20 us later, after 25 MB of other waves' rows per XCD had gone
 // through its 4 MB L2: the kernel ran at 2 TB/s whatever the load width.
 typedef float F4U __attribute__((ext_vector_type(4), aligned(4)));   // four floats at any dword address
+typedef unsigned short H4U __attribute__((ext_vector_type(4), aligned(2)));   // four bf16 at any 2-byte address
 constexpr int kDwsPasses = 5;
-__device__ __forceinline__ void dws_load_row(const float* __restrict__ row, int t_lo, int t_hi, int q, bool zero_tail,
+template <typename XT>
+__device__ __forceinline__ void dws_load_row(const XT* __restrict__ row, int t_lo, int t_hi, int q, bool zero_tail,
                                              float (&f)[kDwsPasses][4]) {
 #pragma unroll
   for (int p = 0; p < kDwsPasses; ++p) {
     const int t0 = t_lo + 16 * p, t = t0 + 4 * q;
     if (t0 + 16 <= t_hi) {                                  // wave-uniform: every lane's four steps lie inside the row
-      const F4U w = *reinterpret_cast<const F4U*>(row + t);
-      f[p][0] = w.x; f[p][1] = w.y; f[p][2] = w.z; f[p][3] = w.w;
+      if constexpr (std::is_same<XT, float>::value) {
+        const F4U w = *reinterpret_cast<const F4U*>(row + t);
+        f[p][0] = w.x; f[p][1] = w.y; f[p][2] = w.z; f[p][3] = w.w;
+      } else {                                              // bf16 rows: one 8-byte load, widened
+        const H4U w = *reinterpret_cast<const H4U*>(row + t);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) f[p][e] = __uint_as_float((unsigned)w[e] << 16);
+      }
     } else {                                                // clamped addresses (and selects): no test around a load
 #pragma unroll
-      for (int e = 0; e < 4; ++e) f[p][e] = row[t + e < t_hi ? t + e : t_hi - 1];
+      for (int e = 0; e < 4; ++e) f[p][e] = ldx(row + (t + e < t_hi ? t + e : t_hi - 1));
       if (zero_tail) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) f[p][e] = t + e < t_hi ? f[p][e] : 0.f;
@@ -1424,7 +1481,8 @@ __device__ __forceinline__ void dws_load_row(const float* __restrict__ row, int 
     }
   }
 }
-__device__ __forceinline__ void eeg_bwd_dws_kernel_body(const float* __restrict__ v, const float* __restrict__ x,
+template <typename XT>
+__device__ __forceinline__ void eeg_bwd_dws_kernel_body(const float* __restrict__ v, const XT* __restrict__ x,
                                                          float* __restrict__ part, int B, int C, int T,
     unsigned zgx, unsigned zgy, unsigned zbz, unsigned zgz) {   // this zone's own gridDim.x/.y, blockIdx.z, gridDim.z
   const int lane = threadIdx.x, q = lane >> 4, jl = lane & 15;
@@ -1481,6 +1539,12 @@ __global__ __launch_bounds__(64) void eeg_bwd_dws_kernel(const float* __restrict
       gridDim.x, gridDim.y, blockIdx.z, gridDim.z);
 }
 ISD_ZONE_REGISTER(eeg_bwd_dws_kernel)
+__global__ __launch_bounds__(64) void eeg_bwd_dws_kernel_bf16(const float* __restrict__ v, const uint16_t* __restrict__ x,
+                                                              float* __restrict__ part, int B, int C, int T) {
+  eeg_bwd_dws_kernel_body(v, x, part, B, C, T,
+      gridDim.x, gridDim.y, blockIdx.z, gridDim.z);
+}
+ISD_ZONE_REGISTER_AS(eeg_bwd_dws_kernel_bf16, eeg_bwd_dws_kernel)
 
 // dWs[g,c] = s1[f] * sum_slabs raw + o1[f] * Sd[g].  Block = 64 elements x 16 slab groups (coalesced 256-B rows, two
 // independent chains per group, LDS combine in a fixed order): one thread per element walking up to 1024 slabs on
@@ -1940,6 +2004,7 @@ struct isd_eegnet_plan {
   int P1, P2;      // AvgPool widths of the two stages
   EegOff off;
   const unsigned long long* seed_dev;   // optional device-resident dropout step counter (isd_eegnet_plan_set_seed_counter)
+  int xdt;         // element type of x: ISD_ACT_F32 or ISD_ACT_BF16 (isd_eegnet_plan_set_input_dtype)
 };
 
 static inline int64_t al64(int64_t v) { return (v + 63) / 64 * 64; }
@@ -1999,6 +2064,13 @@ static int eeg_plan_create(isd_eegnet_plan** out, int in_channels, int feature_d
 extern "C" int isd_eegnet_plan_set_seed_counter(isd_eegnet_plan* p, const uint64_t* seed_dev) {
   ISD_CHECK_ARG(p, "isd_eegnet_plan_set_seed_counter: null plan");
   p->seed_dev = (const unsigned long long*)seed_dev;
+  return ISD_OK;
+}
+
+extern "C" int isd_eegnet_plan_set_input_dtype(isd_eegnet_plan* p, int dtype) {
+  ISD_CHECK_ARG(p, "isd_eegnet_plan_set_input_dtype: null plan");
+  ISD_CHECK_ARG(dtype == ISD_ACT_F32 || dtype == ISD_ACT_BF16, "isd_eegnet_plan_set_input_dtype: dtype=%d", dtype);
+  p->xdt = dtype;
   return ISD_OK;
 }
 
@@ -2091,6 +2163,8 @@ static int eeg_forward_stage(const isd_eegnet_plan* p, int stage, const float* x
   // needs (input attributions differentiate the eval-mode network)
   const int keep = training != 0;
   training &= 1;
+  const bool x16 = p->xdt == ISD_ACT_BF16;
+  const uint16_t* xh = reinterpret_cast<const uint16_t*>(x);
   if (stage == 0) {
     ISD_HIP_TRY(zone_clear(S, sizeof(EegStats), st));
     if (training) {
@@ -2098,13 +2172,19 @@ static int eeg_forward_stage(const isd_eegnet_plan* p, int stage, const float* x
         const int MT = (T + 16) / 16;                              // 16 MT >= T + 1: room for the column of ones
         const int64_t want_g = cdiv(cdiv(rows, 4), (int64_t)kStatWaves * 8);   // >= 8 row groups per wave (see below)
         const int grid_g = want_g < 1024 ? (int)want_g : 1024;
+#define ISD_EEG_GRAM(M_)                                                                                          \
+  do {                                                                                                            \
+    if (x16) ISD_ZLAUNCH(eeg_stats_gram_kernel_bf16<M_>, dim3(grid_g), dim3(64 * kStatWaves), 0, st, xh, S, rows, T); \
+    else ISD_ZLAUNCH(eeg_stats_gram_kernel<M_>, dim3(grid_g), dim3(64 * kStatWaves), 0, st, x, S, rows, T);        \
+  } while (0)
         switch (MT) {
-          case 1: ISD_ZLAUNCH(eeg_stats_gram_kernel<1>, dim3(grid_g), dim3(64 * kStatWaves), 0, st, x, S, rows, T); break;
-          case 2: ISD_ZLAUNCH(eeg_stats_gram_kernel<2>, dim3(grid_g), dim3(64 * kStatWaves), 0, st, x, S, rows, T); break;
-          case 3: ISD_ZLAUNCH(eeg_stats_gram_kernel<3>, dim3(grid_g), dim3(64 * kStatWaves), 0, st, x, S, rows, T); break;
-          case 4: ISD_ZLAUNCH(eeg_stats_gram_kernel<4>, dim3(grid_g), dim3(64 * kStatWaves), 0, st, x, S, rows, T); break;
-          default: ISD_ZLAUNCH(eeg_stats_gram_kernel<5>, dim3(grid_g), dim3(64 * kStatWaves), 0, st, x, S, rows, T); break;
+          case 1: ISD_EEG_GRAM(1); break;
+          case 2: ISD_EEG_GRAM(2); break;
+          case 3: ISD_EEG_GRAM(3); break;
+          case 4: ISD_EEG_GRAM(4); break;
+          default: ISD_EEG_GRAM(5); break;
         }
+#undef ISD_EEG_GRAM
         ISD_ZLAUNCH(eeg_stats_gram_derive_kernel, dim3(1), dim3(64), 0, st, S, T);
       } else {
         // every workgroup ends with 1280 (bulk) / 3072 (edge) fp64 atomics on the plan's accumulators: give a wave at
@@ -2112,10 +2192,12 @@ static int eeg_forward_stage(const isd_eegnet_plan* p, int stage, const float* x
         // heads' zone shape sent 6.5 M of them per launch: 0.2 ms for 20 MB of input)
         const int64_t want = cdiv(rows, (int64_t)kStatWaves * 16);
         const int grid = want < 2048 ? (int)want : 2048;             // bulk: 32 waves per CU
-        ISD_ZLAUNCH(eeg_stats_kernel, dim3(grid), dim3(64 * kStatWaves), 0, st, x, S, rows, T);
+        if (x16) ISD_ZLAUNCH(eeg_stats_kernel_bf16, dim3(grid), dim3(64 * kStatWaves), 0, st, xh, S, rows, T);
+        else ISD_ZLAUNCH(eeg_stats_kernel, dim3(grid), dim3(64 * kStatWaves), 0, st, x, S, rows, T);
         const int64_t want_e = cdiv(cdiv(rows, 4), (int64_t)kStatWaves * 8);
         const int grid_e = want_e < 512 ? (int)want_e : 512;         // edge: 4 rows per MFMA step, head and tail blocks
-        ISD_ZLAUNCH(eeg_stats_edge_kernel, dim3(grid_e, 2), dim3(64 * kStatWaves), 0, st, x, S, rows, T);
+        if (x16) ISD_ZLAUNCH(eeg_stats_edge_kernel_bf16, dim3(grid_e, 2), dim3(64 * kStatWaves), 0, st, xh, S, rows, T);
+        else ISD_ZLAUNCH(eeg_stats_edge_kernel, dim3(grid_e, 2), dim3(64 * kStatWaves), 0, st, x, S, rows, T);
         ISD_ZLAUNCH(eeg_stats_derive_kernel, dim3(1), dim3(64), 0, st, S);
       }
     }
@@ -2125,9 +2207,15 @@ static int eeg_forward_stage(const isd_eegnet_plan* p, int stage, const float* x
   if (stage == 1) {
     ISD_ZLAUNCH(eeg_finalize1_kernel, dim3(1), dim3(256), 0, st, params, buffers, S, Cf, p->off, C, K, T,
                        rows * world, training, momentum, eps, p->seed_dev);
-    if (C >= 128)                                               // wide inputs: whole rows per workgroup
+    if (C >= 128 && x16)                                        // wide inputs: whole rows per workgroup
+      ISD_ZLAUNCH(eeg_spatial_rows_kernel_bf16<5>, dim3((unsigned)cdiv(cdiv(T, 16), 5), (unsigned)B), dim3(256), 0, st,
+                         xh, params + p->off.Ws, ws + w.z, C, T);
+    else if (C >= 128)
       ISD_ZLAUNCH(eeg_spatial_rows_kernel<5>, dim3((unsigned)cdiv(cdiv(T, 16), 5), (unsigned)B), dim3(256), 0, st,
                          x, params + p->off.Ws, ws + w.z, C, T);
+    else if (x16)
+      ISD_ZLAUNCH(eeg_spatial_kernel_bf16, dim3((unsigned)cdiv(T, 16), (unsigned)B), dim3(256), 0, st, xh,
+                         params + p->off.Ws, ws + w.z, C, T, (int)cdiv(T, 16));
     else
       ISD_ZLAUNCH(eeg_spatial_kernel, dim3((unsigned)cdiv(T, 16), (unsigned)B), dim3(256), 0, st, x,
                          params + p->off.Ws, ws + w.z, C, T, (int)cdiv(T, 16));
@@ -2278,8 +2366,12 @@ static int eeg_backward_stage(const isd_eegnet_plan* p, int stage, const float* 
     }
     const int64_t n_chunks = B * ((T + kDwsPasses * 16 - 1) / (kDwsPasses * 16));
     const int slabs = n_chunks < w.n_slabs ? (int)n_chunks : w.n_slabs;
-    ISD_ZLAUNCH(eeg_bwd_dws_kernel, dim3(slabs, (unsigned)cdiv(C, 256)), dim3(64), 0, st, ws + w.v, x, ws + w.part,
-                       (int)B, C, T);
+    if (p->xdt == ISD_ACT_BF16)
+      ISD_ZLAUNCH(eeg_bwd_dws_kernel_bf16, dim3(slabs, (unsigned)cdiv(C, 256)), dim3(64), 0, st, ws + w.v,
+                  reinterpret_cast<const uint16_t*>(x), ws + w.part, (int)B, C, T);
+    else
+      ISD_ZLAUNCH(eeg_bwd_dws_kernel, dim3(slabs, (unsigned)cdiv(C, 256)), dim3(64), 0, st, ws + w.v, x, ws + w.part,
+                         (int)B, C, T);
     // dWs takes the LOCAL sum of da2 (it is linear in the local batch): it runs in front of the all-reduce of B2
     ISD_ZLAUNCH(eeg_bwd_dws_reduce_kernel, dim3((unsigned)cdiv((int64_t)kF2 * C, 64)), dim3(1024), 0, st,
                        ws + w.part, slabs, S, Cf, dparams + p->off.Ws, C);
@@ -2321,6 +2413,11 @@ extern "C" int isd_eegnet_backward_x(const isd_eegnet_plan* p, const float* x, c
                                      float dropout_p, uint64_t seed, void* stream) {
   int rc = eeg_backward_check(p, x, params, dout, dparams, workspace, B, 1);
   if (rc) return rc;
+  if (p->xdt != ISD_ACT_F32) {
+    set_error("isd_eegnet_backward_x: the plan reads bf16 inputs (isd_eegnet_plan_set_input_dtype); input gradients "
+              "need an fp32 plan");
+    return ISD_ERR_UNSUPPORTED;
+  }
   ISD_CHECK_ARG(dx, "isd_eegnet_backward_x: null dx");
   ISD_CHECK_ARG(training == 1 || training == 2, "isd_eegnet_backward_x: training=%d (1: batch statistics, 2: eval + kept)",
                 training);

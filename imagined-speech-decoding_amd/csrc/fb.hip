@@ -1002,7 +1002,8 @@ void fused_long_kernel(const FbSec* __restrict__ secs, const FbBand* __restrict_
                                                         const float* __restrict__ x, float* __restrict__ feat, int C,
                                                         int T, int nb, int ns, int J, int log2_nblk, int n_bins_max,
                                                         float scale2, FusedBands fbnd, int mode, float eps,
-                                                        const int* __restrict__ bmap, int nb_out, int n_rows) {
+                                                        const int* __restrict__ bmap, int nb_out, int n_rows,
+                                                        int out16) {
   using O = VOps<VT>;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int lane = threadIdx.x;
@@ -1100,8 +1101,10 @@ void fused_long_kernel(const FbSec* __restrict__ secs, const FbBand* __restrict_
     float2 S[KB];
 #pragma unroll
     for (int kk = 0; kk < KB; ++kk) S[kk] = Sblk[kk * 64 + lane];
+    // out16: feat is the bf16 map [B][nb_out][C][J] (byte offset formed as in fused_serial_kernel)
+    const int64_t oi = (((int64_t)bt * nb_out + bmap[b]) * C + ch) * (int64_t)J;
     blocksum_finish<KB>(S, tw, lane, k0, nbin, nblk, J, scale2, mode, eps,
-                        feat + (((int64_t)bt * nb_out + bmap[b]) * C + ch) * (int64_t)J);
+                        reinterpret_cast<char*>(feat) + (oi << (out16 ? 1 : 2)), out16);
     wave_lds_sync();
   }
 }
@@ -1171,7 +1174,7 @@ void fused_rows4_kernel(const FbSec* __restrict__ secs, const FbBand* __restrict
                         const float* __restrict__ x, float* __restrict__ feat, int C,
                         int T, int nb, int ns, int J, int log2_nblk, int n_bins_max,
                         float scale2, FusedBands fbnd, int mode, float eps,
-                        const int* __restrict__ bmap, int nb_out, int n_rows, int share_n) {
+                        const int* __restrict__ bmap, int nb_out, int n_rows, int share_n, int out16) {
   using O = VOps<VT>;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int lane0 = threadIdx.x;
@@ -1201,7 +1204,8 @@ void fused_rows4_kernel(const FbSec* __restrict__ secs, const FbBand* __restrict
     const int row = row_ok ? quad * 4 + q : n_rows - 1;                    // a missing row recomputes the last one
     const float4* src4 = reinterpret_cast<const float4*>(x + row * (int64_t)T + li * kL);
     const int bt = row / C, ch = row - bt * C;
-    float* out = feat + (((int64_t)bt * nb_out + bmap[b]) * C + ch) * (int64_t)J;
+    // out16: feat is the bf16 map [B][nb_out][C][J] (byte offset formed as in fused_serial_kernel)
+    char* out = reinterpret_cast<char*>(feat) + ((((int64_t)bt * nb_out + bmap[b]) * C + ch) * (int64_t)J << (out16 ? 1 : 2));
     const int klo = fbnd.klo[b], khi = fbnd.khi[b];
     const int k0 = klo - 1, nbin = khi - klo + 1;
     if (NS == 0 && lane < ns * 8) carry[lane] = 0.0;
@@ -1376,7 +1380,7 @@ void fused_rows4_kernel(const FbSec* __restrict__ secs, const FbBand* __restrict
         }
         float r = nbin > 0 ? acc / (float)nbin : 0.f;
         if (mode == ISD_BP_LOGPOWER) r = logf(r + eps);
-        if (row_ok && j >= 0 && j < J) out[j] = r;
+        if (row_ok && j >= 0 && j < J) store_feat(out, j, r, out16);
       }
       wave_lds_sync();                                   // the ring slots this round read may be overwritten next pass
     }
@@ -2034,11 +2038,6 @@ static int features_fused_impl(const isd_fb_plan* fb, const isd_stft_plan* st, c
   if (B == 0) return ISD_OK;
   ISD_CHECK_ARG(B * C <= kMaxRows, "isd_features_fused: too many rows (%lld)", (long long)(B * C));
   hipStream_t s = (hipStream_t)stream;
-  if (!short_rows && out16) {
-    set_error("isd_features_fused_bf16: bf16 feature maps are written by the short-row extractor only "
-              "(nperseg=64/noverlap=32/T<=1024)");
-    return ISD_ERR_UNSUPPORTED;
-  }
   if (!short_rows) {
     g_fused_path = 3;
     // long rows, heavily overlapped frames: filterbank + block sums in one kernel per band set
@@ -2067,7 +2066,8 @@ static int features_fused_impl(const isd_fb_plan* fb, const isd_stft_plan* st, c
 #define ISD_FL_LAUNCH2(VT, K, V)                                                                                      \
   hipLaunchKernelGGL((fused_long_kernel<VT, K, V>), dim3((unsigned)(cdiv(rows, 8) * 8 * kLongShare)), dim3(64), lds, s, \
                      fs.d_sec, fs.d_band, fs.d_Q, st->d_blk, x, feat, (int)C, st->T, fs.nb, fb->n_sections, st->J,      \
-                     log2_nblk, st->n / 2, st->scale * st->scale, fbnd, mode, eps, fs.d_map, fb->n_bands, (int)rows)
+                     log2_nblk, st->n / 2, st->scale * st->scale, fbnd, mode, eps, fs.d_map, fb->n_bands, (int)rows, \
+                     out16)
       // rows of whole 512-sample passes covering all 64 blocks: four rows per wave, no cross-group chain
       const bool rows4 = vec && st->T % kSeg == 0 && log2_nblk <= 4 && log2_nblk >= 1 && rows4_enabled();
       const size_t lds4 = sizeof(float2) * ((size_t)4 * KB * 32 + 64) + sizeof(double) * (8 + 64) * (size_t)fb->n_sections;
@@ -2079,7 +2079,7 @@ static int features_fused_impl(const isd_fb_plan* fb, const isd_stft_plan* st, c
     hipLaunchKernelGGL((fused_rows4_kernel<VT, K, N>), dim3((unsigned)(cdiv(cdiv(rows, 4), 8) * 8 * share4)), dim3(64),   \
                        lds4, s, fs.d_sec, fs.d_band, fs.d_Q, st->d_blk, x, feat, (int)C, st->T, fs.nb, fb->n_sections,  \
                        st->J, log2_nblk, st->n / 2, st->scale * st->scale, fbnd, mode, eps, fs.d_map, fb->n_bands,      \
-                       (int)rows, share4);                                                                            \
+                       (int)rows, share4, out16);                                                                     \
   } while (0)
       // fp32 instance with the usual four sections (order-4 Butterworth band-pass): the carried states in registers
 #define ISD_FL_LAUNCH4(VT, K)                                                                           \

@@ -19,16 +19,28 @@ namespace isd {
 constexpr int kMaxBands = 64;
 
 #if defined(__HIPCC__)
+// Feature j of a map row: fp32, or (out16) bf16 rounded to nearest even -- the gfx950 conversion fused_serial_kernel
+// uses.  A bf16 row of the long-row extractor is 2 J = 130 bytes, so its start is only 2-byte aligned: 2-byte stores.
+__device__ __forceinline__ void store_feat(void* __restrict__ row, int j, float r, int out16) {
+  if (out16) {
+    unsigned pk;
+    asm("v_cvt_pk_bf16_f32 %0, %1, %1" : "=v"(pk) : "v"(r));
+    reinterpret_cast<unsigned short*>(row)[j] = (unsigned short)pk;
+  } else {
+    reinterpret_cast<float*>(row)[j] = r;
+  }
+}
+
 // Last stage of the block-sum band power (stft.hip bandpower_blocksum_kernel, fb.hip fused_long_kernel).
 // In: lane m holds S[kk] = sum_{t in block m} y[t] e^{-2 pi i (k0+kk) (t - 64 m... block-local phase)} -- the per-block DFT
 // sums with BLOCK-LOCAL phase for bins k0 .. k0+KB-1 (k0 = klo - 1); tw[u] = e^{-2 pi i u / nblk} in LDS.
 // Applies the absolute block phase, forms the two sliding-window sums over lanes (zero fill outside [0, 64)),
 // combines the Hann neighbours per frame and writes out_row[j], j < J (frame j = lane; frame 64 in a second,
-// wave-uniform pass so that every lane takes part in the shuffles).
+// wave-uniform pass so that every lane takes part in the shuffles).  out_row is fp32, or bf16 when out16 (store_feat).
 template <int KB>
 __device__ __forceinline__ void blocksum_finish(const float2 (&S)[KB], const float2* tw, int lane, int k0, int nbin,
                                                 int nblk, int J, float scale2, int mode, float eps,
-                                                float* __restrict__ out_row) {
+                                                void* __restrict__ out_row, int out16 = 0) {
   const int half = nblk >> 1;
   float2 Cw[KB], Bw[KB];
 #pragma unroll
@@ -74,7 +86,7 @@ __device__ __forceinline__ void blocksum_finish(const float2 (&S)[KB], const flo
     }
     float r = nbin > 0 ? acc / (float)nbin : 0.f;
     if (mode == ISD_BP_LOGPOWER) r = logf(r + eps);
-    if (j < J) out_row[j] = r;
+    if (j < J) store_feat(out_row, j, r, out16);
   }
 }
 #endif

@@ -150,7 +150,8 @@ inline hipError_t zone_clear(void* ptr, size_t bytes, hipStream_t st) {
 // A zone-batchable kernel NAME: `NAME_body(params..., zgx, zgy, zbz, zgz)` is the __device__ body (zgx / zgy / zgz
 // stand for gridDim.x / .y / .z of the zone's own launch, zbz for its blockIdx.z).  ISD_ZONE_FN defines the functor the
 // multi-zone kernel calls, ISD_ZONE_REGISTER ties it to the plain __global__ entry point (kernel templates:
-// ISD_ZONE_FN_T, then one ISD_ZONE_REGISTER_T per instantiation that is launched).
+// ISD_ZONE_FN_T, then one ISD_ZONE_REGISTER_T per instantiation that is launched; further entry points onto the same
+// body: ISD_ZONE_REGISTER_AS / ISD_ZONE_REGISTER_T_AS).
 #define ISD_ZONE_FN(NAME, BOUNDS)                                                        \
   struct NAME##_zfn {                                                                    \
     static constexpr int kBounds = BOUNDS;                                               \
@@ -171,6 +172,13 @@ auto zone_zip_of(void (*)(P...)) -> hipError_t (*)(int, const ZoneOp* const*, hi
   };
 #define ISD_ZONE_REGISTER_T(NAME, V) \
   static ZoneRegistrar NAME##_zreg_##V(reinterpret_cast<const void*>(&NAME<V>), zone_zip_of<NAME##_zfn<V>>(&NAME<V>));
+// a second entry point KERNEL onto the body of NAME -- e.g. an instance for another input element type, which the
+// body (a function template) deduces from its arguments
+#define ISD_ZONE_REGISTER_AS(KERNEL, NAME) \
+  static ZoneRegistrar KERNEL##_zreg(reinterpret_cast<const void*>(&KERNEL), zone_zip_of<NAME##_zfn>(&KERNEL));
+#define ISD_ZONE_REGISTER_T_AS(KERNEL, NAME, V)                                                      \
+  static ZoneRegistrar KERNEL##_zreg_##V(reinterpret_cast<const void*>(&KERNEL<V>),                  \
+                                         zone_zip_of<NAME##_zfn<V>>(&KERNEL<V>));
 #endif  // __HIPCC__
 
 }  // namespace isd

@@ -155,8 +155,10 @@ class FeatureExtractor:
 
     def __call__(self, x, fused=None, out=None, out_dtype=None):
         """x f32 CUDA [B, C, T] -> f32 CUDA [B, n_bands, C, J].  ``out_dtype=torch.bfloat16`` (or a bf16 ``out``): the
-        fused extractor writes the map as bf16, round to nearest even -- BASELINE config 3, what the bf16 classifier
-        (``HotPath`` of a model with ``act_dtype='bf16'``) and the reference's autocast round its input to anyway."""
+        fused extractor writes the map as bf16, the fp32 map's values rounded to nearest even.  Short rows: BASELINE
+        config 3, what the bf16 classifier (``HotPath`` of a model with ``act_dtype='bf16'``) and the reference's
+        autocast round its input to anyway.  Long rows (the stress configuration): the map an ``EEGNet_Encoder`` /
+        ``CVBlock`` reads as bf16 and widens exactly to fp32 (``FilterbankEEGNetClassifier(precision='bf16')``)."""
         _require_cuda(x, "trials")
         B, Cc, T = x.shape
         if T != self.stft.T:

@@ -203,8 +203,16 @@ class _SoftmaxCEFn(torch.autograd.Function):
         return dlt * g, None, None
 
 
+_HEAD_X_DTYPES = {torch.float32: 0, torch.bfloat16: 1}    # ISD_ACT_F32 / ISD_ACT_BF16
+
+
 class EEGNetPlan:
-    def __init__(self, in_channels, feature_dim, kernel_length, T, cvblock=False):
+    """isd_eegnet_plan wrapper.  ``dtype``: element type of the input x, float32 or bfloat16 (a bf16 map is widened
+    to fp32 on load, exactly; the head's arithmetic is the fp32 one)."""
+
+    def __init__(self, in_channels, feature_dim, kernel_length, T, cvblock=False, dtype=torch.float32):
+        if dtype not in _HEAD_X_DTYPES:
+            raise TypeError(f"the EEGNet / CVBlock input is float32 or bfloat16, got {dtype}")
         self._h = C.c_void_p()
         if cvblock:
             _lib.check(_lib.lib().isd_cvblock_plan_create(C.byref(self._h), int(in_channels), int(feature_dim), int(T)))
@@ -214,7 +222,10 @@ class EEGNetPlan:
                                                          int(kernel_length), int(T)))
         self.n_params = int(_lib.lib().isd_eegnet_param_count(self._h))
         self.F = int(feature_dim)
+        self.dtype = dtype
         self._seed_dev = None
+        if dtype != torch.float32:
+            _lib.check(_lib.lib().isd_eegnet_plan_set_input_dtype(self._h, _HEAD_X_DTYPES[dtype]))
 
     def set_seed_counter(self, counter):
         """``counter``: int64 device tensor (or None) mixed into every pass's dropout seed (graph replay)."""
@@ -291,6 +302,32 @@ def eegnet_backward(plan, x, flat, dout, dflat, ws, dropout_p, seed, world=1):
             _all_reduce_block(dist, ws, off.value, n.value, bool(L.isd_eegnet_sync_block_kind(1, stage)))
 
 
+def _bf16_head_refusals(x_grad, eval_param_grads):
+    """A bfloat16 input has no input gradient, so the BatchNorm heads take it for an eval forward without gradients
+    and for a train-mode forward with parameter gradients only (eval-mode parameter gradients run the input-gradient
+    pass, isd_eegnet_backward_x)."""
+    if x_grad:
+        raise TypeError("a bfloat16 x cannot require grad: the EEGNet / CVBlock head has no input gradient for bf16 "
+                        "inputs (pass x.float() to differentiate w.r.t. the input)")
+    if eval_param_grads:
+        raise TypeError("eval-mode parameter gradients need the input-gradient pass, which bfloat16 inputs do not "
+                        "have: call the module in train mode, under torch.no_grad(), or with x.float()")
+
+
+def _head_x(x, plan, x_grad, mode):
+    """The input of an EEGNet_Encoder / CVBlock pass: float32, or a bfloat16 map (widened exactly to fp32 on load)."""
+    if x.dtype == torch.float32:
+        return _f32c(x, "x")
+    if x.dtype != torch.bfloat16:
+        raise TypeError(f"x must be a float32 or bfloat16 CUDA tensor, got {x.dtype}")
+    if not x.is_cuda:
+        raise TypeError("x must be a CUDA tensor (the product has no CPU path)")
+    _bf16_head_refusals(x_grad, mode == 2)
+    if plan.dtype != torch.bfloat16:
+        raise TypeError("a bfloat16 x needs a plan built for bfloat16 input")
+    return x if x.is_contiguous() else x.contiguous()
+
+
 class _EEGNetFn(torch.autograd.Function):
     """EEGNet_Encoder / CVBlock.  Differentiable w.r.t. the parameters and -- single device -- the input trials, in
     train mode (batch statistics: BatchNorm's mean / variance paths are part of the input gradient) and in eval mode
@@ -298,13 +335,13 @@ class _EEGNetFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, flat, bufs, plan, training, momentum, eps, dropout_p, seed, sync):
-        x, flat = _f32c(x, "x"), _f32c(flat, "params")
+        want_bwd = any(ctx.needs_input_grad[:2])
+        mode = 1 if training else (2 if want_bwd else 0)     # 2: eval-mode statistics, activations kept for backward
+        x, flat = _head_x(x, plan, ctx.needs_input_grad[0], mode), _f32c(flat, "params")
         B = x.shape[0]
         out = torch.empty((B, plan.F), dtype=torch.float32, device=x.device)
         ws = torch.empty(max(int(_lib.lib().isd_eegnet_workspace_bytes(plan._h, B)) // 4, 1), dtype=torch.float32,
                          device=x.device)
-        want_bwd = any(ctx.needs_input_grad[:2])
-        mode = 1 if training else (2 if want_bwd else 0)     # 2: eval-mode statistics, activations kept for backward
         with torch.cuda.device(x.device):
             world = eegnet_forward(plan, x, flat, bufs, out, ws, mode, momentum, eps, dropout_p, seed, sync)
         ctx.plan, ctx.ws, ctx.dp, ctx.seed, ctx.mode, ctx.world = plan, ws, float(dropout_p), int(seed), mode, world
@@ -870,10 +907,13 @@ class _BNStackMixin(_FlatParamMixin):
                     off += n
         return flat
 
-    def _plan_for(self, T):
-        plan = self._plans.get(T)
+    def _plan_for(self, T, dtype=torch.float32):
+        """The plan for T-sample inputs of element type ``dtype`` (float32, or bfloat16: a bf16 map read directly)."""
+        if dtype not in _HEAD_X_DTYPES:
+            raise TypeError(f"x must be a float32 or bfloat16 CUDA tensor, got {dtype}")
+        plan = self._plans.get((T, dtype))
         if plan is None:
-            plan = self._plans[T] = self._make_plan(T)
+            plan = self._plans[(T, dtype)] = self._make_plan(T, dtype)
             if getattr(self, "_seed_dev", None) is not None:
                 plan.set_seed_counter(self._seed_dev)
         return plan
@@ -884,10 +924,10 @@ class _BNStackMixin(_FlatParamMixin):
         for plan in self._plans.values():
             plan.set_seed_counter(counter)
 
-    def _zone_call(self, T):
+    def _zone_call(self, T, dtype=torch.float32):
         """One forward's bookkeeping (call counter, ``num_batches_tracked``) and the arguments of ``_EEGNetFn`` after
-        ``x`` -- also what ``Head`` hands to the zone-batched ``_BNZonesFn``."""
-        plan = self._plan_for(T)
+        ``x`` -- also what ``Head`` hands to the zone-batched ``_BNZonesFn`` (always float32 there)."""
+        plan = self._plan_for(T, dtype)
         theta = self.packed_theta()
         bn = self._bns()[0]
         self._calls += 1
@@ -899,7 +939,9 @@ class _BNStackMixin(_FlatParamMixin):
                 getattr(self, "sync_bn", True))
 
     def _run(self, x):
-        return _EEGNetFn.apply(x, *self._zone_call(x.shape[-1])[1:])
+        if x.dtype == torch.bfloat16 and torch.is_grad_enabled():        # refused before any bookkeeping
+            _bf16_head_refusals(x.requires_grad, not self.training and any(p.requires_grad for p in self.parameters()))
+        return _EEGNetFn.apply(x, *self._zone_call(x.shape[-1], x.dtype)[1:])
 
 
 class EEGNet_Encoder(nn.Module, _BNStackMixin):
@@ -933,8 +975,8 @@ class EEGNet_Encoder(nn.Module, _BNStackMixin):
                 self.separable_conv[0].weight, self.separable_conv[1].weight, b3.weight, b3.bias,
                 self.projector[2].weight, self.projector[2].bias]
 
-    def _make_plan(self, T):
-        return EEGNetPlan(self.in_channels, self.feature_dim, self.kernel_length, T)
+    def _make_plan(self, T, dtype=torch.float32):
+        return EEGNetPlan(self.in_channels, self.feature_dim, self.kernel_length, T, dtype=dtype)
 
     def forward(self, x):
         if x.dim() != 3:
@@ -970,8 +1012,8 @@ class CVBlock(nn.Module, _BNStackMixin):
         return [self.conv1.weight, self.bn1.weight, self.bn1.bias, self.conv2.weight, self.bn2.weight, self.bn2.bias,
                 self.conv3.weight, self.bn3.weight, self.bn3.bias, self.projector.weight, self.projector.bias]
 
-    def _make_plan(self, T):
-        plan = EEGNetPlan(self.in_channels, self.feature_dim, 64, T, cvblock=True)
+    def _make_plan(self, T, dtype=torch.float32):
+        plan = EEGNetPlan(self.in_channels, self.feature_dim, 64, T, cvblock=True, dtype=dtype)
         if plan.flat_dim != self.flat_dim:
             raise RuntimeError(f"CVBlock: a {T}-sample window flattens to {plan.flat_dim} features but the projector "
                                f"expects {self.flat_dim} (fixed by the 250-sample window, fast.py:66-74)")

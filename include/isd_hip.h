@@ -119,9 +119,11 @@ int isd_stft_bandpower(const isd_stft_plan* plan, const float* y, float* feat,
 int isd_features_fused(const isd_fb_plan* fb, const isd_stft_plan* st, const float* x,
                        float* feat, int64_t B, int64_t C, const int* klo, const int* khi,
                        int mode, float eps, void* stream);
-/* The same with the feature map written as bf16 (round to nearest even) -- BASELINE config 3: it is the rounding the
- * bf16 classifier (isd_featcnn_step_bf16) and the reference's autocast apply to the convolution's input anyway.
- * Rows of at most 1024 samples (the nperseg 64 / noverlap 32 extractor); ISD_ERR_UNSUPPORTED otherwise. */
+/* The same with the feature map written as bf16: each value is the fp32 map's value rounded to nearest even.
+ * BASELINE config 3: it is the rounding the bf16 classifier (isd_featcnn_step_bf16) and the reference's autocast apply
+ * to the convolution's input anyway.  Both extractor families write it: the short-row one (nperseg 64 / noverlap 32,
+ * rows of at most 1024 samples) and the long-row block-sum one (hop 64; the stress configuration, whose bf16 map the
+ * EEGNet head reads through isd_eegnet_plan_set_input_dtype). */
 int isd_features_fused_bf16(const isd_fb_plan* fb, const isd_stft_plan* st, const float* x, uint16_t* feat,
                             int64_t B, int64_t C, const int* klo, const int* khi, int mode, float eps, void* stream);
 
@@ -257,6 +259,13 @@ int64_t isd_cvblock_flat_dim(const isd_eegnet_plan* plan);
  * seed, so a captured HIP graph -- which replays the same seed argument -- draws new masks by incrementing the counter
  * inside the graph.  Null (the default) = the seed argument alone. */
 int isd_eegnet_plan_set_seed_counter(isd_eegnet_plan* plan, const uint64_t* seed_dev);
+/* Element type of the input x of every isd_eegnet_* call on this plan (forward, backward, the _stage forms, zone-batched
+ * calls): ISD_ACT_F32 (the default) or ISD_ACT_BF16, x then being [B][C][T] bf16 passed through the same const float*
+ * argument (e.g. the map of isd_features_fused_bf16).  bf16 values are widened to fp32 on load, which is exact, and the
+ * head then computes exactly what it computes in fp32 on those values: same kernels, same order, the same bits as an
+ * fp32 call on the widened input.  It is not autocast: the head's arithmetic stays fp32 throughout.  No input
+ * gradient: isd_eegnet_backward_x returns ISD_ERR_UNSUPPORTED on a bf16 plan. */
+int isd_eegnet_plan_set_input_dtype(isd_eegnet_plan* plan, int dtype);
 int isd_eegnet_plan_destroy(isd_eegnet_plan* plan);
 int64_t isd_eegnet_param_count(const isd_eegnet_plan* plan);
 int64_t isd_eegnet_buffer_count(const isd_eegnet_plan* plan);
