@@ -21,6 +21,7 @@
 #include <vector>
 #include <string.h>
 #include <type_traits>
+#include <atomic>
 
 namespace isd {
 
@@ -1136,6 +1137,18 @@ __device__ __forceinline__ f2 sym_pair(const f2& p, const f2& q) {
 __device__ __forceinline__ void pmac(f2& acc, const f2& ad, const f2& t) {
   asm("v_pk_fma_f32 %0, %1, %2, %0" : "+v"(acc) : "v"(ad), "s"(t));
 }
+// ad * t + 0: the first term of a sum (the same fma as pmac on a zeroed accumulator, without the v_mov_b64 of the zeros)
+__device__ __forceinline__ f2 pmac0(const f2& ad, const f2& t) {
+  f2 acc;
+  asm("v_pk_fma_f32 %0, %1, %2, 0" : "=v"(acc) : "v"(ad), "s"(t));
+  return acc;
+}
+// u.x += hi(p), in place (written as a vector add, the compiler issued a v_pk_add and a v_mov for the untouched half)
+__device__ __forceinline__ void add_lo(f2& u, const f2& p) {
+  float x = u.x;
+  asm("v_add_f32 %0, %0, %1" : "+v"(x) : "v"(p.y));
+  u.x = x;
+}
 // acc += lo(pr) * conj(t)
 __device__ __forceinline__ void cmac_lo_conj(f2& acc, const f2& pr, const f2& t) {
   asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[0,1,1] neg_hi:[0,1,0]" : "+v"(acc) : "v"(pr), "s"(t));
@@ -1431,6 +1444,21 @@ __device__ __forceinline__ void ser_dma16(const void* src_lane, unsigned lds_bas
 // (Issuing the loads a stage AHEAD by hand does not work with this compiler: an inline-asm output of an SGPR vector
 // type reads back as its first element in every lane of the vector -- hipcc 7.2, "=s" / "+s" on ext_vector_type(2..16)
 // -- and left to itself the scheduler sinks scalar loads to their first use.)
+// d = fma(a, b, c) into a register of the compiler's choice (the accumulating v_fmac ties d to c's register)
+__device__ __forceinline__ float fma_to(float a, float b, float c) {
+  float d;
+  asm("v_fma_f32 %0, %1, %2, %3" : "=v"(d) : "s"(a), "v"(b), "v"(c));
+  return d;
+}
+// d = fma(a, b, c) over d, whose old value is dead (d = c2 of the carried state)
+__device__ __forceinline__ void fma_over(double& d, double a, double b, double c) {
+  asm("v_fma_f64 %0, %1, %2, %3" : "+v"(d) : "s"(a), "v"(b), "v"(c));
+}
+// d = fma(a, d, c) in place (d = c1 of the carried state)
+__device__ __forceinline__ void fma_over_mid(double& d, double a, double c) {
+  asm("v_fma_f64 %0, %1, %0, %2" : "+v"(d) : "s"(a), "v"(c));
+}
+
 __device__ __forceinline__ void section_serial_f32(f2 (&v)[kL / 2], const SerSec& sc0, double& c1, double& c2) {
   const SerSec& sc = *later(&sc0);
   const float na1 = -sc.a1, na2 = -sc.a2;
@@ -1459,12 +1487,15 @@ __device__ __forceinline__ void section_serial_f32(f2 (&v)[kL / 2], const SerSec
   const double e1 = (double)fmaf(n16[0], S1.x, fmaf(n16[1], S2.x, S1.y));
   const double e2 = (double)fmaf(n16[2], S1.x, fmaf(n16[3], S2.x, S2.y));
   const float t1 = (float)c1, t2 = (float)c2;                      // state entering the chunk
-  const double n1 = fma(m0, c1, fma(m1, c2, e1));                  // state leaving it: M c + e
-  const double n2 = fma(m2, c1, fma(m3, c2, e2));
-  c1 = n1;
-  c2 = n2;
-  const float u1 = fmaf(n16[0], t1, fmaf(n16[1], t2, sA1));
-  const float u2 = fmaf(n16[2], t1, fmaf(n16[3], t2, sA2));
+  // State leaving the chunk, M c + e, written over the carried registers: n2 first (c1 is still needed for it), then n1.
+  // Computed into fresh registers the new states were copied back at the end of every band (8 v_mov_b64).
+  const double i1 = fma(m1, c2, e1), i2 = fma(m3, c2, e2);
+  fma_over(c2, m2, c1, i2);
+  fma_over_mid(c1, m0, i1);
+  // u written by non-accumulating FMAs, so that it lands in the high half of its fix-up pair (v_fmac accumulated it in
+  // the register of S.x and a v_mov per value carried it over)
+  const float u1 = fma_to(n16[0], t1, fmaf(n16[1], t2, sA1));
+  const float u2 = fma_to(n16[2], t1, fmaf(n16[3], t2, sA2));
   const f2 T1 = {t1, u1}, T2 = {t2, u2};
 #pragma unroll
   for (int j = 0; j < kL / 2; ++j)
@@ -1586,17 +1617,18 @@ void fused_serial_kernel(const SerSec* __restrict__ secs, const FbBand* __restri
             f2 tc[17];
 #pragma unroll
             for (int m = 1; m <= 16; ++m) tc[m] = tq[m - 1];
-            f2 acc_a = {0.f, 0.f}, acc_b = {0.f, 0.f};
+            f2 acc_a = pmac0(ad[0], tc[1]), acc_b = pmac0(ad[1], tc[2]);
 #pragma unroll
-            for (int m = 1; m <= 13; m += 2) {
+            for (int m = 3; m <= 13; m += 2) {
               pmac(acc_a, ad[m - 1], tc[m]);
               pmac(acc_b, ad[m], tc[m + 1]);
             }
             pmac(acc_a, ad[14], tc[15]);
             cmac_lo_conj(acc_b, v[0], tc[16]);                        // y[0] e^{+i 16 th}
             f2 U = acc_a + acc_b;
-            U.x += v[0].y;                                            // y[16]
-            const float sg = (k & 1) ? -1.f : 1.f;                    // frame j = U_{j-1} + (-1)^k U_j
+            add_lo(U, v[0]);                                          // y[16]
+            // frame j = U_{j-1} + (-1)^k U_j; the sign as a wave-uniform bit pattern (a float select was a v_cndmask)
+            const float sg = __builtin_bit_cast(float, 0x3f800000u | ((unsigned)k << 31));
             Xs[kk] = __builtin_elementwise_fma(U, (f2){sg, sg}, prevU[i][kk]);
             prevU[i][kk] = U;
           }
@@ -1942,6 +1974,22 @@ static bool serial_wanted() {
   return !(e && e[0] == '0');
 }
 
+// Tiles above 48 KiB (four row groups: 64 KiB) need the kernels' dynamic-LDS limit raised: once per process and device,
+// to the largest tile the launcher builds, instead of twice in front of every launch.
+static void serial_lds_limit() {
+  static std::atomic<unsigned long long> done{0};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+  const unsigned long long bit = 1ull << dev;
+  if (done.load(std::memory_order_relaxed) & bit) return;
+  const int lds = (int)(sizeof(float) * kSerMaxGroups * 2 * kSerRows * kL);
+  const void* k[] = {(const void*)fused_serial_kernel<1, false>, (const void*)fused_serial_kernel<1, true>,
+                     (const void*)fused_serial_kernel<2, false>, (const void*)fused_serial_kernel<2, true>,
+                     (const void*)fused_serial_kernel<3, false>, (const void*)fused_serial_kernel<3, true>};
+  for (const void* f : k) (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  done.fetch_or(bit, std::memory_order_relaxed);
+}
+
 static bool fused_serial_launch(const isd_fb_plan* fb, const FbSet& fs, const isd_stft_plan* st, const float* x,
                                 float* feat, int64_t R, int C, const FusedBands& fbnd, int mode, float eps,
                                 hipStream_t stream, int out16) {
@@ -1965,14 +2013,9 @@ static bool fused_serial_launch(const isd_fb_plan* fb, const FbSet& fs, const is
   const dim3 grid((unsigned)cdiv(R, (int64_t)kSerRows * groups));
   const size_t lds = sizeof(float) * (size_t)groups * 2 * kSerRows * kL;
   const bool mag = mode == ISD_BP_MAGNITUDE;
+  if (lds > 48 * 1024) serial_lds_limit();
 #define ISD_SER(BPW_)                                                                                                   \
   do {                                                                                                                  \
-    if (lds > 48 * 1024) {                                                                                              \
-      (void)hipFuncSetAttribute((const void*)fused_serial_kernel<BPW_, true>,                                           \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                  \
-      (void)hipFuncSetAttribute((const void*)fused_serial_kernel<BPW_, false>,                                          \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                  \
-    }                                                                                                                   \
     if (mag)                                                                                                            \
       hipLaunchKernelGGL((fused_serial_kernel<BPW_, true>), grid, dim3(64 * nw * groups), lds, stream, fs.d_ser,        \
                          fs.d_band, st->d_sym, x, feat, (int)R, C, st->T, fs.nb, st->J, st->scale * st->scale, fbnd,    \
