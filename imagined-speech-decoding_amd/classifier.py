@@ -700,6 +700,46 @@ class FilterbankCNNClassifier(_Estimator):
             feats[i:i + 4096] = self._inputs(X[i:i + 4096].contiguous())
         return feats, (lambda fb: fb)
 
+    def input_gradient(self, X, target=None, batch_size=256):
+        """d logit[target_i](X_i) / d X_i as float32 NumPy [n, C, T]: the gradient attribution of the reference's
+        explain_fast.py / global_shap_analysis.py (GradientExplainer) through extractor and network.  ``target``: None
+        (the predicted class), an int, or an int array [n].  The fitted network runs in eval mode through its autograd
+        modules; no parameter gradient, running statistic or training flag changes."""
+        if self.precision == "bf16":
+            raise TypeError("input_gradient: a precision='bf16' estimator has no input gradient (bf16 feature maps and "
+                            "activations are not differentiated); use precision='fp32'")
+        model = self._fitted_model()
+        dev = self._device()
+        n = len(X)
+        n_cls = self._n_classes()
+        tgt = None
+        if target is not None:
+            tgt = np.broadcast_to(np.asarray(target.cpu() if isinstance(target, torch.Tensor) else target), (n,))
+            if tgt.dtype.kind not in "iu":
+                raise TypeError(f"target must hold integer class indices, got dtype {tgt.dtype}")
+            if n and (int(tgt.min()) < 0 or int(tgt.max()) >= n_cls):
+                raise ValueError(f"target must lie in [0, {n_cls})")
+        net = model.net
+        flags = [(m, m.training) for m in net.modules()]
+        net.eval()
+        outs = []
+        try:
+            for i in range(0, n, batch_size):
+                xb = _to_device(X[i:i + batch_size], dev).detach().requires_grad_(True)
+                with torch.enable_grad():
+                    f = self._extractor(xb.shape[-1])(xb, fused=self.fused)
+                    logits = net(f.view(f.shape[0], -1, f.shape[-1]))
+                    t = logits.detach().argmax(1) if tgt is None else \
+                        torch.as_tensor(np.ascontiguousarray(tgt[i:i + xb.shape[0]]), dtype=torch.long, device=dev)
+                    gx, = torch.autograd.grad(logits.gather(1, t[:, None]).sum(), xb)
+                outs.append(gx.cpu().numpy())
+        finally:
+            for m, was in flags:
+                m.training = was
+        if not outs:
+            return np.zeros((0,) + tuple(X.shape[1:]), np.float32)
+        return np.concatenate(outs)
+
 
 class FilterbankEEGNetClassifier(FilterbankCNNClassifier):
     """extract_features -> ``EEGNet_Encoder(nb*C, feature_dim)`` (fast.py:122-167, through the head contract

@@ -2193,3 +2193,310 @@ int isd::bandpower_direct(const isd_stft_plan* st, const float* y, float* feat, 
   ISD_LAUNCH_CHECK();
   return ISD_OK;
 }
+
+// ------------------------------------------------------------------------------------------------------------------
+// Input gradient of the extractor (isd_features_backward).  Per (trial, channel) row and band b, with
+// s = 1 / sum(w) and frame starts s_j = j hop - N/2 (y_b is zero outside [0, T)):
+//   forward   y_b = H_b x ;  Z_jk = s sum_n w[n] y_b[s_j + n] e^{-2 pi i k n / N}  (k = klo..khi, nk bins) ;
+//             P_j = (1/nk) sum_k |Z_jk|^2 ;  feature log(P_j + eps) | P_j | (1/nk) sum_k |Z_jk|
+//   backward  dy_b[t] = sum_j sum_k w[t - s_j] Re(C_jk e^{+2 pi i k (t - s_j) / N}),  C_jk = c_jk Z_jk,
+//             c_jk = 2 s g_j / (nk (P_j + eps)) | 2 s g_j / nk | s g_j / (nk |Z_jk|) (0 where |Z_jk| = 0) ;
+//             dx = sum_b H_b^T dy_b,  H_b^T = R H_b R: the same causal cascade over the time-reversed gradient.
+// The cascade is the forward's own section arithmetic: fp32 bands run section_serial_f32 (zero-state fp32 chunk
+// recursion, fp64 carried states), fp64 bands a serial fp64 recursion.
+// One row per lane, every lane of a wave in the same band / frame / sample loop: the tables (window, twiddles, section
+// constants) are wave-uniform and only the row data differ.  The row data live in the caller's workspace laid out
+// [sample][row] (row fastest), so that every access of a wave is coalesced:
+//   xT [T][RS] the trials | yT [T][RS] y_b, then dy_b | dT [T][RS] the running band sum of dx | co [J][nkmax][RS] float2
+//   Z_jk, then C_jk
+// for RS rows at a time (larger batches run in chunks).  Each lane owns its row and adds the bands into it in a fixed
+// order (the fp32 set, then the fp64 set, each in plan order): no atomics, the same bits on every call and for a trial
+// at any batch size.
+namespace isd {
+
+constexpr int kGradKB = 8;                              // bins per register block of the frame DFT / synthesis
+constexpr int64_t kGradWorkspaceCap = 2LL << 30;        // bytes of workspace; more rows run in chunks
+
+struct GradBands {                                      // the bands of one precision set, in set order
+  int out[kMaxBands];                                   // position in the caller's band order (feature map)
+  int klo[kMaxBands];
+  int khi[kMaxBands];
+};
+
+// e^{-2 pi i m / N} from the plan's half table tw[u] = e^{-2 pi i u / N}, u < N/2
+__device__ __forceinline__ float2 grad_twiddle(const float2* __restrict__ tw, int m, int N) {
+  const int u = m & (N - 1);
+  const float2 e = tw[u & (N / 2 - 1)];
+  return (u & (N / 2)) ? make_float2(-e.x, -e.y) : e;
+}
+
+// Serial fp64 DF2T section over a chunk (the fp64 bands, both directions); (s1, s2) the carried state
+__device__ __forceinline__ void section_grad_f64(double (&v)[kL], const FbSec& sc, double& s1, double& s2) {
+  const double na1 = -sc.a1d, na2 = -sc.a2d;
+#pragma unroll
+  for (int j = 0; j < kL; ++j) {
+    const double xj = v[j], y = xj + s1;
+    s1 = fma(na1, y, s2);
+    s2 = fma(na2, y, -xj);
+    v[j] = y;
+  }
+}
+
+// gain + the band's cascade over one 32-sample chunk of the lane's row, in place; st: the lane's carried section
+// states in LDS, [section][2][64 lanes]
+template <typename VT>
+__device__ __forceinline__ void grad_cascade(float (&io)[kL], const FbSec* __restrict__ sec,
+                                             const SerSec* __restrict__ ser, const FbBand& band, int ns, double* st,
+                                             int lane) {
+  if constexpr (std::is_same<VT, float>::value) {
+    f2 v[kL / 2];                                       // sample pairs {j, j + 16}, as fused_serial_kernel holds them
+    const float g = band.gf;
+#pragma unroll
+    for (int j = 0; j < kL / 2; ++j) v[j] = (f2){io[j] * g, io[j + 16] * g};
+    for (int s = 0; s < ns; ++s) {
+      double c1 = st[(2 * s) * 64 + lane], c2 = st[(2 * s + 1) * 64 + lane];
+      section_serial_f32(v, ser[s], c1, c2);
+      st[(2 * s) * 64 + lane] = c1;
+      st[(2 * s + 1) * 64 + lane] = c2;
+    }
+#pragma unroll
+    for (int j = 0; j < kL / 2; ++j) {
+      io[j] = v[j].x;
+      io[j + 16] = v[j].y;
+    }
+  } else {
+    double v[kL];
+    const double g = band.gd;
+#pragma unroll
+    for (int j = 0; j < kL; ++j) v[j] = (double)io[j] * g;
+    for (int s = 0; s < ns; ++s) {
+      double c1 = st[(2 * s) * 64 + lane], c2 = st[(2 * s + 1) * 64 + lane];
+      section_grad_f64(v, sec[s], c1, c2);
+      st[(2 * s) * 64 + lane] = c1;
+      st[(2 * s + 1) * 64 + lane] = c2;
+    }
+#pragma unroll
+    for (int j = 0; j < kL; ++j) io[j] = (float)v[j];
+  }
+}
+
+// One precision set of bands over n_rows rows starting at row0.  first: copy the trials in and clear the dx sum;
+// last: write dx out.
+template <typename VT>
+__global__ __launch_bounds__(64) void features_grad_kernel(
+    const FbSec* __restrict__ secs, const SerSec* __restrict__ sers, const FbBand* __restrict__ bands, GradBands gb,
+    int nb, int ns, const float* __restrict__ win, const float2* __restrict__ tw, const float* __restrict__ x,
+    const float* __restrict__ dfeat, float* __restrict__ dx, float* __restrict__ ws, int64_t row0, int n_rows,
+    int64_t RS, int C, int T, int N, int hop, int J, int nb_out, int nkmax, float scale, int mode, float eps,
+    int first, int last) {
+  __shared__ double st[kMaxSec * 2 * 64];
+  const int lane = threadIdx.x;
+  const int r = blockIdx.x * 64 + lane;
+  if (r >= n_rows) return;                              // lanes never exchange data
+  const int64_t row = row0 + r, bt = row / C, ch = row - bt * C;
+  float* const xT = ws + r;
+  float* const yT = ws + (int64_t)T * RS + r;
+  float* const dT = ws + 2 * (int64_t)T * RS + r;
+  float2* const co = reinterpret_cast<float2*>(ws + 3 * (int64_t)T * RS) + r;
+  const int half = N / 2;
+  if (first) {
+    const float* xr = x + row * (int64_t)T;
+    for (int t = 0; t < T; ++t) {
+      xT[t * RS] = xr[t];
+      dT[t * RS] = 0.f;
+    }
+  }
+  for (int i = 0; i < nb; ++i) {
+    const int klo = gb.klo[i], khi = gb.khi[i];
+    if (khi < klo) continue;                            // an empty band contributes nothing
+    const int nk = khi - klo + 1;
+    const FbSec* bsec = secs + i * ns;
+    const SerSec* bser = std::is_same<VT, float>::value ? sers + i * ns : nullptr;
+    const FbBand band = bands[i];
+    // 1. causal pass: y_b
+    for (int e = 0; e < 2 * ns; ++e) st[e * 64 + lane] = 0.0;
+    for (int t0 = 0; t0 < T; t0 += kL) {
+      float io[kL];
+#pragma unroll
+      for (int j = 0; j < kL; ++j) io[j] = t0 + j < T ? xT[(t0 + j) * RS] : 0.f;
+      grad_cascade<VT>(io, bsec, bser, band, ns, st, lane);
+#pragma unroll
+      for (int j = 0; j < kL; ++j)
+        if (t0 + j < T) yT[(t0 + j) * RS] = io[j];
+    }
+    // 2. Z_jk of every frame, kGradKB bins at a time
+    for (int k0 = klo; k0 <= khi; k0 += kGradKB) {
+      const int nkb = min(kGradKB, khi - k0 + 1);
+      for (int j = 0; j < J; ++j) {
+        const int s0 = j * hop - half, n0 = max(0, -s0), n1 = min(N, T - s0);
+        float2 acc[kGradKB];
+#pragma unroll
+        for (int q = 0; q < kGradKB; ++q) acc[q] = make_float2(0.f, 0.f);
+        for (int n = n0; n < n1; ++n) {
+          const float yw = yT[(s0 + n) * RS] * win[n];
+#pragma unroll
+          for (int q = 0; q < kGradKB; ++q)
+            if (q < nkb) {
+              const float2 e = grad_twiddle(tw, (k0 + q) * n, N);
+              acc[q].x = fmaf(yw, e.x, acc[q].x);
+              acc[q].y = fmaf(yw, e.y, acc[q].y);
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < kGradKB; ++q)
+          if (q < nkb) co[((int64_t)j * nkmax + (k0 - klo + q)) * RS] = make_float2(acc[q].x * scale, acc[q].y * scale);
+      }
+    }
+    // 3. C_jk = c_jk Z_jk in place
+    const float* gr = dfeat + ((bt * nb_out + gb.out[i]) * C + ch) * (int64_t)J;
+    const float inv = 1.f / (float)nk;
+    for (int j = 0; j < J; ++j) {
+      float2* cj = co + (int64_t)j * nkmax * RS;
+      const float g = gr[j];
+      float P = 0.f;
+      if (mode != ISD_BP_MAGNITUDE) {
+        for (int k = 0; k < nk; ++k) {
+          const float2 z = cj[k * RS];
+          P = fmaf(z.x, z.x, fmaf(z.y, z.y, P));
+        }
+        P *= inv;
+      }
+      const float cp = mode == ISD_BP_LOGPOWER ? 2.f * scale * g * inv / (P + eps) : 2.f * scale * g * inv;
+      for (int k = 0; k < nk; ++k) {
+        const float2 z = cj[k * RS];
+        float c = cp;
+        if (mode == ISD_BP_MAGNITUDE) {
+          const float a = sqrtf(fmaf(z.x, z.x, z.y * z.y));
+          c = a > 0.f ? scale * g * inv / a : 0.f;
+        }
+        cj[k * RS] = make_float2(c * z.x, c * z.y);
+      }
+    }
+    // 4. dy_b over y_b: frame by frame, Re(C e^{+i th}) = C.x cos th - C.y sin th with the table's (cos, -sin)
+    for (int t = 0; t < T; ++t) yT[t * RS] = 0.f;
+    for (int k0 = klo; k0 <= khi; k0 += kGradKB) {
+      const int nkb = min(kGradKB, khi - k0 + 1);
+      for (int j = 0; j < J; ++j) {
+        float2 cc[kGradKB];
+#pragma unroll
+        for (int q = 0; q < kGradKB; ++q)
+          cc[q] = q < nkb ? co[((int64_t)j * nkmax + (k0 - klo + q)) * RS] : make_float2(0.f, 0.f);
+        const int s0 = j * hop - half, n0 = max(0, -s0), n1 = min(N, T - s0);
+        for (int n = n0; n < n1; ++n) {
+          float d = 0.f;
+#pragma unroll
+          for (int q = 0; q < kGradKB; ++q)
+            if (q < nkb) {
+              const float2 e = grad_twiddle(tw, (k0 + q) * n, N);
+              d = fmaf(cc[q].x, e.x, fmaf(cc[q].y, e.y, d));
+            }
+          float* p = yT + (s0 + n) * RS;
+          *p = fmaf(win[n], d, *p);
+        }
+      }
+    }
+    // 5. anti-causal pass R H_b R dy_b, added into dx (reversed sample q <-> t = T - 1 - q)
+    for (int e = 0; e < 2 * ns; ++e) st[e * 64 + lane] = 0.0;
+    for (int q0 = 0; q0 < T; q0 += kL) {
+      float io[kL];
+#pragma unroll
+      for (int j = 0; j < kL; ++j) io[j] = q0 + j < T ? yT[(T - 1 - q0 - j) * RS] : 0.f;
+      grad_cascade<VT>(io, bsec, bser, band, ns, st, lane);
+#pragma unroll
+      for (int j = 0; j < kL; ++j)
+        if (q0 + j < T) {
+          float* p = dT + (T - 1 - q0 - j) * RS;
+          *p += io[j];
+        }
+    }
+  }
+  if (last) {
+    float* dr = dx + row * (int64_t)T;
+    for (int t = 0; t < T; ++t) dr[t] = dT[t * RS];
+  }
+}
+
+// Workspace bytes per row, and the rows of one chunk (a multiple of 64, at most kGradWorkspaceCap bytes)
+static int64_t grad_row_bytes(const isd_stft_plan* st, int nkmax) {
+  return ((int64_t)3 * st->T + (int64_t)2 * st->J * nkmax) * (int64_t)sizeof(float);
+}
+static int64_t grad_chunk_rows(int64_t rows, int64_t row_bytes) {
+  int64_t rc = (kGradWorkspaceCap / row_bytes) / 64 * 64;
+  if (rc < 64) rc = 64;
+  const int64_t all = cdiv(rows, 64) * 64;
+  return rc < all ? rc : all;
+}
+// The band-bin tables checked, and the widest band (at least 1)
+static int grad_bins(const isd_fb_plan* fb, const isd_stft_plan* st, const int* klo, const int* khi, int* lo, int* hi,
+                     int& nkmax, const char* who) {
+  const int rc = fill_band_args(st, fb->n_bands, klo, khi, lo, hi, who);
+  if (rc) return rc;
+  nkmax = 1;
+  for (int b = 0; b < fb->n_bands; ++b)
+    if (hi[b] - lo[b] + 1 > nkmax) nkmax = hi[b] - lo[b] + 1;
+  return ISD_OK;
+}
+
+}  // namespace isd
+
+extern "C" int64_t isd_features_backward_workspace_bytes(const isd_fb_plan* fb, const isd_stft_plan* st, int64_t B,
+                                                         int64_t C, const int* klo, const int* khi) {
+  ISD_CHECK_ARG(fb && st, "isd_features_backward_workspace_bytes: null plan");
+  ISD_CHECK_ARG(B >= 0 && C >= 1 && C <= (1 << 20), "isd_features_backward_workspace_bytes: bad shape B=%lld C=%lld",
+                (long long)B, (long long)C);
+  int lo[kMaxBands], hi[kMaxBands], nkmax = 1;
+  const int rc = grad_bins(fb, st, klo, khi, lo, hi, nkmax, "isd_features_backward_workspace_bytes");
+  if (rc) return rc;
+  if (B == 0) return 0;
+  const int64_t rb = grad_row_bytes(st, nkmax);
+  return grad_chunk_rows(B * C, rb) * rb;
+}
+
+extern "C" int isd_features_backward(const isd_fb_plan* fb, const isd_stft_plan* st, const float* x, const float* dfeat,
+                                     float* dx, void* workspace, int64_t B, int64_t C, const int* klo, const int* khi,
+                                     int mode, float eps, void* stream) {
+  ISD_CHECK_ARG(mode >= ISD_BP_MAGNITUDE && mode <= ISD_BP_LOGPOWER, "isd_features_backward: bad mode %d", mode);
+  ISD_CHECK_ARG(B >= 0 && C >= 1 && C <= (1 << 20), "isd_features_backward: bad shape B=%lld C=%lld", (long long)B,
+                (long long)C);
+  ISD_CHECK_ARG(fb && st, "isd_features_backward: null plan");
+  ISD_CHECK_ARG(B == 0 || (x && dfeat && dx && workspace), "isd_features_backward: null argument");
+  int lo[kMaxBands], hi[kMaxBands], nkmax = 1;
+  const int rc = grad_bins(fb, st, klo, khi, lo, hi, nkmax, "isd_features_backward");
+  if (rc) return rc;
+  if (B == 0) return ISD_OK;
+  ISD_CHECK_ARG(B * C <= kMaxRows, "isd_features_backward: too many rows (%lld)", (long long)(B * C));
+  GradBands gb[2] = {};
+  int nsets = 0;
+  for (int k = 0; k < 2; ++k) {
+    for (int i = 0; i < fb->set[k].nb; ++i) {
+      const int b = fb->host_map[k][i];
+      gb[k].out[i] = b;
+      gb[k].klo[i] = lo[b];
+      gb[k].khi[i] = hi[b];
+    }
+    if (fb->set[k].nb) ++nsets;
+  }
+  const int64_t rows = B * C, RS = grad_chunk_rows(rows, grad_row_bytes(st, nkmax));
+  hipStream_t s = (hipStream_t)stream;
+  float* ws = static_cast<float*>(workspace);
+  for (int64_t r0 = 0; r0 < rows; r0 += RS) {
+    const int n = (int)(rows - r0 < RS ? rows - r0 : RS);
+    int done = 0;
+    for (int k = 0; k < 2; ++k) {
+      const FbSet& fs = fb->set[k];
+      if (!fs.nb) continue;
+      const int first = done == 0, last = done == nsets - 1;
+      const dim3 grid((unsigned)cdiv(n, 64));
+#define ISD_GRAD(VT) hipLaunchKernelGGL((features_grad_kernel<VT>), grid, dim3(64), 0, s, fs.d_sec, fs.d_ser, fs.d_band, \
+                                        gb[k], fs.nb, fb->n_sections, st->d_win, st->d_tw, x, dfeat, dx, ws, r0, n, RS, \
+                                        (int)C, st->T, st->n, st->hop, st->J, fb->n_bands, nkmax, st->scale, mode, eps, \
+                                        first, last)
+      if (k == 0) ISD_GRAD(float);
+      else ISD_GRAD(double);
+#undef ISD_GRAD
+      ISD_LAUNCH_CHECK();
+      ++done;
+    }
+  }
+  return ISD_OK;
+}

@@ -11,6 +11,7 @@ import functools
 
 import numpy as np
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 from .constants import BANDS_9, band_edges
@@ -169,6 +170,13 @@ class FeatureExtractor:
             out_dtype = torch.float32 if out is None else out.dtype
         if out_dtype not in (torch.float32, torch.bfloat16):
             raise TypeError(f"features are float32 or bfloat16, got {out_dtype}")
+        if x.requires_grad and torch.is_grad_enabled():
+            if out_dtype == torch.bfloat16:
+                raise TypeError("bf16 feature maps have no input gradient: extract float32 features (the default) "
+                                "from trials that require grad")
+            if out is not None:
+                raise TypeError("out= cannot carry a gradient: leave it out when the trials require grad")
+            return _FeaturesFn.apply(x, self, fused)
         if out is None:
             out = torch.empty((B, self.n_bands, Cc, self.n_frames), dtype=out_dtype, device=x.device)
         elif out.dtype != out_dtype or tuple(out.shape) != (B, self.n_bands, Cc, self.n_frames) or not out.is_contiguous():
@@ -190,6 +198,43 @@ class FeatureExtractor:
         y = self.fb.forward(x)
         return self.stft.bandpower(y, self.bins, self.mode, self.eps, out=out)
 
+    def backward(self, x, dfeat):
+        """Input gradient: x f32 CUDA [B, C, T], dfeat f32 CUDA [B, n_bands, C, J] -> dx = d<dfeat, self(x)>/dx f32
+        [B, C, T] (``isd_features_backward``; the same for every forward kernel)."""
+        _require_cuda(x, "trials")
+        _require_cuda(dfeat, "dfeat")
+        B, Cc, T = x.shape
+        if tuple(dfeat.shape) != (B, self.n_bands, Cc, self.n_frames):
+            raise ValueError(f"dfeat must be [{B}, {self.n_bands}, {Cc}, {self.n_frames}], got {tuple(dfeat.shape)}")
+        dx = torch.empty_like(x)
+        L = _lib.lib()
+        nbytes = int(L.isd_features_backward_workspace_bytes(self.fb._h, self.stft._h, B, Cc, self._klo, self._khi))
+        if nbytes < 0:
+            _lib.check(nbytes)
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=x.device)
+        with torch.cuda.device(x.device):
+            _lib.check(L.isd_features_backward(self.fb._h, self.stft._h, x.data_ptr(), dfeat.data_ptr(), dx.data_ptr(),
+                                               ws.data_ptr(), B, Cc, self._klo, self._khi, _MODE[self.mode], self.eps,
+                                               _stream_ptr()))
+        return dx
+
+
+class _FeaturesFn(torch.autograd.Function):
+    """Spec-S extraction of trials that require grad: the forward is the no-grad call itself (same kernel, same bits),
+    the backward ``isd_features_backward``."""
+
+    @staticmethod
+    def forward(ctx, x, fx, fused):
+        ctx.fx = fx
+        ctx.save_for_backward(x)
+        return fx(x, fused=fused)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dfeat):
+        x, = ctx.saved_tensors
+        return ctx.fx.backward(x, dfeat.contiguous().float()), None, None
+
 
 @functools.lru_cache(maxsize=32)
 def _cached_extractor(T, fs, bands, order, nperseg, noverlap, eps, precision, device_index):
@@ -204,6 +249,8 @@ def extract_features(trials, *, fs=256.0, bands=BANDS_9, order=4, nperseg=64, no
     ``trials`` may be a CUDA tensor (used in place, result stays on the device)
     or a NumPy array / CPU tensor (copied to ``device`` and the result copied
     back as NumPy).  There is no CPU implementation behind this function.
+    A CUDA tensor that requires grad gives a differentiable result (input
+    gradient: ``isd_features_backward``; the forward values are unchanged).
     """
     as_numpy = not (isinstance(trials, torch.Tensor) and trials.is_cuda)
     if as_numpy:

@@ -134,6 +134,21 @@ int isd_features_fused_bf16(const isd_fb_plan* fb, const isd_stft_plan* st, cons
  *   block-sum kernels. */
 int isd_features_fused_last_path(void);
 
+/* Input gradient of the extractor (spec S backward): dx = d<dfeat, feat(x)>/dx for the feature map that
+ * isd_features_fused / isd_fb_forward + isd_stft_bandpower compute from x with the same plans, bins, mode and eps --
+ * whichever kernel computed it.  The attributions of scripts/explain_fast.py / global_shap_analysis.py (gradients
+ * w.r.t. the raw trials) through the feature classifiers.
+ *   x [B][C][T] f32, dfeat [B][n_bands][C][J] f32, dx [B][C][T] f32 (overwritten).
+ * Any STFT plan (power-of-two nperseg, any noverlap, ragged T), f32 / f64 / mixed filterbank plans, all three modes.
+ * The filtered signals are recomputed per row and band, never materialised for the batch: `workspace` holds
+ * isd_features_backward_workspace_bytes bytes (per-row scratch, bounded; larger batches run in row chunks).
+ * Deterministic: no atomics, the bands are summed in a fixed order, and a trial's dx is the same at any batch size. */
+int64_t isd_features_backward_workspace_bytes(const isd_fb_plan* fb, const isd_stft_plan* st, int64_t B, int64_t C,
+                                              const int* klo, const int* khi);
+int isd_features_backward(const isd_fb_plan* fb, const isd_stft_plan* st, const float* x, const float* dfeat,
+                          float* dx, void* workspace, int64_t B, int64_t C, const int* klo, const int* khi,
+                          int mode, float eps, void* stream);
+
 /* ------------------------------------------------------------------------
  * Zero-phase FIR filter.  Replaces the band-pass of the SVM baseline,
  *   mne.filter.filter_data(X, 250, l_freq=4, h_freq=40)   notebooks/svm_baseline.ipynb:238-239, :968-969
