@@ -56,6 +56,8 @@ SIGNATURES = {
     "isd_features_fused_last_path": (_i, []),
     "isd_features_backward_workspace_bytes": (_i64, [_p, _p, _i64, _i64, _pi, _pi]),
     "isd_features_backward": (_i, [_p, _p, _p, _p, _p, _p, _i64, _i64, _pi, _pi, _i, _f, _p]),
+    "isd_attr_mix": (_i, [_p, _p, _p, _p, _p, _i64, _i64, _i, _i64, _i, _p]),
+    "isd_attr_accumulate": (_i, [_p, _p, _p, _p, _p, _i64, _i64, _i, _i64, _i, _f, _p]),
     "isd_fir_plan_create": (_i, [C.POINTER(_p), _i, _pd]),
     "isd_fir_plan_destroy": (_i, [_p]),
     "isd_fir_plan_taps": (_i, [_p]),

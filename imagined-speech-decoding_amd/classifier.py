@@ -626,6 +626,54 @@ class _Estimator:
     def score(self, X, y):
         return float((self.predict(X) == np.asarray(y)).mean())
 
+    def _differentiable_logits(self, what):
+        """(network, fn): the fitted network and ``fn(x [m, C, T] requiring grad) -> logits [m, K]`` through its
+        autograd modules -- the eval-mode logits ``decision_function`` returns.  ``what`` names the caller in the
+        refusals (unfitted, not differentiable)."""
+        raise NotImplementedError
+
+    def input_gradient(self, X, target=None, batch_size=256):
+        """d logit[target_i](X_i) / d X_i as float32 NumPy [n, C, T]: the gradient attribution of the reference's
+        explain_fast.py / global_shap_analysis.py (GradientExplainer) through extractor and network.  ``target``: None
+        (the predicted class), an int, or an int array [n].  The fitted network runs in eval mode through its autograd
+        modules; no parameter gradient, running statistic or training flag changes."""
+        net, logits_of = self._differentiable_logits("input_gradient")
+        dev = self._device()
+        n = len(X)
+        n_cls = self._n_classes()
+        tgt = None
+        if target is not None:
+            tgt = np.broadcast_to(np.asarray(target.cpu() if isinstance(target, torch.Tensor) else target), (n,))
+            if tgt.dtype.kind not in "iu":
+                raise TypeError(f"target must hold integer class indices, got dtype {tgt.dtype}")
+            if n and (int(tgt.min()) < 0 or int(tgt.max()) >= n_cls):
+                raise ValueError(f"target must lie in [0, {n_cls})")
+        flags = [(m, m.training) for m in net.modules()]
+        net.eval()
+        outs = []
+        try:
+            for i in range(0, n, batch_size):
+                xb = _to_device(X[i:i + batch_size], dev).detach().requires_grad_(True)
+                with torch.enable_grad():
+                    logits = logits_of(xb)
+                    t = logits.detach().argmax(1) if tgt is None else \
+                        torch.as_tensor(np.ascontiguousarray(tgt[i:i + xb.shape[0]]), dtype=torch.long, device=dev)
+                    gx, = torch.autograd.grad(logits.gather(1, t[:, None]).sum(), xb)
+                outs.append(gx.cpu().numpy())
+        finally:
+            for m, was in flags:
+                m.training = was
+        if not outs:
+            return np.zeros((0,) + tuple(X.shape[1:]), np.float32)
+        return np.concatenate(outs)
+
+    def explain(self, X, background, nsamples=200, ranked_outputs=None, rseed=0, batch_size=256, draws=None):
+        """Expected-gradients attributions of the eval-mode logits (``isd_amd.explain.GradientExplainer`` on this
+        estimator): float32 NumPy [n, C, T, K], or ([n, C, T, R], ranks int64 [n, R]) with ``ranked_outputs=R``."""
+        from .explain import GradientExplainer
+        ex = GradientExplainer(self, background, batch_size=batch_size)
+        return ex.shap_values(X, nsamples=nsamples, ranked_outputs=ranked_outputs, rseed=rseed, draws=draws)
+
 
 class FilterbankCNNClassifier(_Estimator):
     """extract_features (Butterworth filterbank -> STFT -> log band power) -> 4-layer CNN -> Linear.
@@ -700,45 +748,16 @@ class FilterbankCNNClassifier(_Estimator):
             feats[i:i + 4096] = self._inputs(X[i:i + 4096].contiguous())
         return feats, (lambda fb: fb)
 
-    def input_gradient(self, X, target=None, batch_size=256):
-        """d logit[target_i](X_i) / d X_i as float32 NumPy [n, C, T]: the gradient attribution of the reference's
-        explain_fast.py / global_shap_analysis.py (GradientExplainer) through extractor and network.  ``target``: None
-        (the predicted class), an int, or an int array [n].  The fitted network runs in eval mode through its autograd
-        modules; no parameter gradient, running statistic or training flag changes."""
+    def _differentiable_logits(self, what):
         if self.precision == "bf16":
-            raise TypeError("input_gradient: a precision='bf16' estimator has no input gradient (bf16 feature maps and "
+            raise TypeError(f"{what}: a precision='bf16' estimator has no input gradient (bf16 feature maps and "
                             "activations are not differentiated); use precision='fp32'")
-        model = self._fitted_model()
-        dev = self._device()
-        n = len(X)
-        n_cls = self._n_classes()
-        tgt = None
-        if target is not None:
-            tgt = np.broadcast_to(np.asarray(target.cpu() if isinstance(target, torch.Tensor) else target), (n,))
-            if tgt.dtype.kind not in "iu":
-                raise TypeError(f"target must hold integer class indices, got dtype {tgt.dtype}")
-            if n and (int(tgt.min()) < 0 or int(tgt.max()) >= n_cls):
-                raise ValueError(f"target must lie in [0, {n_cls})")
-        net = model.net
-        flags = [(m, m.training) for m in net.modules()]
-        net.eval()
-        outs = []
-        try:
-            for i in range(0, n, batch_size):
-                xb = _to_device(X[i:i + batch_size], dev).detach().requires_grad_(True)
-                with torch.enable_grad():
-                    f = self._extractor(xb.shape[-1])(xb, fused=self.fused)
-                    logits = net(f.view(f.shape[0], -1, f.shape[-1]))
-                    t = logits.detach().argmax(1) if tgt is None else \
-                        torch.as_tensor(np.ascontiguousarray(tgt[i:i + xb.shape[0]]), dtype=torch.long, device=dev)
-                    gx, = torch.autograd.grad(logits.gather(1, t[:, None]).sum(), xb)
-                outs.append(gx.cpu().numpy())
-        finally:
-            for m, was in flags:
-                m.training = was
-        if not outs:
-            return np.zeros((0,) + tuple(X.shape[1:]), np.float32)
-        return np.concatenate(outs)
+        net = self._fitted_model().net
+
+        def logits(xb):
+            f = self._extractor(xb.shape[-1])(xb, fused=self.fused)
+            return net(f.view(f.shape[0], -1, f.shape[-1]))
+        return net, logits
 
 
 class FilterbankEEGNetClassifier(FilterbankCNNClassifier):
@@ -789,6 +808,10 @@ class FASTHeadClassifier(_Estimator):
     def _build(self, X):
         cfg = self.config or fast_config(ELECTRODES, ZONES, seq_len=int(X.shape[-1]))
         return _FastModel(cfg)
+
+    def _differentiable_logits(self, what):
+        net = self._fitted_model().net
+        return net, lambda xb: net(xb, "train_head")
 
     def load_reference_state_dict(self, sd, X_like=None):
         """Load a reference FAST state_dict (keys ``head.encoders...``, ``input_layer.0...``, ``last_layer...``).

@@ -150,6 +150,28 @@ int isd_features_backward(const isd_fb_plan* fb, const isd_stft_plan* st, const 
                           int mode, float eps, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Expected gradients (scripts/explain_fast.py, global_shap_analysis.py:
+ *   shap.GradientExplainer(model, background).shap_values(X), local_smoothing = 0):
+ *   phi_k[i] = (1/S) sum_s (x_i - b_r) * df_k/dx (b_r + alpha_is (x_i - b_r)),   r = ridx[i][s].
+ * The two kernels are the sampling arithmetic around the model's forward and backward passes; the draws (ridx, alpha)
+ * are made on the host (isd_amd.explain.draw_samples) and live on the device as [n][S] arrays.  A pair is
+ * p = i * S + s; a TILE is the pairs pair0 .. pair0 + n_pairs - 1 and may start and end inside a trial.
+ *   x [n][E] f32, bg [M][E] f32 (E = C*T elements per trial, any E >= 1: rows need dword alignment only),
+ *   ridx [n*S] int32 in [0, M) -- checked by the caller, not here --, alpha [n*S] f32.
+ * ---------------------------------------------------------------------- */
+/* out [n_pairs][E]: out[q] = fmaf(alpha[p], x[p / S] - bg[ridx[p]], bg[ridx[p]]),  p = pair0 + q */
+int isd_attr_mix(const float* x, const float* bg, const int32_t* ridx, const float* alpha, float* out,
+                 int64_t n_pairs, int64_t pair0, int S, int64_t E, int M, void* stream);
+/* grad [n_pairs][E]: the model's gradient at the tile's interpolated inputs; acc [n][E] (zeroed by the caller before
+ * the first tile).  For every trial i with pairs in the tile and every element e, in s order within one thread,
+ *   acc[i][e] = fmaf(x[i][e] - bg[ridx[p]][e], grad[p - pair0][e], acc[i][e]);
+ * the difference is recomputed, never stored.  No atomics and no cross-lane sums: the bits do not depend on how the
+ * pairs are cut into tiles, provided the tiles are passed in order.  A trial whose last pair (s = S - 1) lies in the
+ * tile is multiplied by `scale` (1/S for the mean; 1 to keep the sum) after that pair, once. */
+int isd_attr_accumulate(const float* x, const float* bg, const int32_t* ridx, const float* grad, float* acc,
+                        int64_t n_pairs, int64_t pair0, int S, int64_t E, int M, float scale, void* stream);
+
+/* ------------------------------------------------------------------------
  * Zero-phase FIR filter.  Replaces the band-pass of the SVM baseline,
  *   mne.filter.filter_data(X, 250, l_freq=4, h_freq=40)   notebooks/svm_baseline.ipynb:238-239, :968-969
  * (MNE is a third-party dependency that is not vendored in the reference; its documented defaults are restated:
