@@ -159,6 +159,24 @@ def check(rc):
     return rc
 
 
+class Handle:
+    """Owner of one library plan: ``_create`` fills ``_h`` through a ``*_plan_create`` entry point, and the wrapper's
+    end releases it through the entry point the subclass names in ``_destroy``."""
+    _destroy = None
+
+    def _create(self, create, *args):
+        self._h = C.c_void_p()
+        check(getattr(lib(), create)(C.byref(self._h), *args))
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            try:
+                getattr(lib(), self._destroy)(h)
+            except Exception:
+                pass
+
+
 def int_array(vals):
     return (C.c_int * len(vals))(*[int(v) for v in vals])
 

@@ -17,24 +17,16 @@ from . import _lib
 from .filter_design import fir_design
 
 
-class FirFilter:
+class FirFilter(_lib.Handle):
     """Plan for one zero-phase FIR filter: host taps (float64) + the device tables of csrc/fir.hip."""
+    _destroy = "isd_fir_plan_destroy"
 
     def __init__(self, sfreq, l_freq, h_freq, filter_length="auto", l_trans_bandwidth="auto",
                  h_trans_bandwidth="auto", fir_window="hamming", taps=None):
         self.sfreq, self.l_freq, self.h_freq = float(sfreq), l_freq, h_freq
         self.taps = (np.ascontiguousarray(taps, dtype=np.float64) if taps is not None else
                      fir_design(sfreq, l_freq, h_freq, filter_length, l_trans_bandwidth, h_trans_bandwidth, fir_window))
-        self._h = C.c_void_p()
-        _lib.check(_lib.lib().isd_fir_plan_create(C.byref(self._h), len(self.taps), _lib.double_array(self.taps)))
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            try:
-                _lib.lib().isd_fir_plan_destroy(h)
-            except Exception:
-                pass
+        self._create("isd_fir_plan_create", len(self.taps), _lib.double_array(self.taps))
 
     def __call__(self, x, out=None):
         """x CUDA tensor [..., T], float32 (fp32 arithmetic) or float64 (fp64 arithmetic) -> same shape / dtype."""

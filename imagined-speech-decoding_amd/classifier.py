@@ -7,7 +7,6 @@ The step itself bypasses autograd: feature kernels -> conv stack -> FC head -> s
 kernels write straight into ONE flat gradient block, which data-parallel training all-reduces once
 (RCCL over xGMI through ``torch.distributed``), followed by one AdamW step on the flat parameter.
 """
-import ctypes as C
 
 import numpy as np
 import torch
@@ -16,8 +15,8 @@ import torch.nn as nn
 from . import _lib
 from .constants import BANDS_9, BANDS_40, CLASSES, ELECTRODES, ZONES
 from .features import FeatureExtractor
-from .nn import (FAST, EEGNet_Encoder, FeatureCNN, _FlatParamMixin, _dropout_seed, _stream, eegnet_backward,
-                 eegnet_forward, fast_config, token_mean_predict)
+from .nn import (FAST, EEGNet_Encoder, FeatureCNN, _FlatParamMixin, _stream, bn_head_backward, bn_head_forward,
+                 bn_head_workspace_floats, fast_config, token_mean_predict)
 
 
 def cosine_scheduler(base_value, final_value, epochs, niter_per_ep, warmup_epochs=0, start_warmup_value=0):
@@ -189,9 +188,21 @@ class HotPath:
             raise TypeError("a bfloat16 input is taken by the one-call classifier step only (isd_featcnn_step_bf16)")
         feat = self._buf("feat", B * N * plan.n_zones * plan.F, dev)
         _lib.check(L.isd_conv4_forward(plan._h, x.data_ptr(), fp, feat.data_ptr(), ws.data_ptr(), B, T, st))
-        # dense layers
+        out, dfeat = self._dense_tail(feat, B, N, plan.n_zones * plan.F, flat, offs, labels, global_batch, gflat)
+        if dfeat is not None:
+            _lib.check(L.isd_conv4_backward(plan._h, x.data_ptr(), fp, dfeat.data_ptr(), gflat.data_ptr(), ws.data_ptr(),
+                                            B, T, st))
+        return out
+
+    def _dense_tail(self, feat, B, N, K, flat, offs, labels, global_batch, gflat):
+        """Dense layers (``flat`` / ``offs`` of ``_layout``) -> token-mean softmax-CE -> dense backward on the resident
+        feature block ``feat`` [B*N, K].  Returns (dict(logits, pred[, loss]), the gradient w.r.t. ``feat``); with
+        labels and a gradient block ``gflat`` the dense layers' gradients are written into it, else the second is None."""
+        L, want_grad = _lib.lib(), gflat is not None
+        dev, st = feat.device, _stream()
+        fp, f4 = flat.data_ptr(), 4
         acts, pres = [feat], []
-        M, K = B * N, plan.n_zones * plan.F
+        M = B * N
         n_lin = len(offs)
         for i, (wo, bo, nout, nin) in enumerate(offs):
             assert nin == K
@@ -210,7 +221,7 @@ class HotPath:
         if labels is None:
             _lib.check(L.isd_softmax_ce(acts[-1].data_ptr(), 0, 0, logits.data_ptr(), 0, 0, pred.data_ptr(), B, N,
                                         n_cls, 1.0, 0, st))
-            return out
+            return out, None
         loss = torch.empty((), dtype=torch.float32, device=dev)
         dlt = self._buf("dlt", M * n_cls, dev)
         scale = 1.0 / float(global_batch or B)
@@ -220,7 +231,7 @@ class HotPath:
                                     scale, cws.data_ptr(), st))
         out["loss"] = loss
         if not want_grad:
-            return out
+            return out, None
         gp = gflat.data_ptr()
         dy = dlt
         for i in range(n_lin - 1, -1, -1):
@@ -232,8 +243,7 @@ class HotPath:
                                              0 if pres[i] is None else pres[i].data_ptr(), dx.data_ptr(),
                                              gp + wo * f4, gp + bo * f4, lws.data_ptr(), M, nin, nout, act, st))
             dy = dx
-        _lib.check(L.isd_conv4_backward(plan._h, x.data_ptr(), fp, dy.data_ptr(), gp, ws.data_ptr(), B, T, st))
-        return out
+        return out, dy
 
 
 class _EEGNetFeatureNet(nn.Module):
@@ -287,55 +297,20 @@ class EEGNetPath(HotPath):
         return True
 
     def _forward(self, x, labels, global_batch, want_grad):
-        m, L = self.model, _lib.lib()
-        enc, fc = m.net.enc, m.net.fc
-        flat = m.flat_params()
+        m = self.model
+        flat, _, offs = self._layout()
         gflat = m.flat_grads() if want_grad else None
-        bufs = enc.flat_buffers()
         B, _, T = x.shape
-        plan = enc._plan_for(T, x.dtype)
-        dev, st = x.device, _stream()
-        n_enc = plan.n_params
-        F_, n_cls = fc.in_features, fc.out_features
-        fp, f4 = flat.data_ptr(), 4
-        wo, bo = n_enc, n_enc + fc.weight.numel()
-        training = bool(want_grad and labels is not None)
-        bn = enc._bns()[0]
-        p_drop = enc.p if training else 0.0
-        enc._calls += 1
-        seed = _dropout_seed(enc._stream_id, enc._calls)
-        if training:
-            for b in enc._bns():
-                b.num_batches_tracked += 1
-        ws = self._buf("eeg", int(L.isd_eegnet_workspace_bytes(plan._h, B)) // 4, dev)
-        h = self._buf("h", B * F_, dev)
+        # the encoder's parameters and gradients lead the model's flat blocks (no_grad: no autograd node for its theta)
+        with torch.no_grad():
+            call = m.net.enc._head_call(T, x.dtype, training=want_grad and labels is not None)._replace(theta=flat)
+        ws = self._buf("eeg", bn_head_workspace_floats(call, B), x.device)
+        h = self._buf("h", B * call.plan.F, x.device)
         # data parallel: BatchNorm over the global batch (the sum blocks are all-reduced between the stages)
-        world = eegnet_forward(plan, x, flat, bufs, h, ws, training, 0.1 if bn.momentum is None else float(bn.momentum),
-                               float(bn.eps), float(p_drop), seed, getattr(enc, "sync_bn", True))
-        ytok = self._buf("ytok", B * n_cls, dev)
-        _lib.check(L.isd_linear_forward(h.data_ptr(), fp + wo * f4, fp + bo * f4, ytok.data_ptr(), 0, B, F_, n_cls, 0, st))
-        logits = torch.empty((B, n_cls), dtype=torch.float32, device=dev)
-        pred = torch.empty((B,), dtype=torch.int64, device=dev)
-        out = {"logits": logits, "pred": pred}
-        if labels is None:
-            _lib.check(L.isd_softmax_ce(ytok.data_ptr(), 0, 0, logits.data_ptr(), 0, 0, pred.data_ptr(), B, 1, n_cls,
-                                        1.0, 0, st))
-            return out
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        dlt = self._buf("dlt", B * n_cls, dev)
-        cws = self._buf("cews", int(L.isd_softmax_ce_workspace_bytes(B)) // 4 + 1, dev)
-        _lib.check(L.isd_softmax_ce(ytok.data_ptr(), labels.data_ptr(), labels.element_size(), logits.data_ptr(),
-                                    loss.data_ptr(), dlt.data_ptr() if training else 0, pred.data_ptr(), B, 1, n_cls,
-                                    1.0 / float(global_batch or B), cws.data_ptr(), st))
-        out["loss"] = loss
-        if not training:
-            return out
-        gp = gflat.data_ptr()
-        dh = self._buf("dh", B * F_, dev)
-        lws = self._buf("lws", int(L.isd_linear_workspace_bytes(B, F_, n_cls)) // 4 + 64, dev)
-        _lib.check(L.isd_linear_backward(h.data_ptr(), fp + wo * f4, dlt.data_ptr(), 0, dh.data_ptr(), gp + wo * f4,
-                                         gp + bo * f4, lws.data_ptr(), B, F_, n_cls, 0, st))
-        eegnet_backward(plan, x, flat, dh, gflat, ws, float(p_drop), seed, world)
+        world = bn_head_forward(call, x, h, ws)
+        out, dh = self._dense_tail(h, B, 1, call.plan.F, flat, offs, labels, global_batch, gflat)
+        if dh is not None:
+            bn_head_backward(call, x, dh, gflat, ws, world)
         return out
 
 

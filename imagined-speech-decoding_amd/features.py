@@ -40,28 +40,19 @@ def band_bins(fs, nperseg, bands):
     return out
 
 
-class Filterbank:
+class Filterbank(_lib.Handle):
     """Butterworth band-pass filterbank plan (``butter(order, band, 'bandpass', fs, 'sos')`` + ``sosfilt``)."""
+    _destroy = "isd_fb_plan_destroy"
 
     def __init__(self, bands, fs, order=4, precision="auto"):
         self.bands = band_edges(bands)
         self.fs, self.order = float(fs), int(order)
         a12, gain = filterbank_tables(self.bands, self.fs, self.order)
         self.a12, self.gain = a12, gain
-        self._h = C.c_void_p()
-        _lib.check(_lib.lib().isd_fb_plan_create(C.byref(self._h), len(self.bands), self.order,
-                                                 _lib.double_array(a12.ravel()), _lib.double_array(gain),
-                                                 _PREC[precision]))
+        self._create("isd_fb_plan_create", len(self.bands), self.order, _lib.double_array(a12.ravel()),
+                     _lib.double_array(gain), _PREC[precision])
         self.precision = {_lib.FB_F32: "f32", _lib.FB_F64: "f64", _lib.FB_MIXED: "mixed"}[
             int(_lib.lib().isd_fb_plan_precision(self._h))]          # "mixed": per-band fp32 / fp64 (auto)
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            try:
-                _lib.lib().isd_fb_plan_destroy(h)
-            except Exception:
-                pass
 
     @property
     def n_bands(self):
@@ -81,24 +72,16 @@ class Filterbank:
         return out
 
 
-class Stft:
+class Stft(_lib.Handle):
     """scipy-legacy STFT plan (periodic Hann, zero boundary, padded, one-sided, 'spectrum' scaling)."""
+    _destroy = "isd_stft_plan_destroy"
 
     def __init__(self, T, nperseg=64, noverlap=None):
         self.T, self.nperseg = int(T), int(nperseg)
         self.noverlap = self.nperseg // 2 if noverlap is None else int(noverlap)
-        self._h = C.c_void_p()
-        _lib.check(_lib.lib().isd_stft_plan_create(C.byref(self._h), self.T, self.nperseg, self.noverlap))
+        self._create("isd_stft_plan_create", self.T, self.nperseg, self.noverlap)
         self.n_frames = _lib.lib().isd_stft_plan_frames(self._h)
         self.n_bins = _lib.lib().isd_stft_plan_bins(self._h)
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            try:
-                _lib.lib().isd_stft_plan_destroy(h)
-            except Exception:
-                pass
 
     def forward(self, x):
         """x f32 CUDA [..., T] -> complex64 CUDA [..., n_bins, n_frames] (scipy's Zxx layout)."""

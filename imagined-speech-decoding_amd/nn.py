@@ -14,6 +14,7 @@ optimizer.
 import ctypes as C
 import math
 import os
+from typing import NamedTuple
 
 import torch
 import torch.nn as nn
@@ -33,32 +34,23 @@ def _f32c(t, name):
 
 
 # ----------------------------------------------------------------------------- plans
-class ConvStackPlan:
+class ConvStackPlan(_lib.Handle):
     """isd_conv4_plan wrapper: static geometry of a zone-wise Conv4Layers stack."""
+    _destroy = "isd_conv4_plan_destroy"
 
     def __init__(self, c_total, zone_idx, feature_dim, n_layers, window_len, slide_step, act_dtype="f32"):
         self.c_total, self.zone_idx = int(c_total), [list(map(int, z)) for z in zone_idx]
         self.F, self.n_layers = int(feature_dim), int(n_layers)
         self.window_len, self.slide_step = int(window_len), int(slide_step)
-        self._h = C.c_void_p()
         sizes = [len(z) for z in self.zone_idx]
         flat = [c for z in self.zone_idx for c in z]
-        _lib.check(_lib.lib().isd_conv4_plan_create(C.byref(self._h), self.c_total, len(sizes), _lib.int_array(sizes),
-                                                    _lib.int_array(flat), self.F, self.n_layers, self.window_len,
-                                                    self.slide_step))
+        self._create("isd_conv4_plan_create", self.c_total, len(sizes), _lib.int_array(sizes), _lib.int_array(flat),
+                     self.F, self.n_layers, self.window_len, self.slide_step)
         self.n_params = int(_lib.lib().isd_conv4_param_count(self._h))
         if act_dtype not in ("f32", "bf16"):
             raise ValueError("act_dtype must be 'f32' or 'bf16'")
         self.act_dtype = act_dtype
         _lib.check(_lib.lib().isd_conv4_plan_set_activation_dtype(self._h, 1 if act_dtype == "bf16" else 0))
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            try:
-                _lib.lib().isd_conv4_plan_destroy(h)
-            except Exception:
-                pass
 
     @property
     def n_zones(self):
@@ -206,20 +198,19 @@ class _SoftmaxCEFn(torch.autograd.Function):
 _HEAD_X_DTYPES = {torch.float32: 0, torch.bfloat16: 1}    # ISD_ACT_F32 / ISD_ACT_BF16
 
 
-class EEGNetPlan:
+class EEGNetPlan(_lib.Handle):
     """isd_eegnet_plan wrapper.  ``dtype``: element type of the input x, float32 or bfloat16 (a bf16 map is widened
     to fp32 on load, exactly; the head's arithmetic is the fp32 one)."""
+    _destroy = "isd_eegnet_plan_destroy"
 
     def __init__(self, in_channels, feature_dim, kernel_length, T, cvblock=False, dtype=torch.float32):
         if dtype not in _HEAD_X_DTYPES:
             raise TypeError(f"the EEGNet / CVBlock input is float32 or bfloat16, got {dtype}")
-        self._h = C.c_void_p()
         if cvblock:
-            _lib.check(_lib.lib().isd_cvblock_plan_create(C.byref(self._h), int(in_channels), int(feature_dim), int(T)))
+            self._create("isd_cvblock_plan_create", int(in_channels), int(feature_dim), int(T))
             self.flat_dim = int(_lib.lib().isd_cvblock_flat_dim(self._h))
         else:
-            _lib.check(_lib.lib().isd_eegnet_plan_create(C.byref(self._h), int(in_channels), int(feature_dim),
-                                                         int(kernel_length), int(T)))
+            self._create("isd_eegnet_plan_create", int(in_channels), int(feature_dim), int(kernel_length), int(T))
         self.n_params = int(_lib.lib().isd_eegnet_param_count(self._h))
         self.F = int(feature_dim)
         self.dtype = dtype
@@ -232,21 +223,69 @@ class EEGNetPlan:
         self._seed_dev = counter                          # keeps the tensor alive
         _lib.check(_lib.lib().isd_eegnet_plan_set_seed_counter(self._h, 0 if counter is None else counter.data_ptr()))
 
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            try:
-                _lib.lib().isd_eegnet_plan_destroy(h)
-            except Exception:
-                pass
+
+class PaperHeadPlan(_lib.Handle):
+    _destroy = "isd_paperhead_plan_destroy"
+
+    def __init__(self, in_channels, feature_dim, T):
+        self._create("isd_paperhead_plan_create", int(in_channels), int(feature_dim), int(T))
+        self.n_params = int(_lib.lib().isd_paperhead_param_count(self._h))
+        self.F = int(feature_dim)
+
+
+class _HeadKind(NamedTuple):
+    """What tells the two C-ABI families of BatchNorm heads apart: the entry points by name, and the four things
+    their argument lists differ in.  Everything else about driving a head is shared (``bn_head_forward`` /
+    ``bn_head_backward``)."""
+    forward: str
+    forward_stage: str
+    backward: str
+    backward_stage: str
+    backward_x: str
+    sync_block: str
+    sync_block_kind: str
+    workspace_bytes: str
+    stages: int         # of the staged pass, per direction (a BatchNorm sum block is exchanged after all but the last)
+    dropout: bool       # the passes take (dropout_p, seed)
+    bf16_x: bool        # a bfloat16 input map is taken (by a plan built for it)
+    eval_keep: int      # ``training`` of an eval-mode forward that keeps its activations for ``backward_x``
+
+    def mode(self, training, keep):
+        """The ABI's ``training`` integer of ``forward`` and ``backward_x``: 1 batch statistics, 0 running statistics,
+        ``eval_keep`` running statistics with a backward pass to follow."""
+        return 1 if training else (self.eval_keep if keep else 0)
+
+
+_EEG_KIND = _HeadKind(                                      # EEGNet_Encoder and CVBlock (one plan type)
+    "isd_eegnet_forward", "isd_eegnet_forward_stage", "isd_eegnet_backward", "isd_eegnet_backward_stage",
+    "isd_eegnet_backward_x", "isd_eegnet_sync_block", "isd_eegnet_sync_block_kind", "isd_eegnet_workspace_bytes",
+    stages=4, dropout=True, bf16_x=True, eval_keep=2)
+_PAPER_KIND = _HeadKind(                                    # HeadConv_Paper_Version: every forward keeps its activations
+    "isd_paperhead_forward", "isd_paperhead_forward_stage", "isd_paperhead_backward", "isd_paperhead_backward_stage",
+    "isd_paperhead_backward_x", "isd_paperhead_sync_block", "isd_paperhead_sync_block_kind",
+    "isd_paperhead_workspace_bytes", stages=5, dropout=False, bf16_x=False, eval_keep=0)
+
+
+class _HeadCall(NamedTuple):
+    """One forward of one BatchNorm head, as ``_BNStackMixin._head_call`` records it."""
+    kind: _HeadKind
+    theta: torch.Tensor          # the packed parameters
+    bufs: torch.Tensor           # the packed running statistics
+    plan: object
+    training: bool
+    momentum: float
+    eps: float
+    p: float                     # dropout probability of this pass (0 in eval mode and for a kind without dropout)
+    seed: int
+    sync: bool                   # BatchNorm over the global batch when torch.distributed runs more than one rank
 
 
 def _bn_sync_world(sync, training):
-    """(torch.distributed, world size) when BatchNorm statistics are to be synchronised, else (None, 1)."""
+    """The number of ranks BatchNorm statistics are to be synchronised over (1: this pass keeps to its own batch)."""
     import torch.distributed as dist
-    if sync and training and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-        return dist, dist.get_world_size()
-    return None, 1
+    if sync and training and dist.is_available() and dist.is_initialized():
+        return dist.get_world_size()
+    return 1
 
 
 def _all_reduce_block(dist, ws, byte_off, n_words, integer=False):
@@ -262,50 +301,62 @@ def _all_reduce_block(dist, ws, byte_off, n_words, integer=False):
         dist.all_reduce(blk, op=dist.ReduceOp.SUM)
 
 
-def eegnet_forward(plan, x, flat, bufs, out, ws, training, momentum, eps, dropout_p, seed, sync=True):
-    """EEGNet_Encoder / CVBlock forward through the C ABI.  With torch.distributed initialised (world > 1) and
-    ``sync`` the three BatchNorm layers use the statistics of the GLOBAL batch: the pass runs in four
-    stages and the fp64 sum block of each stage is all-reduced in between.  Returns the world size that was used
-    (pass it to ``eegnet_backward``)."""
-    L, B, st = _lib.lib(), x.shape[0], _stream()
-    dist, world = _bn_sync_world(sync, int(training) == 1)      # training: 0 eval, 1 batch statistics, 2 eval + keep
-    args = (x.data_ptr(), flat.data_ptr(), bufs.data_ptr(), out.data_ptr(), ws.data_ptr(), B, int(training),
-            float(momentum), float(eps), float(dropout_p), int(seed))
-    if world == 1:
-        _lib.check(L.isd_eegnet_forward(plan._h, *args, st))
-        return 1
+def _staged_pass(call, stage_fn, direction, args, ws, B, world):
+    """A pass in stages (``direction`` 0 forward, 1 backward): each stage leaves the batch sums of one BatchNorm layer
+    in the workspace, and the block is all-reduced before the next stage reads it."""
+    import torch.distributed as dist
+    k, L, h = call.kind, _lib.lib(), call.plan._h
     off, n = C.c_int64(), C.c_int64()
-    for stage in range(4):
-        _lib.check(L.isd_eegnet_forward_stage(plan._h, stage, *args, world, st))
-        if stage < 3:
-            _lib.check(L.isd_eegnet_sync_block(plan._h, B, 0, stage, C.byref(off), C.byref(n)))
-            _all_reduce_block(dist, ws, off.value, n.value, bool(L.isd_eegnet_sync_block_kind(0, stage)))
+    for stage in range(k.stages):
+        _lib.check(getattr(L, stage_fn)(h, stage, *args, world, _stream()))
+        if stage < k.stages - 1:
+            _lib.check(getattr(L, k.sync_block)(h, B, direction, stage, C.byref(off), C.byref(n)))
+            _all_reduce_block(dist, ws, off.value, n.value, bool(getattr(L, k.sync_block_kind)(direction, stage)))
+
+
+def bn_head_workspace_floats(call, B):
+    return max(int(getattr(_lib.lib(), call.kind.workspace_bytes)(call.plan._h, B)) // 4, 1)
+
+
+def bn_head_forward(call, x, out, ws, keep=False):
+    """Forward of a BatchNorm head through the C ABI: ``out[B, F]`` from ``x``; ``keep``: an eval-mode forward whose
+    activations ``bn_head_backward`` will need.  With torch.distributed initialised (world > 1) and ``call.sync`` the
+    BatchNorm layers of a training pass use the statistics of the GLOBAL batch: the pass runs in stages.  Returns the
+    world size that was used (pass it to ``bn_head_backward``)."""
+    k, B = call.kind, x.shape[0]
+    world = _bn_sync_world(call.sync, call.training)
+    args = (x.data_ptr(), call.theta.data_ptr(), call.bufs.data_ptr(), out.data_ptr(), ws.data_ptr(), B,
+            k.mode(call.training, keep), call.momentum, call.eps) + ((call.p, call.seed) if k.dropout else ())
+    if world == 1:
+        _lib.check(getattr(_lib.lib(), k.forward)(call.plan._h, *args, _stream()))
+    else:
+        _staged_pass(call, k.forward_stage, 0, args, ws, B, world)
     return world
 
 
-def eegnet_backward(plan, x, flat, dout, dflat, ws, dropout_p, seed, world=1):
-    """Parameter gradients of the forward above; ``world`` > 1: the BatchNorm backward sums are all-reduced between the
-    stages and the gradients assembled from global sums arrive pre-divided, so that the gradient all-reduce (SUM) of
+def bn_head_backward(call, x, dout, dflat, ws, world, dx=None):
+    """Parameter gradients of the forward above into ``dflat``, and with ``dx`` the input gradient (single device; the
+    one pass an eval-mode forward has).  ``world`` > 1: the BatchNorm backward sums are all-reduced between the stages
+    and the gradients assembled from global sums arrive pre-divided, so that the gradient all-reduce (SUM) of
     data-parallel training yields the single-device gradient."""
-    L, B, st = _lib.lib(), x.shape[0], _stream()
-    args = (x.data_ptr(), flat.data_ptr(), dout.data_ptr(), dflat.data_ptr(), ws.data_ptr(), B, float(dropout_p),
-            int(seed))
-    if world == 1:
-        _lib.check(L.isd_eegnet_backward(plan._h, *args, st))
-        return
-    import torch.distributed as dist
-    off, n = C.c_int64(), C.c_int64()
-    for stage in range(4):
-        _lib.check(L.isd_eegnet_backward_stage(plan._h, stage, *args, world, st))
-        if stage < 3:
-            _lib.check(L.isd_eegnet_sync_block(plan._h, B, 1, stage, C.byref(off), C.byref(n)))
-            _all_reduce_block(dist, ws, off.value, n.value, bool(L.isd_eegnet_sync_block_kind(1, stage)))
+    k, L, h, B = call.kind, _lib.lib(), call.plan._h, x.shape[0]
+    drop = (call.p, call.seed) if k.dropout else ()
+    args = (x.data_ptr(), call.theta.data_ptr(), dout.data_ptr(), dflat.data_ptr())
+    if dx is not None:
+        if world != 1:
+            raise NotImplementedError("the input gradient of the BatchNorm heads is single-device")
+        _lib.check(getattr(L, k.backward_x)(h, *args, dx.data_ptr(), ws.data_ptr(), B, k.mode(call.training, True),
+                                            *drop, _stream()))
+    elif world == 1:
+        _lib.check(getattr(L, k.backward)(h, *args, ws.data_ptr(), B, *drop, _stream()))
+    else:
+        _staged_pass(call, k.backward_stage, 1, args + (ws.data_ptr(), B) + drop, ws, B, world)
 
 
 def _bf16_head_refusals(x_grad, eval_param_grads):
     """A bfloat16 input has no input gradient, so the BatchNorm heads take it for an eval forward without gradients
     and for a train-mode forward with parameter gradients only (eval-mode parameter gradients run the input-gradient
-    pass, isd_eegnet_backward_x)."""
+    pass, the kind's ``backward_x``)."""
     if x_grad:
         raise TypeError("a bfloat16 x cannot require grad: the EEGNet / CVBlock head has no input gradient for bf16 "
                         "inputs (pass x.float() to differentiate w.r.t. the input)")
@@ -314,38 +365,39 @@ def _bf16_head_refusals(x_grad, eval_param_grads):
                         "have: call the module in train mode, under torch.no_grad(), or with x.float()")
 
 
-def _head_x(x, plan, x_grad, mode):
-    """The input of an EEGNet_Encoder / CVBlock pass: float32, or a bfloat16 map (widened exactly to fp32 on load)."""
-    if x.dtype == torch.float32:
+def _head_x(x, call, x_grad, keep):
+    """The input of a BatchNorm head's pass: float32, or -- EEGNet_Encoder / CVBlock -- a bfloat16 map (widened exactly
+    to fp32 on load)."""
+    if x.dtype == torch.float32 or not call.kind.bf16_x:
         return _f32c(x, "x")
     if x.dtype != torch.bfloat16:
         raise TypeError(f"x must be a float32 or bfloat16 CUDA tensor, got {x.dtype}")
     if not x.is_cuda:
         raise TypeError("x must be a CUDA tensor (the product has no CPU path)")
-    _bf16_head_refusals(x_grad, mode == 2)
-    if plan.dtype != torch.bfloat16:
+    _bf16_head_refusals(x_grad, keep)
+    if call.plan.dtype != torch.bfloat16:
         raise TypeError("a bfloat16 x needs a plan built for bfloat16 input")
     return x if x.is_contiguous() else x.contiguous()
 
 
-class _EEGNetFn(torch.autograd.Function):
-    """EEGNet_Encoder / CVBlock.  Differentiable w.r.t. the parameters and -- single device -- the input trials, in
-    train mode (batch statistics: BatchNorm's mean / variance paths are part of the input gradient) and in eval mode
-    (running statistics: what attribution methods differentiate; the forward then keeps its activations)."""
+class _BNHeadFn(torch.autograd.Function):
+    """EEGNet_Encoder / CVBlock / HeadConv_Paper_Version.  Differentiable w.r.t. the parameters and -- single device --
+    the input trials, in train mode (batch statistics: BatchNorm's mean / variance paths are part of the input
+    gradient) and in eval mode (running statistics: what attribution methods differentiate; the forward then keeps its
+    activations and the backward is the input-gradient pass, asked for or not)."""
 
     @staticmethod
-    def forward(ctx, x, flat, bufs, plan, training, momentum, eps, dropout_p, seed, sync):
-        want_bwd = any(ctx.needs_input_grad[:2])
-        mode = 1 if training else (2 if want_bwd else 0)     # 2: eval-mode statistics, activations kept for backward
-        x, flat = _head_x(x, plan, ctx.needs_input_grad[0], mode), _f32c(flat, "params")
+    def forward(ctx, x, theta, call):
+        keep = not call.training and any(ctx.needs_input_grad[:2])
+        x = _head_x(x, call, ctx.needs_input_grad[0], keep)
+        call = call._replace(theta=_f32c(theta, "params"))
         B = x.shape[0]
-        out = torch.empty((B, plan.F), dtype=torch.float32, device=x.device)
-        ws = torch.empty(max(int(_lib.lib().isd_eegnet_workspace_bytes(plan._h, B)) // 4, 1), dtype=torch.float32,
-                         device=x.device)
+        out = torch.empty((B, call.plan.F), dtype=torch.float32, device=x.device)
+        ws = torch.empty(bn_head_workspace_floats(call, B), dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
-            world = eegnet_forward(plan, x, flat, bufs, out, ws, mode, momentum, eps, dropout_p, seed, sync)
-        ctx.plan, ctx.ws, ctx.dp, ctx.seed, ctx.mode, ctx.world = plan, ws, float(dropout_p), int(seed), mode, world
-        ctx.save_for_backward(x, flat)
+            world = bn_head_forward(call, x, out, ws, keep)
+        ctx.call, ctx.ws, ctx.world = call, ws, world
+        ctx.save_for_backward(x, call.theta)
         return out
 
     @staticmethod
@@ -353,102 +405,11 @@ class _EEGNetFn(torch.autograd.Function):
         x, flat = ctx.saved_tensors
         dflat = torch.empty_like(flat)
         dout = _f32c(dout, "dout")
-        dx = None
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] or not ctx.call.training else None
         with torch.cuda.device(x.device):
-            if ctx.needs_input_grad[0] or ctx.mode == 2:
-                if ctx.world != 1:
-                    raise NotImplementedError("the input gradient of the BatchNorm heads is single-device")
-                dx = torch.empty_like(x)
-                _lib.check(_lib.lib().isd_eegnet_backward_x(ctx.plan._h, x.data_ptr(), flat.data_ptr(), dout.data_ptr(),
-                                                            dflat.data_ptr(), dx.data_ptr(), ctx.ws.data_ptr(), x.shape[0],
-                                                            ctx.mode, ctx.dp, ctx.seed, _stream()))
-                if not ctx.needs_input_grad[0]:
-                    dx = None
-            else:
-                eegnet_backward(ctx.plan, x, flat, dout, dflat, ctx.ws, ctx.dp, ctx.seed, ctx.world)
+            bn_head_backward(ctx.call, x, dout, dflat, ctx.ws, ctx.world, dx)
         ctx.ws = None
-        return dx, dflat, None, None, None, None, None, None, None, None
-
-
-class PaperHeadPlan:
-    def __init__(self, in_channels, feature_dim, T):
-        self._h = C.c_void_p()
-        _lib.check(_lib.lib().isd_paperhead_plan_create(C.byref(self._h), int(in_channels), int(feature_dim), int(T)))
-        self.n_params = int(_lib.lib().isd_paperhead_param_count(self._h))
-        self.F = int(feature_dim)
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            try:
-                _lib.lib().isd_paperhead_plan_destroy(h)
-            except Exception:
-                pass
-
-
-class _PaperHeadFn(torch.autograd.Function):
-    """HeadConv_Paper_Version: parameter gradients and the input gradient, after a train-mode (batch statistics) or an
-    eval-mode (running statistics) forward.  With torch.distributed initialised (world > 1) the four BatchNorm layers
-    use the statistics of the GLOBAL batch: the pass runs in stages and each layer's fp64 sum block is all-reduced in
-    between, as for EEGNet_Encoder / CVBlock."""
-
-    @staticmethod
-    def forward(ctx, x, flat, bufs, plan, training, momentum, eps, sync):
-        x, flat = _f32c(x, "x"), _f32c(flat, "params")
-        B = x.shape[0]
-        L = _lib.lib()
-        out = torch.empty((B, plan.F), dtype=torch.float32, device=x.device)
-        ws = torch.empty(max(int(L.isd_paperhead_workspace_bytes(plan._h, B)) // 4, 1), dtype=torch.float32,
-                         device=x.device)
-        dist, world = _bn_sync_world(sync, training)
-        args = (x.data_ptr(), flat.data_ptr(), bufs.data_ptr(), out.data_ptr(), ws.data_ptr(), B, int(training),
-                float(momentum), float(eps))
-        with torch.cuda.device(x.device):
-            if world == 1:
-                _lib.check(L.isd_paperhead_forward(plan._h, *args, _stream()))
-            else:
-                off, n = C.c_int64(), C.c_int64()
-                for stage in range(5):
-                    _lib.check(L.isd_paperhead_forward_stage(plan._h, stage, *args, world, _stream()))
-                    if stage < 4:
-                        _lib.check(L.isd_paperhead_sync_block(plan._h, B, 0, stage, C.byref(off), C.byref(n)))
-                        _all_reduce_block(dist, ws, off.value, n.value, bool(L.isd_paperhead_sync_block_kind(0, stage)))
-        ctx.plan, ctx.ws, ctx.training, ctx.world = plan, ws, training, world
-        ctx.save_for_backward(x, flat)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        x, flat = ctx.saved_tensors
-        dflat = torch.empty_like(flat)
-        dout = _f32c(dout, "dout")
-        dx = None
-        L, B = _lib.lib(), x.shape[0]
-        with torch.cuda.device(x.device):
-            if ctx.needs_input_grad[0] or not ctx.training:
-                if ctx.world != 1:
-                    raise NotImplementedError("the input gradient of the BatchNorm heads is single-device")
-                dx = torch.empty_like(x)
-                _lib.check(L.isd_paperhead_backward_x(ctx.plan._h, x.data_ptr(), flat.data_ptr(), dout.data_ptr(),
-                                                      dflat.data_ptr(), dx.data_ptr(), ctx.ws.data_ptr(), B,
-                                                      int(ctx.training), _stream()))
-                if not ctx.needs_input_grad[0]:
-                    dx = None
-            elif ctx.world == 1:
-                _lib.check(L.isd_paperhead_backward(ctx.plan._h, x.data_ptr(), flat.data_ptr(), dout.data_ptr(),
-                                                    dflat.data_ptr(), ctx.ws.data_ptr(), B, _stream()))
-            else:
-                import torch.distributed as dist
-                off, n = C.c_int64(), C.c_int64()
-                for stage in range(5):
-                    _lib.check(L.isd_paperhead_backward_stage(ctx.plan._h, stage, x.data_ptr(), flat.data_ptr(),
-                                                              dout.data_ptr(), dflat.data_ptr(), ctx.ws.data_ptr(), B,
-                                                              ctx.world, _stream()))
-                    if stage < 4:
-                        _lib.check(L.isd_paperhead_sync_block(ctx.plan._h, B, 1, stage, C.byref(off), C.byref(n)))
-                        _all_reduce_block(dist, ctx.ws, off.value, n.value, bool(L.isd_paperhead_sync_block_kind(1, stage)))
-        ctx.ws = None
-        return dx, dflat, None, None, None, None, None, None
+        return dx if ctx.needs_input_grad[0] else None, dflat, None
 
 
 class _BNZonesFn(torch.autograd.Function):
@@ -462,58 +423,38 @@ class _BNZonesFn(torch.autograd.Function):
     def forward(ctx, xw, idxs, calls, *thetas):
         L, B, dev = _lib.lib(), xw.shape[0], xw.device
         xs = [_f32c(xw.index_select(1, idx), "x") for idx in idxs]
-        thetas = [_f32c(t, "params") for t in thetas]
-        kind = calls[0][0]
-        ws_bytes = L.isd_eegnet_workspace_bytes if kind == "eeg" else L.isd_paperhead_workspace_bytes
-        outs = [torch.empty((B, c[2].F), dtype=torch.float32, device=dev) for c in calls]
-        wss = [torch.empty(max(int(ws_bytes(c[2]._h, B)) // 4, 1), dtype=torch.float32, device=dev) for c in calls]
+        calls = [c._replace(theta=_f32c(t, "params")) for c, t in zip(calls, thetas)]
+        outs = [torch.empty((B, c.plan.F), dtype=torch.float32, device=dev) for c in calls]
+        wss = [torch.empty(bn_head_workspace_floats(c, B), dtype=torch.float32, device=dev) for c in calls]
         with torch.cuda.device(dev):
-            st = _stream()
             _lib.check(L.isd_zone_batch_begin())
             try:
-                for z, (c, x, th, out, ws) in enumerate(zip(calls, xs, thetas, outs, wss)):
+                for z, (c, x, out, ws) in enumerate(zip(calls, xs, outs, wss)):
                     if z:
                         _lib.check(L.isd_zone_batch_next())
-                    if kind == "eeg":
-                        _, bufs, plan, training, momentum, eps, p, seed = c
-                        _lib.check(L.isd_eegnet_forward(plan._h, x.data_ptr(), th.data_ptr(), bufs.data_ptr(),
-                                                        out.data_ptr(), ws.data_ptr(), B, int(bool(training)),
-                                                        float(momentum), float(eps), float(p), int(seed), st))
-                    else:
-                        _, bufs, plan, training, momentum, eps = c
-                        _lib.check(L.isd_paperhead_forward(plan._h, x.data_ptr(), th.data_ptr(), bufs.data_ptr(),
-                                                           out.data_ptr(), ws.data_ptr(), B, int(bool(training)),
-                                                           float(momentum), float(eps), st))
-                _lib.check(L.isd_zone_batch_launch(st))
+                    bn_head_forward(c, x, out, ws)
+                _lib.check(L.isd_zone_batch_launch(_stream()))
             except Exception:
                 L.isd_zone_batch_abort()
                 raise
-        ctx.calls, ctx.wss, ctx.n = calls, wss, len(calls)
-        ctx.save_for_backward(*xs, *thetas)
+        ctx.calls, ctx.wss = calls, wss
+        ctx.save_for_backward(*xs, *(c.theta for c in calls))
         return torch.stack(outs, dim=1)
 
     @staticmethod
     def backward(ctx, dout):
-        L, n = _lib.lib(), ctx.n
+        L, n = _lib.lib(), len(ctx.calls)
         xs, thetas = ctx.saved_tensors[:n], ctx.saved_tensors[n:]
-        B = xs[0].shape[0]
         dz = _f32c(dout.permute(1, 0, 2), "dout")                  # [Z][B'][F]: one contiguous block per zone
         dflats = [torch.empty_like(t) for t in thetas]
-        kind = ctx.calls[0][0]
         with torch.cuda.device(dz.device):
-            st = _stream()
             _lib.check(L.isd_zone_batch_begin())
             try:
-                for z, (c, x, th, dfl, ws) in enumerate(zip(ctx.calls, xs, thetas, dflats, ctx.wss)):
+                for z, (c, x, dfl, ws) in enumerate(zip(ctx.calls, xs, dflats, ctx.wss)):
                     if z:
                         _lib.check(L.isd_zone_batch_next())
-                    if kind == "eeg":
-                        _lib.check(L.isd_eegnet_backward(c[2]._h, x.data_ptr(), th.data_ptr(), dz[z].data_ptr(),
-                                                         dfl.data_ptr(), ws.data_ptr(), B, float(c[6]), int(c[7]), st))
-                    else:
-                        _lib.check(L.isd_paperhead_backward(c[2]._h, x.data_ptr(), th.data_ptr(), dz[z].data_ptr(),
-                                                            dfl.data_ptr(), ws.data_ptr(), B, st))
-                _lib.check(L.isd_zone_batch_launch(st))
+                    bn_head_backward(c, x, dz[z], dfl, ws, 1)
+                _lib.check(L.isd_zone_batch_launch(_stream()))
             except Exception:
                 L.isd_zone_batch_abort()
                 raise
@@ -908,46 +849,59 @@ class _BNStackMixin(_FlatParamMixin):
         return flat
 
     def _plan_for(self, T, dtype=torch.float32):
-        """The plan for T-sample inputs of element type ``dtype`` (float32, or bfloat16: a bf16 map read directly)."""
-        if dtype not in _HEAD_X_DTYPES:
-            raise TypeError(f"x must be a float32 or bfloat16 CUDA tensor, got {dtype}")
+        """The plan for T-sample inputs of element type ``dtype``: float32, or -- where the kind reads a bf16 map
+        directly -- bfloat16."""
+        if dtype != torch.float32 and not (self._kind.bf16_x and dtype == torch.bfloat16):
+            raise TypeError(f"x must be a float32{' or bfloat16' if self._kind.bf16_x else ''} CUDA tensor, got {dtype}")
         plan = self._plans.get((T, dtype))
         if plan is None:
             plan = self._plans[(T, dtype)] = self._make_plan(T, dtype)
-            if getattr(self, "_seed_dev", None) is not None:
+            if self._kind.dropout and getattr(self, "_seed_dev", None) is not None:
                 plan.set_seed_counter(self._seed_dev)
         return plan
 
     def set_seed_counter(self, counter):
-        """Device-resident dropout step counter (int64 tensor, or None): see ``isd_amd.graph``."""
+        """Device-resident dropout step counter (int64 tensor, or None): see ``isd_amd.graph``.  A kind that draws no
+        masks has nothing to mix it into."""
         self._seed_dev = counter
-        for plan in self._plans.values():
-            plan.set_seed_counter(counter)
+        if self._kind.dropout:
+            for plan in self._plans.values():
+                plan.set_seed_counter(counter)
 
-    def _zone_call(self, T, dtype=torch.float32):
-        """One forward's bookkeeping (call counter, ``num_batches_tracked``) and the arguments of ``_EEGNetFn`` after
-        ``x`` -- also what ``Head`` hands to the zone-batched ``_BNZonesFn`` (always float32 there)."""
-        plan = self._plan_for(T, dtype)
+    def _head_call(self, T, dtype=torch.float32, training=None):
+        """One forward's bookkeeping (call counter, ``num_batches_tracked``) and its ``_HeadCall`` record: what
+        ``_BNHeadFn`` runs, what ``Head`` hands to the zone-batched ``_BNZonesFn`` (always float32 there), and what the
+        autograd-free ``classifier.EEGNetPath`` drives -- which decides ``training`` itself."""
+        kind = self._kind
+        plan = self._plan_for(T, dtype)                 # (refuses a dtype before any counter moves)
         theta = self.packed_theta()
+        training = self.training if training is None else bool(training)
         bn = self._bns()[0]
-        self._calls += 1
-        if self.training:
+        p, seed = 0.0, 0
+        if kind.dropout:
+            self._calls += 1
+            p, seed = float(self.p) if training else 0.0, _dropout_seed(self._stream_id, self._calls)
+        if training:
             for b in self._bns():
                 b.num_batches_tracked += 1
-        return ("eeg", theta, self.flat_buffers(), plan, self.training, 0.1 if bn.momentum is None else bn.momentum,
-                bn.eps, self.p if self.training else 0.0, _dropout_seed(self._stream_id, self._calls),
-                getattr(self, "sync_bn", True))
+        return _HeadCall(kind, theta, self.flat_buffers(), plan, training,
+                         0.1 if bn.momentum is None else float(bn.momentum), float(bn.eps), p, seed,
+                         getattr(self, "sync_bn", True))
 
     def _run(self, x):
-        if x.dtype == torch.bfloat16 and torch.is_grad_enabled():        # refused before any bookkeeping
+        if x.dim() != 3:
+            raise ValueError("expected [batch, channels, time]")
+        if x.dtype == torch.bfloat16 and self._kind.bf16_x and torch.is_grad_enabled():    # refused before any bookkeeping
             _bf16_head_refusals(x.requires_grad, not self.training and any(p.requires_grad for p in self.parameters()))
-        return _EEGNetFn.apply(x, *self._zone_call(x.shape[-1], x.dtype)[1:])
+        call = self._head_call(x.shape[-1], x.dtype)
+        return _BNHeadFn.apply(x, call.theta, call)
 
 
 class EEGNet_Encoder(nn.Module, _BNStackMixin):
     """Drop-in for the reference's ``EEGNet_Encoder(in_channels, feature_dim, kernel_length=64, dropout=0.25)``
     (fast.py:122-167); same sub-module / parameter / buffer names, ``forward(x[B', C, T]) -> [B', feature_dim]``.
     Train-mode dropout uses the library's own counter-based stream (statistically nn.Dropout)."""
+    _kind = _EEG_KIND
 
     def __init__(self, in_channels, feature_dim, kernel_length=64, dropout=0.25):
         super().__init__()
@@ -979,8 +933,6 @@ class EEGNet_Encoder(nn.Module, _BNStackMixin):
         return EEGNetPlan(self.in_channels, self.feature_dim, self.kernel_length, T, dtype=dtype)
 
     def forward(self, x):
-        if x.dim() != 3:
-            raise ValueError("expected [batch, channels, time]")
         return self._run(x)
 
 
@@ -988,6 +940,7 @@ class CVBlock(nn.Module, _BNStackMixin):
     """Drop-in for the reference's ``CVBlock(n_channels, dim_token, dropout=0.5)`` (fast.py:32-100); same parameter /
     buffer names.  The projector width is fixed by a 250-sample window exactly as in the reference (fast.py:66-74),
     so other window lengths raise like the reference's shape mismatch does.  3-D or 4-D ([B', 1, C, T]) input."""
+    _kind = _EEG_KIND
 
     def __init__(self, n_channels, dim_token, dropout=0.5):
         super().__init__()
@@ -1029,7 +982,9 @@ class CVBlock(nn.Module, _BNStackMixin):
 
 class HeadConv_Paper_Version(nn.Module, _BNStackMixin):
     """Drop-in for the reference's ``HeadConv_Paper_Version(in_channels, feature_dim=32)`` (fast.py:170-196); same
-    parameter / buffer names, ``forward(x[B', C, T]) -> [B', feature_dim]``."""
+    parameter / buffer names, ``forward(x[B', C, T]) -> [B', feature_dim]``.  It draws no dropout masks, so it owns
+    no dropout stream."""
+    _kind = _PAPER_KIND
 
     def __init__(self, in_channels, feature_dim=32):
         super().__init__()
@@ -1054,22 +1009,11 @@ class HeadConv_Paper_Version(nn.Module, _BNStackMixin):
                 self.cnn2.weight, self.norm2.weight, self.norm2.bias, self.cnn3.weight, self.norm3.weight,
                 self.norm3.bias, self.cnn4.weight, self.norm4.weight, self.norm4.bias]
 
-    def _zone_call(self, T):
-        plan = self._plans.get(T)
-        if plan is None:
-            plan = self._plans[T] = PaperHeadPlan(self.in_channels, self.feature_dim, T)
-        theta = self.packed_theta()
-        if self.training:
-            for b in self._bns():
-                b.num_batches_tracked += 1
-        bn = self.norm1
-        return ("paper", theta, self.flat_buffers(), plan, self.training, 0.1 if bn.momentum is None else bn.momentum,
-                bn.eps, getattr(self, "sync_bn", True))
+    def _make_plan(self, T, dtype=torch.float32):
+        return PaperHeadPlan(self.in_channels, self.feature_dim, T)
 
     def forward(self, x):
-        if x.dim() != 3:
-            raise ValueError("expected [batch, channels, time]")
-        return _PaperHeadFn.apply(x, *self._zone_call(x.shape[-1])[1:])
+        return self._run(x)
 
 
 class Head(nn.Module, _FlatParamMixin):
@@ -1131,7 +1075,7 @@ class Head(nn.Module, _FlatParamMixin):
                                         # whole rows per workgroup from 128 channels on (csrc/eegnet.hip, stage 1)
         if not encs[0].training and torch.is_grad_enabled() and any(p.requires_grad for e in encs for p in e.parameters()):
             return False                                           # eval-mode gradients: the per-zone backward_x path
-        return _bn_sync_world(getattr(encs[0], "sync_bn", True), encs[0].training)[1] == 1
+        return _bn_sync_world(getattr(encs[0], "sync_bn", True), encs[0].training) == 1
 
     def _per_zone(self, xw):
         """Registry heads other than Conv4Layers: one encoder call per zone on its gathered channels (fast.py:210)."""
@@ -1140,9 +1084,8 @@ class Head(nn.Module, _FlatParamMixin):
             if self.index_dict[area].device != xw.device:
                 self.index_dict[area] = self.index_dict[area].to(xw.device)
         if self._zone_batchable(encs, xw):
-            calls = [enc._zone_call(xw.shape[-1]) for enc in encs]
-            return _BNZonesFn.apply(xw, [self.index_dict[a] for a in self.encoders],
-                                    [(c[0],) + tuple(c[2:-1]) for c in calls], *[c[1] for c in calls])
+            calls = [enc._head_call(xw.shape[-1]) for enc in encs]
+            return _BNZonesFn.apply(xw, [self.index_dict[a] for a in self.encoders], calls, *[c.theta for c in calls])
         # The zones are independent until the stack: each runs on its own HIP stream (forked from / joined to the
         # caller's), so their short kernels overlap on the GPU and, in a captured graph, form parallel branches.
         main = torch.cuda.current_stream(xw.device)

@@ -304,3 +304,22 @@ def test_batchnorm_heads_are_bitwise_repeatable(inn, head):
         assert torch.equal(ta, tb), (head, name, "same launch pattern")
         assert torch.equal(ta, tc), (head, name, "disturbed launch pattern")
     assert bool(torch.isfinite(a[2]).all())
+
+
+def test_paperhead_ignores_the_dropout_seed_counter(inn):
+    """``isd_amd.graph`` hands every encoder that has ``set_seed_counter`` the device-resident dropout step counter,
+    whenever the capture happens.  HeadConv_Paper_Version draws no masks: with a plan already cached (a forward has
+    run) setting and clearing the counter is a no-op, and the next forward carries the bits of a fresh module with the
+    same parameters."""
+    torch.manual_seed(11)
+    m = inn.HeadConv_Paper_Version(6, 32).cuda().eval()
+    x = torch.randn(5, 6, 250, device="cuda")
+    with torch.no_grad():
+        m(x)
+        m.set_seed_counter(torch.zeros(1, dtype=torch.int64, device="cuda"))
+        m.set_seed_counter(None)
+        y = m(x)
+        fresh = inn.HeadConv_Paper_Version(6, 32).cuda().eval()
+        fresh.load_state_dict(m.state_dict())
+        assert torch.equal(y, fresh(x))
+    assert not hasattr(m, "_stream_id")
