@@ -63,6 +63,11 @@ SIGNATURES = {
     "isd_fir_plan_taps": (_i, [_p]),
     "isd_fir_zero_phase_f32": (_i, [_p, _p, _p, _i64, _i, _p]),
     "isd_fir_zero_phase_f64": (_i, [_p, _p, _p, _i64, _i, _p]),
+    "isd_trial_cov_f32": (_i, [_p, _p, _i64, _i, _i, _p]),
+    "isd_trial_cov_f64": (_i, [_p, _p, _i64, _i, _i, _p]),
+    "isd_cov_group_mean": (_i, [_p, _i, _p, _p, _i, _p, _i64, _i, _i, _p]),
+    "isd_csp_power_f32": (_i, [_p, _p, _p, _i64, _i, _i, _i, _i, _p]),
+    "isd_csp_power_f64": (_i, [_p, _p, _p, _i64, _i, _i, _i, _i, _p]),
     "isd_conv4_plan_create": (_i, [C.POINTER(_p), _i, _i, _pi, _pi, _i, _i, _i, _i]),
     "isd_conv4_plan_destroy": (_i, [_p]),
     "isd_conv4_plan_set_activation_dtype": (_i, [_p, _i]),

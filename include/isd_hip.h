@@ -189,6 +189,34 @@ int isd_fir_zero_phase_f32(const isd_fir_plan* plan, const float* x, float* y, i
 int isd_fir_zero_phase_f64(const isd_fir_plan* plan, const double* x, double* y, int64_t rows, int T, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Common Spatial Patterns: the data-sized steps of the transformer behind that band-pass,
+ *   Pipeline(CSP(8, log=True) -> StandardScaler -> SVC)   notebooks/svm_baseline.ipynb:240-248, :307, :316
+ * (mne.decoding.CSP; MNE is not vendored in the reference, its documented behaviour is restated).  The generalised
+ * eigen-decomposition / joint diagonalisation of the [K][C][C] class covariances is host work: isd_amd.csp.decompose.
+ * All pointers are device memory; no call synchronises with the host; 1 <= C <= 128, T >= 1.
+ *
+ * trial_cov:   x [n][C][T] -> cov [n][C][C], cov_i = X_i X_i^T / T: the second moment with no mean removal (MNE's
+ *              empirical estimate for data assumed centred, reg=None).  cov[i][a][b] and cov[i][b][a] are the same
+ *              bits.  The _f32 entry accumulates in fp32 on the fp32-input matrix cores, the _f64 entry in fp64.
+ * group_mean:  cov [n][C][C] (fp64 when cov_f64 != 0, else fp32); idx [offs[K]] int64 trial indices in [0, n), grouped
+ *              by class; offs [K+1] int64 with class k owning idx[offs[k] .. offs[k+1]); out [K][C][C] double,
+ *              out_k = mean over the class's trials of cov_i, each divided by its trace first when norm_trace != 0
+ *              (zeros for an empty class; NaN if an index lies outside [0, n)).  fp64 sums in the order of idx, one
+ *              thread per element, no atomics: bitwise repeatable.
+ * csp_power:   x [n][C][T], w [m][C] (1 <= m <= 16, same dtype) -> out [n][m],
+ *              out[i][j] = mean_t (sum_c w[j][c] x[i][c][t])^2, its natural log when take_log != 0.  The projected
+ *              signal is never written; the sum over T has a fixed order.
+ * ---------------------------------------------------------------------- */
+int isd_trial_cov_f32(const float* x, float* cov, int64_t n, int C, int T, void* stream);
+int isd_trial_cov_f64(const double* x, double* cov, int64_t n, int C, int T, void* stream);
+int isd_cov_group_mean(const void* cov, int cov_f64, const int64_t* idx, const int64_t* offs, int norm_trace,
+                       double* out, int64_t n, int C, int K, void* stream);
+int isd_csp_power_f32(const float* x, const float* w, float* out, int64_t n, int C, int T, int m, int take_log,
+                      void* stream);
+int isd_csp_power_f64(const double* x, const double* w, double* out, int64_t n, int C, int T, int m, int take_log,
+                      void* stream);
+
+/* ------------------------------------------------------------------------
  * Zone-wise Conv4Layers stack over sliding windows: the reference's
  *   FAST.forward_head   src/fast/models/fast.py:242-252  (unfold window_len / slide_step)
  *   Head.forward        src/fast/models/fast.py:209-210  (zone gather, one encoder per zone, stack)
