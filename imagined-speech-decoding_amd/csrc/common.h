@@ -76,9 +76,6 @@ __device__ __forceinline__ double read_lane(double v, int src) {
   return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
 }
 
-// LDS hand-over between the lanes of ONE wave (workgroups of 64 threads): LDS operations of a wave execute in
-// order, so it is enough to wait for the outstanding LDS operations and to keep the compiler from moving accesses
-// across this point.  Unlike __syncthreads() this does not drain vmcnt: global stores and loads stay in flight.
 // GELU (erf form, nn.GELU's default) and its derivative through  erfc(|z|) = t (a1 + t (a2 + ...)) exp(-z^2),
 // t = 1 / (1 + p |z|)  (Abramowitz & Stegun 7.1.26, absolute error 1.5e-7 -- the fp32 rounding level of the
 // activation).  libm's erff is ~100 instructions per element and, where an activation tile ends in GELU and GELU',
@@ -103,9 +100,25 @@ __device__ __forceinline__ float gelu_grad_fast(float x) {
   return fmaf(x * 0.39894228040143267794f, ez, cdf);
 }
 
+// LDS hand-over between the lanes of ONE wave (workgroups of 64 threads): LDS operations of a wave execute in
+// order, so it is enough to wait for the outstanding LDS operations and to keep the compiler from moving accesses
+// across this point.  Unlike __syncthreads() this does not drain vmcnt: global stores and loads stay in flight.
 __device__ __forceinline__ void wave_lds_sync() {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_wave_barrier();
+}
+
+// ------------------------------------------------------------------ host side, HIP sources
+// Launches `kernel` with `lds_bytes` of dynamic LDS and checks the launch.  A kernel may use up to 48 KiB without
+// asking; above that its limit is raised first.
+template <typename... Params, typename... Args>
+static inline int launch_lds(void (*kernel)(Params...), dim3 grid, dim3 block, size_t lds_bytes, hipStream_t stream,
+                             Args... args) {
+  if (lds_bytes > 48 * 1024)
+    ISD_HIP_TRY(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+  hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, args...);
+  ISD_LAUNCH_CHECK();
+  return ISD_OK;
 }
 
 #endif  // __HIPCC__

@@ -416,6 +416,12 @@ __global__ __launch_bounds__(256) void conv5_fwd_kernel(ConvArgs a) {
   }
 }
 
+// dynamic LDS of conv5_fwd_kernel (the in_tile / w_tile lines at its top): 4 floats of slack, in_tile [IPW][CK][RS]
+// rounded up to 16 bytes, w_tile [CK/4][5][GT][64], 32 floats of slack behind it
+static size_t conv5_fwd_lds(int IPW, int CK, int RS, int GT) {
+  return sizeof(float) * (4 + (((size_t)IPW * CK * RS + 3) & ~(size_t)3) + (size_t)(CK / 4) * kTaps * GT * 64 + 32);
+}
+
 // ---------------------------------------------------------------------------------------
 // First-layer forward for wide inputs (spec-S features: hundreds of channels, a handful of time steps):
 // same tiling as conv5_fwd_kernel<0, float> on contiguous rows, but the input and weight chunks are
@@ -555,6 +561,13 @@ __global__ __launch_bounds__(256) void conv5_fwd_glds_kernel(ConvArgs a) {
       }
     }
   }
+}
+
+// dynamic LDS of conv5_fwd_glds_kernel (in_len / w_len / buf_len at its top): 4 floats of slack, then two buffers of
+// in_tile [ipw][kCK][W], w_tile [kCK/4][5][GT][64] and 32 floats of slack
+static size_t conv5_fwd_glds_lds(int ipw, int W, int GT) {
+  const size_t buf = (size_t)(((ipw * kCK * W + 3) & ~3) + (kCK / 4) * kTaps * GT * 64 + 32);
+  return sizeof(float) * (4 + 2 * buf);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -723,6 +736,13 @@ __global__ __launch_bounds__(256) void conv5_fwd_bf16_kernel(ConvArgs a, const u
       *reinterpret_cast<uint2*>((unsigned short*)a.out + ((item * a.Z + z) * a.Tout + jl) * (int64_t)a.F + g) = o;
     }
   }
+}
+
+// dynamic LDS of conv5_fwd_bf16_kernel<2, ...> (in_len / w_len / buf_len at its top): as the LDS-DMA kernel above with
+// w_tile [kCK/4][GT = 2][64] fragments of 16 bytes
+static size_t conv5_fwd_bf16_lds(int ipw, int W) {
+  const size_t buf = (size_t)(((ipw * kCK * W + 3) & ~3) + (kCK / 4) * 2 * 64 * 4 + 32);
+  return sizeof(float) * (4 + 2 * buf);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -994,6 +1014,13 @@ __global__ __launch_bounds__(NW * 64) void conv4_fused_fwd_kernel(FusedFwdArgs a
   }
 }
 
+// dynamic LDS of conv4_fused_fwd_kernel<NW> (xz .. bls at its top): 4 floats of slack, xz [16][W], t2 and t3 [F][T1],
+// red [NW][F], the Weff / cnn3 / cnn4 fragment sets of 4 + 8 + 8 blocks, 64 floats of slack holding beff
+static size_t conv4_fused_fwd_lds(int NW, int F, int W, int T1) {
+  return sizeof(float) * (size_t)(4 + ((16 * W + 3) & ~3) + 2 * ((F * T1 + 3) & ~3) + NW * F +
+                                  (4 + 8 + 8) * kTaps * 2 * 64 + 64);
+}
+
 // ---------------------------------------------------------------------------------------
 // Fused backward of one (window, zone) item for the reference-native shape (companion of conv4_fused_fwd_kernel):
 //   G4 = dfeat/T1 * GELU'(A4);  dW4 += G4 (*) A3;  G3 = W4^T (*) G4;  dW3 += G3 (*) A2;  G2 = W3^T (*) G3;
@@ -1213,6 +1240,13 @@ __global__ __launch_bounds__(NW * 64) void conv4_fused_bwd_kernel(FusedBwdArgs a
       if (jl < kTaps) s0[((int64_t)g0 * cin1 + cz) * kTaps + jl] = jl == 0 ? accb[r] : 0.f;
     }
   }
+}
+
+// dynamic LDS of conv4_fused_bwd_kernel<8> (xz .. dfs at its top): xz [16][W], three tiles [F][T1] with 4 floats of
+// slack before each, the two transposed fragment sets, dfs [32] and 16 floats of slack
+static size_t conv4_fused_bwd_lds(int F, int W, int T1) {
+  const int tile = ((F * T1 + 3) & ~3) + 4;
+  return sizeof(float) * (size_t)(((4 + 16 * W + 3) & ~3) + 4 + 3 * tile + 2 * 8 * kTaps * 2 * 64 + 32 + 16);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1519,6 +1553,13 @@ __global__ __launch_bounds__(NW * 64, 4) void conv4_fused_fwd_bf16_kernel(FusedF
   }
 }
 
+// dynamic LDS of conv4_fused_fwd_bf16_kernel<8> (t2 .. w4s at its top): t2, t3 (its front doubles as the bf16 x tile),
+// row sums [8][32], bias, three Weff fragment sets and the cnn3 / cnn4 sets of 16 bytes per lane
+static size_t conv4_fused_fwd_bf16_lds(int TT) {
+  const size_t tile_f = (size_t)fused16_rows(TT) * 16, w16 = (size_t)kTaps * 2 * 64 * 4;
+  return sizeof(float) * (2 * tile_f + 8 * 32 + 32 + 3 * 2 * 64 * 4 + 2 * w16 + 16);
+}
+
 // transposed 4-row x 16-column block read of a [row][32] bf16 tile: the lane of column c receives rows r0 .. r0 + 3 of
 // that column, packed (lane 4 r + p of the 16-lane group supplies the address of row r, columns 4 p .. 4 p + 3)
 __device__ __forceinline__ unsigned tr_addr(unsigned tile_base, int row0, int col0, int jl) {
@@ -1787,6 +1828,13 @@ __global__ __launch_bounds__(NW * 64) void conv4_fused_bwd_bf16_kernel(FusedBwdA
         if (jl < kTaps) s0[((int64_t)g * cin1 + cz) * kTaps + jl] = jl == 0 ? accb[gt][r] : 0.f;
       }
   }
+}
+
+// dynamic LDS of conv4_fused_bwd_bf16_kernel<8> (sets .. w3s at its top): two sets of {GELU'(A4) / G4 / G2, A3, A2},
+// G3, the bf16 x tile of xt_rows rows and the two transposed fragment sets
+static size_t conv4_fused_bwd_bf16_lds(int TT) {
+  const size_t tile_f = (size_t)fused16_rows(TT) * 16, w16 = (size_t)kTaps * 2 * 64 * 4;
+  return sizeof(float) * (7 * tile_f + (size_t)(32 * ((TT + 1) / 2) + 16) * 8 + 2 * w16 + 16);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -2210,6 +2258,14 @@ __global__ __launch_bounds__(NW * 64) void featcnn_tail_kernel(TailArgs a) {
                             accfc, accb, loss_acc, a.part + (int64_t)blockIdx.x * a.slab, a.slab, n_cls);
 }
 
+// dynamic LDS of featcnn_tail_kernel<NW, false> (w3s .. priv at its top): four fragment sets, the FC weights and bias,
+// per wave and item slot four tiles [F][T1] + 64 floats; at least the epilogue's two accumulator copies
+static size_t featcnn_tail_lds(int NW, int F, int T1) {
+  const int tile = (F * T1 + 3) & ~3;
+  const size_t lds = sizeof(float) * (size_t)(4 * 8 * kTaps * 2 * 64 + kTailMaxCls * (F + 1) + NW * kTailNI * (4 * tile + 64) + 16);
+  return lds < sizeof(float) * 2 * kTailCombCopy ? sizeof(float) * 2 * kTailCombCopy : lds;
+}
+
 // BASELINE config 3, round 3: the same launch on the bf16 matrix cores (v_mfma_f32_16x16x32_bf16).  The fp32-MFMA
 // instance above (featcnn_tail_kernel<., true>: bf16 I/O and bf16-rounded intermediates, 480 v_mfma_f32_16x16x4_f32
 // per item, 256 VGPRs + 172 AGPRs, one wave per SIMD) was the largest kernel of the bf16 classifier stage.  Here the
@@ -2383,6 +2439,13 @@ __global__ __launch_bounds__(NW * 64) void featcnn_tail_bf16_kernel(TailArgs a) 
                             accfc, accb, loss_acc, a.part + (int64_t)blockIdx.x * a.slab, a.slab, n_cls);
 }
 
+// dynamic LDS of featcnn_tail_bf16_kernel<NW> (w3s .. logL at its top): four K = 32 fragment sets, the FC weights and
+// bias, per wave priv_b = four tiles of 40 rows x 64 bytes + 256; at least the epilogue's three accumulator copies
+static size_t featcnn_tail_bf16_lds(int NW, int F) {
+  const size_t lds = (size_t)4 * kTaps * 2 * 64 * 16 + sizeof(float) * kTailMaxCls * (F + 1) + (size_t)NW * (4 * 40 * 64 + 256) + 64;
+  return lds < sizeof(float) * 3 * kTailCombCopy ? sizeof(float) * 3 * kTailCombCopy : lds;
+}
+
 // ---------------------------------------------------------------------------------------
 // GELU + mean over time (fast.py:117-118) and its backward (in place on the activation).
 // one 16-lane row per (item, zone, filter) row of length T
@@ -2452,6 +2515,9 @@ __global__ __launch_bounds__(256) void conv5_dx_kernel(const float* __restrict__
     atomicAdd(&dx[(b * Ctot + chan_idx[zd.idx_off + c]) * (int64_t)Tx + (int64_t)n * S + t], acc);
   }
 }
+
+// dynamic LDS of conv5_dx_kernel: the G2 tile [F][T1]
+static size_t conv5_dx_lds(int F, int T1) { return sizeof(float) * (size_t)F * T1; }
 
 // ---------------------------------------------------------------------------------------
 // Weight gradient: dW[g][c][k] = sum_{item,t} dOut[item][g][t] * In[item][c][t + k - pad].
@@ -2688,6 +2754,11 @@ __global__ __launch_bounds__(256) void conv5_wgrad_kernel(WgradArgs a) {
   }
 }
 
+// dynamic LDS of conv5_wgrad_kernel (do_tile / in_tile at its top): per staged item F rows of RSo gradient samples and
+// CW rows of RSi input samples, IPS items, 4 floats for the rounding of do_sz
+static int64_t conv5_wgrad_item_floats(int F, int RSo, int CW, int RSi) { return (int64_t)F * RSo + (int64_t)CW * RSi; }
+static size_t conv5_wgrad_lds(int ips, int64_t per_item) { return sizeof(float) * ((size_t)ips * per_item + 4); }
+
 // First-layer weight gradient for wide inputs (companion of conv5_fwd_glds_kernel; same preconditions).
 // A workgroup owns 64 input channels (one 16-channel tile per wave, all GT filter tiles) and a range of items;
 // dOut [F][Tout] and the 64 input rows of IPS items are double-buffered in LDS by LDS-DMA; the MFMA loop is
@@ -2818,6 +2889,11 @@ __global__ __launch_bounds__(256) void conv5_wgrad_wide_kernel(WgradArgs a) {
       if (with_bias && jl < kTaps) slab[((int64_t)gg * cin1 + cin) * kTaps + jl] = jl == 0 ? accb[g][r] : 0.f;
     }
 }
+
+// dynamic LDS of conv5_wgrad_wide_kernel and its bf16 twin (item_len / buf_len at their tops): two buffers of IPS items
+// + 32 floats, 8 floats behind them; an item is the gradient tile [F][T1] and 64 input rows of W samples
+static int conv5_wgrad_wide_item_floats(int F, int T1, int W) { return (F * T1 + 64 * W + 3) & ~3; }
+static size_t conv5_wgrad_wide_lds(int ips, int item_len) { return sizeof(float) * (size_t)(2 * (ips * item_len + 32) + 8); }
 
 // ---------------------------------------------------------------------------------------
 // BASELINE config 3: first-layer weight gradient on the bf16 matrix cores (companion of conv5_fwd_bf16_kernel).
@@ -2967,6 +3043,10 @@ __global__ __launch_bounds__(256) void conv5_wgrad_wide_bf16_kernel(WgradArgs a)
       if (with_bias && jl < kTaps) slab[((int64_t)gg * cin1 + cin) * kTaps + jl] = jl == 0 ? accb[g][r] : 0.f;
     }
 }
+
+// an item of conv5_wgrad_wide_bf16_kernel (do_len / in_len at its top): a gradient image of 16 x F bf16 and 64 input
+// rows of W samples
+static int conv5_wgrad_wide_bf16_item_floats(int F, int W) { return (16 * F / 2 + 64 * W + 3) & ~3; }
 
 // sum the per-workgroup slabs: out[e] = sum_s part[s][e].  Block = 64 elements x 4 slab groups
 // (coalesced 256-B rows, 4 independent load streams per element, LDS combine).  blockIdx.y selects a run of
@@ -3206,12 +3286,6 @@ struct isd_conv4_plan {
 };
 
 static inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
-static inline int row_threads(int row_len) {   // power of two in [16, 256] covering a staged row
-  int tw = 16;
-  while (tw < row_len && tw < 256) tw <<= 1;
-  return tw;
-}
-
 extern "C" int isd_conv4_plan_create(isd_conv4_plan** out, int c_total, int n_zones, const int* zone_sizes,
                                      const int* zone_channels, int feature_dim, int n_layers, int window_len,
                                      int slide_step) {
@@ -3303,6 +3377,13 @@ extern "C" int isd_conv4_windows(const isd_conv4_plan* p, int64_t T) {
 }
 
 namespace {
+// Which kernels run the Conv4Layers stack.  choose_route decides it once per call; the forward, the backward and
+// launch_prep only read the result (DESIGN.md lists route -> condition -> kernels).
+enum class Route { kLayerwise, kFusedF32, kFusedBf16 };
+// waves per workgroup of the four fused kernels (measured after the prefetch restructure, B=4096, T=512: 8 waves
+// 25.6 ms/step, 16 waves 25.6, 4 waves 28.3)
+constexpr int kFusedNW = 8;
+
 struct Geo {           // derived sizes for one call
   int N, T1, TT, IPW, RS_a, RS_b, lin0, CK;
   int64_t items, act;  // act = floats of one activation tensor
@@ -3310,6 +3391,11 @@ struct Geo {           // derived sizes for one call
   int64_t o_eff, o_eff16, o_beff, o_w3, o_w3t, o_w4, o_w4t, o_a2, o_a3, o_a4, o_s, o_wg, o_wg34, o_part, total;
   int ipw0, ipw1, ns0, ns1, cw0, cw1, grp0, grp1;   // wgrad: items per wg, slabs (incl. wave groups), channels per wg
   int64_t slab0, slab1;
+  Route route = Route::kLayerwise;
+  int fwd_per_zone = 0, bwd_per_zone = 0;   // fused routes: workgroups per zone
+  size_t fwd_lds = 0, bwd_lds = 0;          // fused routes: dynamic LDS bytes
+  bool keep_dgelu = false;                  // the forward leaves GELU'(A4), not A4, in the A4 buffer; the backward reads it as such
+  bool prep16 = false;                      // prep_fused_kernel writes cnn3 / cnn4 as K = 32 bf16 fragments
 };
 
 int row_stride_fwd(int need) {           // unpadded rows; B-fragment reads touch 4 rows x 16 consecutive t
@@ -3317,6 +3403,46 @@ int row_stride_fwd(int need) {           // unpadded rows; B-fragment reads touc
   int rs = need;
   while (rs % 32 != 16) ++rs;
   return rs;
+}
+
+// persistent workgroups per zone: `per_gpu` over the zones, at least one, at most one per item
+int per_zone_workgroups(const isd_conv4_plan* p, const Geo& g, int per_gpu) {
+  int per_zone = per_gpu / p->Z;
+  if (per_zone < 1) per_zone = 1;
+  if (per_zone > g.items) per_zone = (int)g.items;
+  return per_zone;
+}
+
+int choose_route(const isd_conv4_plan* p, Geo& g) {
+  const int F = p->F;
+  const size_t bwd16 = conv4_fused_bwd_bf16_lds(g.TT);
+  if (p->n_layers == 4 && F == 32 && p->act_bf16 && p->max_cz <= 16 && g.TT <= 16 && g.TT >= 4 && bwd16 <= 160 * 1024) {
+    // reference-native shape, bf16 activations: the fused pair on the bf16 matrix cores; the LDS test is a condition of
+    // the route, not an invariant
+    g.route = Route::kFusedBf16;
+    g.fwd_lds = conv4_fused_fwd_bf16_lds(g.TT);
+    g.bwd_lds = bwd16;
+    g.fwd_per_zone = per_zone_workgroups(p, g, g.fwd_lds <= 80 * 1024 ? 512 : 256);   // two workgroups per CU when the tiles allow
+    g.bwd_per_zone = per_zone_workgroups(p, g, 256);
+    g.keep_dgelu = g.prep16 = true;
+  } else if (p->n_layers == 4 && F == 32 && !p->act_bf16 && p->max_cz <= 16 && g.TT <= 16 && (F * g.T1) % 4 == 0 &&
+             g.TT >= 4) {
+    // reference-native shape: one persistent fused kernel each way (register-resident weights, activations and
+    // gradient tiles through LDS).  The forward always keeps GELU'(A4) on this route:
+    //   TT <= 16  =>  T1 <= 256  =>  W = T1 + 4 <= 260, and both sizes grow monotonically with W.  At W = 260, T1 = 256:
+    //   forward   4 + 4160 + 2 * 8192 + 8 * 32 + 20 * 640 + 64      = 33668 floats = 134672 bytes <= 150 KiB (153600)
+    //   backward  4164 + 4 + 3 * (8192 + 4) + 16 * 640 + 32 + 16   = 39044 floats = 156176 bytes <= 160 KiB (163840)
+    // so both kernels fit for every shape the predicate admits, and neither a forward that keeps plain A4 (store == 1)
+    // nor a fall-through to the layer-wise chain can happen.  The check below fails loudly if a tile size changes that.
+    g.route = Route::kFusedF32;
+    g.fwd_lds = conv4_fused_fwd_lds(kFusedNW, F, p->W, g.T1);
+    g.bwd_lds = conv4_fused_bwd_lds(F, p->W, g.T1);
+    ISD_CHECK_ARG(g.fwd_lds <= 150 * 1024 && g.bwd_lds <= 160 * 1024,
+                  "conv4: the fused fp32 kernels need %zu / %zu bytes of LDS at window_len=%d", g.fwd_lds, g.bwd_lds, p->W);
+    g.fwd_per_zone = g.bwd_per_zone = per_zone_workgroups(p, g, 256);
+    g.keep_dgelu = true;
+  }
+  return ISD_OK;
 }
 
 int make_geo(const isd_conv4_plan* p, int64_t B, int64_t T, Geo& g) {
@@ -3365,7 +3491,6 @@ int make_geo(const isd_conv4_plan* p, int64_t B, int64_t T, Geo& g) {
   g.slab1 = (int64_t)p->Z * p->F * p->F * kTaps;
   g.o_wg34 = o; o += align_up(g.slab1, 64);
   // wgrad slabs: ~1024 workgroups over (item ranges) x zones x channel groups
-  const int GT = p->F / 16;
   auto plan_wg = [&](int cin_max, int& cw, int& ipw, int& ns, int& grp) {
     cw = cin_max >= 64 ? 64 : (int)align_up(cin_max, 16);
     grp = 4 / (cw / 16);                                    // wave groups of the kernel (cw is 16, 32 or 64)
@@ -3387,7 +3512,56 @@ int make_geo(const isd_conv4_plan* p, int64_t B, int64_t T, Geo& g) {
   const int64_t pmax = pa > pb ? pa : pb;
   g.o_part = o; o += align_up(pmax > pf ? pmax : pf, 64);
   g.total = o;
-  return ISD_OK;
+  return choose_route(p, g);
+}
+
+// the geometry fields that ConvArgs, WgradArgs, FusedFwdArgs and FusedBwdArgs share under the same names
+template <typename Args>
+void fill_geometry(Args& a, const isd_conv4_plan* p, const Geo& g, int64_t T) {
+  a.zones = p->d_zones; a.chan_idx = p->d_idx; a.items = g.items; a.Z = p->Z;
+  a.Ctot = p->Ctot; a.Tx = (int)T; a.N = g.N; a.S = p->S;
+}
+// the fused pair additionally shares the window geometry and the stride of the cnn3 / cnn4 fragment blocks
+template <typename Args>
+void fill_fused_geometry(Args& a, const isd_conv4_plan* p, const Geo& g, int64_t T) {
+  fill_geometry(a, p, g, T);
+  a.wz_stride = p->conv_zstride; a.W = p->W; a.T1 = g.T1; a.TT = g.TT;
+}
+// the fields every conv5_fwd launch of a call shares; the layer fills in, out, wfrag, bias, Tin, pad, RS, lin, wz_stride
+ConvArgs make_conv_args(const isd_conv4_plan* p, const Geo& g, int64_t T) {
+  ConvArgs a = {};
+  fill_geometry(a, p, g, T);
+  a.F = p->F; a.TT = g.TT; a.IPW = g.IPW; a.Tout = g.T1; a.CK = g.CK;
+  return a;
+}
+// the fields every wgrad launch of a call shares; the layer fills the rest
+WgradArgs make_wgrad_args(const isd_conv4_plan* p, const Geo& g, int64_t T, float* ws) {
+  WgradArgs w = {};
+  fill_geometry(w, p, g, T);
+  w.F = p->F; w.Tout = g.T1; w.part = ws + g.o_part;
+  return w;
+}
+FusedFwdArgs make_fused_fwd_args(const isd_conv4_plan* p, const Geo& g, const float* x, float* feat, float* ws, int64_t T) {
+  FusedFwdArgs fa = {};
+  fill_fused_geometry(fa, p, g, T);
+  fa.x = x; fa.weff = ws + g.o_eff; fa.beff = ws + g.o_beff; fa.w3 = ws + g.o_w3; fa.w4 = ws + g.o_w4;
+  fa.a2 = ws + g.o_a2; fa.a3 = ws + g.o_a3; fa.a4 = ws + g.o_a4; fa.feat = feat;
+  fa.store = g.keep_dgelu ? 2 : 1;
+  return fa;
+}
+// the partial sums lie back to back: part4 and part3 in four slabs per workgroup (the bf16 kernel's count; the fp32
+// kernel fills two of them), then part0
+FusedBwdArgs make_fused_bwd_args(const isd_conv4_plan* p, const Geo& g, const float* x, const float* dfeat, float* ws,
+                                 int64_t T) {
+  FusedBwdArgs fb = {};
+  fill_fused_geometry(fb, p, g, T);
+  fb.x = x; fb.dfeat = dfeat; fb.a2 = ws + g.o_a2; fb.a3 = ws + g.o_a3; fb.a4 = ws + g.o_a4;
+  fb.w3t = ws + g.o_w3t; fb.w4t = ws + g.o_w4t;
+  fb.part4 = ws + g.o_part;
+  fb.part3 = fb.part4 + (int64_t)g.bwd_per_zone * 4 * g.slab1;
+  fb.part0 = fb.part3 + (int64_t)g.bwd_per_zone * 4 * g.slab1;
+  fb.slab1 = g.slab1; fb.slab0 = g.slab0;
+  return fb;
 }
 }  // namespace
 
@@ -3398,56 +3572,29 @@ extern "C" int64_t isd_conv4_workspace_bytes(const isd_conv4_plan* p, int64_t B,
   return g.total * 4;
 }
 
+using ConvKernel = void (*)(ConvArgs);
+static ConvKernel conv5_fwd_instance(int mode, int bf16, int GT, int NT) {
+  static const ConvKernel k[2][2][2][3] = {   // [mode][bf16][GT == 2 ? 0 : 1][NT == 4 ? 0 : NT == 2 ? 1 : 2]
+      {{{conv5_fwd_kernel<0, float, 2, 4>, conv5_fwd_kernel<0, float, 2, 2>, conv5_fwd_kernel<0, float, 2, 1>},
+        {conv5_fwd_kernel<0, float, 1, 4>, conv5_fwd_kernel<0, float, 1, 2>, conv5_fwd_kernel<0, float, 1, 1>}},
+       {{conv5_fwd_kernel<0, bf16_t, 2, 4>, conv5_fwd_kernel<0, bf16_t, 2, 2>, conv5_fwd_kernel<0, bf16_t, 2, 1>},
+        {conv5_fwd_kernel<0, bf16_t, 1, 4>, conv5_fwd_kernel<0, bf16_t, 1, 2>, conv5_fwd_kernel<0, bf16_t, 1, 1>}}},
+      {{{conv5_fwd_kernel<1, float, 2, 4>, conv5_fwd_kernel<1, float, 2, 2>, conv5_fwd_kernel<1, float, 2, 1>},
+        {conv5_fwd_kernel<1, float, 1, 4>, conv5_fwd_kernel<1, float, 1, 2>, conv5_fwd_kernel<1, float, 1, 1>}},
+       {{conv5_fwd_kernel<1, bf16_t, 2, 4>, conv5_fwd_kernel<1, bf16_t, 2, 2>, conv5_fwd_kernel<1, bf16_t, 2, 1>},
+        {conv5_fwd_kernel<1, bf16_t, 1, 4>, conv5_fwd_kernel<1, bf16_t, 1, 2>, conv5_fwd_kernel<1, bf16_t, 1, 1>}}}};
+  return k[mode != 0][bf16 != 0][GT == 2 ? 0 : 1][NT == 4 ? 0 : NT == 2 ? 1 : 2];
+}
+
 static int launch_conv(int mode, int bf16, const ConvArgs& a, int n_zones, hipStream_t st) {
   const int64_t blocks = cdiv(a.items, a.IPW);
   ISD_CHECK_ARG(blocks <= 0x7fffffffLL, "conv4: too many items");
   const int GT = a.F / 16;
-  const size_t lds = sizeof(float) * (4 + (((size_t)a.IPW * a.CK * a.RS + 3) & ~(size_t)3) + (size_t)(a.CK / 4) * kTaps * GT * 64 + 32);
+  const size_t lds = conv5_fwd_lds(a.IPW, a.CK, a.RS, GT);
   ISD_CHECK_ARG(lds <= 150 * 1024, "conv4: LDS tile of %zu bytes exceeds 150 KiB (window too long)", lds);
-  const dim3 grid((unsigned)blocks, n_zones);
   const int tiles = a.IPW * a.TT;                     // column tiles per workgroup -> tiles per wave (1, 2 or 4)
   const int NT = tiles > 8 ? 4 : tiles > 4 ? 2 : 1;
-#define ISD_CONV_LAUNCH_1(M, T, G, N)                                                                \
-  do {                                                                                               \
-    if (lds > 48 * 1024)                                                                             \
-      ISD_HIP_TRY(hipFuncSetAttribute((const void*)conv5_fwd_kernel<M, T, G, N>,                     \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));        \
-    hipLaunchKernelGGL((conv5_fwd_kernel<M, T, G, N>), grid, dim3(256), lds, st, a);                 \
-  } while (0)
-#define ISD_CONV_LAUNCH_N(M, T, G)                                                                   \
-  do {                                                                                               \
-    if (NT == 4) ISD_CONV_LAUNCH_1(M, T, G, 4);                                                      \
-    else if (NT == 2) ISD_CONV_LAUNCH_1(M, T, G, 2);                                                 \
-    else ISD_CONV_LAUNCH_1(M, T, G, 1);                                                              \
-  } while (0)
-#define ISD_CONV_LAUNCH(M, T)                                                                         \
-  do {                                                                                               \
-    if (GT == 2) ISD_CONV_LAUNCH_N(M, T, 2);                                                         \
-    else ISD_CONV_LAUNCH_N(M, T, 1);                                                                 \
-  } while (0)
-  if (mode == 0 && !bf16) ISD_CONV_LAUNCH(0, float);
-  else if (mode == 0) ISD_CONV_LAUNCH(0, bf16_t);
-  else if (!bf16) ISD_CONV_LAUNCH(1, float);
-  else ISD_CONV_LAUNCH(1, bf16_t);
-#undef ISD_CONV_LAUNCH
-#undef ISD_CONV_LAUNCH_N
-#undef ISD_CONV_LAUNCH_1
-  ISD_LAUNCH_CHECK();
-  return ISD_OK;
-}
-
-// the reference-native shape with bf16 activations runs the bf16 fused pair (conv4_fused_*_bf16_kernel)
-static bool fused16_ok(const isd_conv4_plan* p, const Geo& g) {
-  return p->n_layers == 4 && p->F == 32 && p->act_bf16 && p->max_cz <= 16 && g.TT <= 16 && g.TT >= 4;
-}
-static size_t fused16_lds(const isd_conv4_plan* p, const Geo& g, bool bwd) {
-  (void)p;
-  const size_t tile_f = (size_t)fused16_rows(g.TT) * 16;
-  const size_t w16 = (size_t)kTaps * 2 * 64 * 4;
-  // backward: two sets of {GELU'(A4) / G4 / G2, A3, A2} + G3 + the bf16 x tile + two weight fragment sets
-  // forward: t2, t3 (its front doubles as the bf16 x tile), row sums, bias, three weight fragment sets
-  return sizeof(float) * (bwd ? 7 * tile_f + (size_t)(32 * ((g.TT + 1) / 2) + 16) * 8 + 2 * w16 + 16
-                              : 2 * tile_f + 8 * 32 + 32 + 3 * 2 * 64 * 4 + 2 * w16 + 16);
+  return launch_lds(conv5_fwd_instance(mode, bf16, GT, NT), dim3((unsigned)blocks, n_zones), dim3(256), lds, st, a);
 }
 
 static int launch_prep(const isd_conv4_plan* p, const Geo& g, const float* params, float* ws, hipStream_t st,
@@ -3456,13 +3603,11 @@ static int launch_prep(const isd_conv4_plan* p, const Geo& g, const float* param
   const int nbw = (int)cdiv(((int64_t)(p->max_cz + 3) / 4) * 4 * F, 256);
   // K = 32 bf16 fragments of cnn3 / cnn4: the raw-EEG fused pair and (tap16) the feature classifier's bf16 tail
   PrepConvArgs pc{ws + g.o_w3, ws + g.o_w3t, ws + g.o_w4, ws + g.o_w4t, p->conv_zstride, p->n_layers,
-                  (tap16 && F == 32) || (fused16_ok(p, g) && fused16_lds(p, g, true) <= 160 * 1024) ? 1 : 0};
+                  (tap16 && F == 32) || g.prep16 ? 1 : 0};
   const int extra = p->n_layers == 4 ? 8 : 0;
-  hipLaunchKernelGGL(prep_fused_kernel, dim3(nbw + F + extra, p->Z), dim3(256), 0, st, params, p->d_zones,
-                     ws + g.o_eff, ws + g.o_beff, F, nbw, p->act_bf16, pc,
-                     tap16 ? reinterpret_cast<uint4*>(ws + g.o_eff16) : (uint4*)nullptr);
-  ISD_LAUNCH_CHECK();
-  return ISD_OK;
+  return launch_lds(prep_fused_kernel, dim3(nbw + F + extra, p->Z), dim3(256), 0, st, params, p->d_zones, ws + g.o_eff,
+                    ws + g.o_beff, F, nbw, p->act_bf16, pc,
+                    tap16 ? reinterpret_cast<uint4*>(ws + g.o_eff16) : (uint4*)nullptr);
 }
 
 // BASELINE config 3 on the bf16 matrix cores: the classifier step (isd_featcnn_step) qualifies when the first layer is
@@ -3477,87 +3622,69 @@ static bool bf16_mfma_ok(const isd_conv4_plan* p, const Geo& g, const void* x) {
 static int first_layer_forward(const isd_conv4_plan* p, const Geo& g, const float* x, int64_t T, float* ws,
                                hipStream_t st, ConvArgs& a, bool tap16 = false, bool in16 = false) {
   const int F = p->F;
-  int rc;
-  a = ConvArgs{};
-  a.zones = p->d_zones; a.chan_idx = p->d_idx; a.items = g.items; a.Z = p->Z; a.F = F;
-  a.TT = g.TT; a.IPW = g.IPW; a.Tout = g.T1; a.CK = g.CK;
-  a.Ctot = p->Ctot; a.Tx = (int)T; a.N = g.N; a.S = p->S;
-  // cnn1 o cnn2
+  a = make_conv_args(p, g, T);
   a.in = x; a.out = ws + g.o_a2; a.wfrag = ws + g.o_eff; a.bias = ws + g.o_beff; a.Tin = p->W; a.pad = 0; a.RS = g.RS_a;
   a.lin = g.lin0;
+  ConvArgs d = a;                                      // the LDS-DMA kernels below: whole rows, their own items per workgroup
+  d.RS = p->W;
   if (tap16) {
     // bf16 matrix cores: 4 items per wave (NT), 16 per workgroup; fewer when the batch is small
-    int NT = 4;
     int ipw = 16;
     const int64_t per_cu = cdiv(g.items * p->Z, 512);
     if (per_cu < ipw) { ipw = per_cu < 4 ? 4 : (int)per_cu; }
-    NT = (ipw + 3) / 4;
+    int NT = (ipw + 3) / 4;
     if (NT == 3) { NT = 4; }
     ipw = NT * 4;
-    const size_t buf = (size_t)(((ipw * kCK * p->W + 3) & ~3) + (kCK / 4) * 2 * 64 * 4 + 32);
-    const size_t lds = sizeof(float) * (4 + 2 * buf);
-    a.IPW = ipw; a.RS = p->W;
-    const dim3 grid((unsigned)cdiv(g.items, ipw), p->Z);
-    const uint4* w16 = reinterpret_cast<const uint4*>(ws + g.o_eff16);
-#define ISD_BF_LAUNCH(N, I16)                                                                                   \
-  do {                                                                                                          \
-    ISD_HIP_TRY(hipFuncSetAttribute((const void*)conv5_fwd_bf16_kernel<2, N, I16>,                              \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                     \
-    hipLaunchKernelGGL((conv5_fwd_bf16_kernel<2, N, I16>), grid, dim3(256), lds, st, a, w16);                   \
-  } while (0)
-    if (in16) { if (NT == 4) ISD_BF_LAUNCH(4, true); else if (NT == 2) ISD_BF_LAUNCH(2, true); else ISD_BF_LAUNCH(1, true); }
-    else { if (NT == 4) ISD_BF_LAUNCH(4, false); else if (NT == 2) ISD_BF_LAUNCH(2, false); else ISD_BF_LAUNCH(1, false); }
-#undef ISD_BF_LAUNCH
-    ISD_LAUNCH_CHECK();
-    a.IPW = g.IPW;
-    return ISD_OK;
+    d.IPW = ipw;
+    static void (*const k[2][3])(ConvArgs, const uint4*) = {   // [in16 ? 0 : 1][NT == 4 ? 0 : NT == 2 ? 1 : 2]
+        {conv5_fwd_bf16_kernel<2, 4, true>, conv5_fwd_bf16_kernel<2, 2, true>, conv5_fwd_bf16_kernel<2, 1, true>},
+        {conv5_fwd_bf16_kernel<2, 4, false>, conv5_fwd_bf16_kernel<2, 2, false>, conv5_fwd_bf16_kernel<2, 1, false>}};
+    return launch_lds(k[in16 ? 0 : 1][NT == 4 ? 0 : NT == 2 ? 1 : 2], dim3((unsigned)cdiv(g.items, ipw), p->Z), dim3(256),
+                      conv5_fwd_bf16_lds(ipw, p->W), st, d, reinterpret_cast<const uint4*>(ws + g.o_eff16));
   }
-  {
-    // wide inputs (>= 2 channel chunks): double-buffered LDS-DMA variant.  Two workgroups of 8 column tiles per CU
-    // when there is enough work (the barrier / DMA wait of one runs under the MFMAs of the other), else one of 16.
-    const int GT = F / 16;
-    int NT = 2;
-    const bool pack = g.TT == 1;                       // one-tile rows: the items' output steps share column tiles
-    int ipw = pack ? (4 * NT * 16) / g.T1 : (4 * NT) / g.TT;
-    // (two workgroups per CU only when there are more workgroups than CUs.  At 4096 items of 13 steps the packed tiles
-    // are 3328 instead of 4096, but both are four per SIMD: the forward pass gains only beyond that batch)
-    if (ipw < 1 || cdiv(g.items * p->Z, ipw) <= 256) {
-      NT = 4;
-      ipw = pack ? (16 * 16) / g.T1 : 16 / g.TT;
-      const int64_t per_cu = cdiv(g.items * p->Z, 256);
-      if (ipw > per_cu) ipw = (int)per_cu;
-    }
-    const size_t buf = (size_t)(((ipw * kCK * p->W + 3) & ~3) + (kCK / 4) * kTaps * GT * 64 + 32);
-    const size_t lds = sizeof(float) * (4 + 2 * buf);
-    if (g.lin0 && p->dma_ok && !p->act_bf16 && p->max_cz > kCK && g.TT <= 4 * NT && ipw >= 1 && lds <= 150 * 1024 &&
-        ((uintptr_t)x & 15) == 0) {
-      a.IPW = ipw; a.RS = p->W;
-      const dim3 grid((unsigned)cdiv(g.items, ipw), p->Z);
-#define ISD_GLDS_LAUNCH(G, N)                                                                                  \
-  do {                                                                                                        \
-    ISD_HIP_TRY(hipFuncSetAttribute((const void*)conv5_fwd_glds_kernel<G, N>,                                 \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                   \
-    hipLaunchKernelGGL((conv5_fwd_glds_kernel<G, N>), grid, dim3(256), lds, st, a);                           \
-  } while (0)
-      if (GT == 2 && NT == 2) ISD_GLDS_LAUNCH(2, 2);
-      else if (GT == 2) ISD_GLDS_LAUNCH(2, 4);
-      else if (NT == 2) ISD_GLDS_LAUNCH(1, 2);
-      else ISD_GLDS_LAUNCH(1, 4);
-#undef ISD_GLDS_LAUNCH
-      ISD_LAUNCH_CHECK();
-      a.IPW = g.IPW;
-      rc = ISD_OK;
-    } else {
-      rc = launch_conv(0, p->act_bf16, a, p->Z, st);
-    }
+  // wide inputs (>= 2 channel chunks): double-buffered LDS-DMA variant.  Two workgroups of 8 column tiles per CU
+  // when there is enough work (the barrier / DMA wait of one runs under the MFMAs of the other), else one of 16.
+  const int GT = F / 16;
+  int NT = 2;
+  const bool pack = g.TT == 1;                       // one-tile rows: the items' output steps share column tiles
+  int ipw = pack ? (4 * NT * 16) / g.T1 : (4 * NT) / g.TT;
+  // (two workgroups per CU only when there are more workgroups than CUs.  At 4096 items of 13 steps the packed tiles
+  // are 3328 instead of 4096, but both are four per SIMD: the forward pass gains only beyond that batch)
+  if (ipw < 1 || cdiv(g.items * p->Z, ipw) <= 256) {
+    NT = 4;
+    ipw = pack ? (16 * 16) / g.T1 : 16 / g.TT;
+    const int64_t per_cu = cdiv(g.items * p->Z, 256);
+    if (ipw > per_cu) ipw = (int)per_cu;
   }
-  return rc;
+  const size_t lds = conv5_fwd_glds_lds(ipw, p->W, GT);
+  if (g.lin0 && p->dma_ok && !p->act_bf16 && p->max_cz > kCK && g.TT <= 4 * NT && ipw >= 1 && lds <= 150 * 1024 &&
+      ((uintptr_t)x & 15) == 0) {
+    d.IPW = ipw;
+    void (*k)(ConvArgs);
+    if (GT == 2 && NT == 2) k = conv5_fwd_glds_kernel<2, 2>;
+    else if (GT == 2) k = conv5_fwd_glds_kernel<2, 4>;
+    else if (NT == 2) k = conv5_fwd_glds_kernel<1, 2>;
+    else k = conv5_fwd_glds_kernel<1, 4>;
+    return launch_lds(k, dim3((unsigned)cdiv(g.items, ipw), p->Z), dim3(256), lds, st, d);
+  }
+  return launch_conv(0, p->act_bf16, a, p->Z, st);
 }
 
-// LDS bytes of conv4_fused_bwd_kernel<8>; the forward keeps GELU'(A4) instead of A4 exactly when this fits
-static size_t fused_bwd_lds(const isd_conv4_plan* p, const Geo& g) {
-  const int tile = ((p->F * g.T1 + 3) & ~3) + 4;
-  return sizeof(float) * (size_t)(((4 + 16 * p->W + 3) & ~3) + 4 + 3 * tile + 2 * 8 * kTaps * 2 * 64 + 32 + 16);
+// the whole stack in one persistent kernel (Route::kFusedF32 / kFusedBf16)
+static int fused_forward(const isd_conv4_plan* p, const Geo& g, const float* x, float* feat, float* ws, int64_t T,
+                         hipStream_t st) {
+  const FusedFwdArgs fa = make_fused_fwd_args(p, g, x, feat, ws, T);
+  void (*k)(FusedFwdArgs) = conv4_fused_fwd_bf16_kernel<kFusedNW>;
+  if (g.route == Route::kFusedF32) k = conv4_fused_fwd_kernel<kFusedNW>;
+  return launch_lds(k, dim3(g.fwd_per_zone, p->Z), dim3(kFusedNW * 64), g.fwd_lds, st, fa);
+}
+
+// GELU + mean over time of the last activation -> feat
+static int launch_gelu_mean_fwd(const isd_conv4_plan* p, const Geo& g, const float* last, float* feat, hipStream_t st) {
+  const int64_t rows = g.items * p->Z * p->F;
+  void (*k)(const void*, float*, int64_t, int) = gelu_mean_fwd_kernel<bf16_t>;
+  if (!p->act_bf16) k = gelu_mean_fwd_kernel<float>;
+  return launch_lds(k, dim3((unsigned)cdiv(rows * 16, 256)), dim3(256), 0, st, last, feat, rows, g.T1);
 }
 
 extern "C" int isd_conv4_forward(const isd_conv4_plan* p, const float* x, const float* params, float* feat,
@@ -3571,50 +3698,9 @@ extern "C" int isd_conv4_forward(const isd_conv4_plan* p, const float* x, const 
   ISD_CHECK_ARG(x && params && feat && workspace, "isd_conv4_forward: null argument");
   hipStream_t st = (hipStream_t)stream;
   float* ws = (float*)workspace;
-  const int F = p->F;
   rc = launch_prep(p, g, params, ws, st);
   if (rc) return rc;
-  if (fused16_ok(p, g) && fused16_lds(p, g, true) <= 160 * 1024) {
-    // reference-native shape, bf16 activations: the fused kernel on the bf16 matrix cores
-    FusedFwdArgs fa = {};
-    fa.x = x; fa.weff = ws + g.o_eff; fa.beff = ws + g.o_beff; fa.w3 = ws + g.o_w3; fa.w4 = ws + g.o_w4;
-    fa.a2 = ws + g.o_a2; fa.a3 = ws + g.o_a3; fa.a4 = ws + g.o_a4; fa.feat = feat;
-    fa.zones = p->d_zones; fa.chan_idx = p->d_idx; fa.wz_stride = p->conv_zstride; fa.items = g.items;
-    fa.Z = p->Z; fa.W = p->W; fa.T1 = g.T1; fa.TT = g.TT; fa.store = 2;
-    fa.Ctot = p->Ctot; fa.Tx = (int)T; fa.N = g.N; fa.S = p->S;
-    const size_t lds = fused16_lds(p, g, false);
-    int per_zone = (lds <= 80 * 1024 ? 512 : 256) / p->Z;     // two workgroups per CU when the tiles allow
-    if (per_zone < 1) per_zone = 1;
-    if (per_zone > g.items) per_zone = (int)g.items;
-    ISD_HIP_TRY(hipFuncSetAttribute((const void*)conv4_fused_fwd_bf16_kernel<8>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((conv4_fused_fwd_bf16_kernel<8>), dim3(per_zone, p->Z), dim3(8 * 64), lds, st, fa);
-    ISD_LAUNCH_CHECK();
-    return ISD_OK;
-  }
-  if (p->n_layers == 4 && F == 32 && !p->act_bf16 && p->max_cz <= 16 && g.TT <= 16 && (F * g.T1) % 4 == 0 &&
-      g.TT >= 4) {
-    // reference-native shape: one persistent fused kernel (register-resident weights, activations through LDS)
-    FusedFwdArgs fa = {};
-    fa.x = x; fa.weff = ws + g.o_eff; fa.beff = ws + g.o_beff; fa.w3 = ws + g.o_w3; fa.w4 = ws + g.o_w4;
-    fa.a2 = ws + g.o_a2; fa.a3 = ws + g.o_a3; fa.a4 = ws + g.o_a4; fa.feat = feat;
-    fa.zones = p->d_zones; fa.chan_idx = p->d_idx; fa.wz_stride = p->conv_zstride; fa.items = g.items;
-    fa.Z = p->Z; fa.W = p->W; fa.T1 = g.T1; fa.TT = g.TT; fa.store = fused_bwd_lds(p, g) <= 160 * 1024 ? 2 : 1;
-    fa.Ctot = p->Ctot; fa.Tx = (int)T; fa.N = g.N; fa.S = p->S;
-    constexpr int NW = 8;   // measured after the prefetch restructure (B=4096, T=512): 8 waves 25.6 ms/step, 16 waves 25.6, 4 waves 28.3
-    const size_t lds = sizeof(float) * (size_t)(4 + ((16 * p->W + 3) & ~3) + 2 * ((F * g.T1 + 3) & ~3) + NW * F +
-                                                 (4 + 8 + 8) * kTaps * 2 * 64 + 64);
-    if (lds <= 150 * 1024) {
-      int per_zone = 256 / p->Z;
-      if (per_zone < 1) per_zone = 1;
-      if (per_zone > g.items) per_zone = (int)g.items;
-      ISD_HIP_TRY(hipFuncSetAttribute((const void*)conv4_fused_fwd_kernel<NW>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL((conv4_fused_fwd_kernel<NW>), dim3(per_zone, p->Z), dim3(NW * 64), lds, st, fa);
-      ISD_LAUNCH_CHECK();
-      return ISD_OK;
-    }
-  }
+  if (g.route != Route::kLayerwise) return fused_forward(p, g, x, feat, ws, T, st);
   ConvArgs a = {};
   rc = first_layer_forward(p, g, x, T, ws, st, a);
   if (rc) return rc;
@@ -3629,33 +3715,16 @@ extern "C" int isd_conv4_forward(const isd_conv4_plan* p, const float* x, const 
     if (rc) return rc;
     last = ws + g.o_a4;
   }
-  const int64_t rows = g.items * p->Z * F;
-  if (p->act_bf16)
-    hipLaunchKernelGGL((gelu_mean_fwd_kernel<bf16_t>), dim3((unsigned)cdiv(rows * 16, 256)), dim3(256), 0, st, last,
-                       feat, rows, g.T1);
-  else
-    hipLaunchKernelGGL((gelu_mean_fwd_kernel<float>), dim3((unsigned)cdiv(rows * 16, 256)), dim3(256), 0, st, last, feat,
-                       rows, g.T1);
-  ISD_LAUNCH_CHECK();
-  return ISD_OK;
+  return launch_gelu_mean_fwd(p, g, last, feat, st);
 }
 
-template <int MODE, typename AT, bool BOTH>
-static int launch_wgrad_b(const WgradArgs& a, dim3 grid, size_t lds, hipStream_t st) {
-  if (lds > 48 * 1024)
-    ISD_HIP_TRY(hipFuncSetAttribute((const void*)conv5_wgrad_kernel<MODE, AT, BOTH>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL((conv5_wgrad_kernel<MODE, AT, BOTH>), grid, dim3(256), lds, st, a);
-  ISD_LAUNCH_CHECK();
-  return ISD_OK;
-}
 template <int MODE, typename AT>
-static int launch_wgrad_t(const WgradArgs& a, dim3 grid, size_t lds, hipStream_t st) {
-  return a.F == 32 ? launch_wgrad_b<MODE, AT, true>(a, grid, lds, st) : launch_wgrad_b<MODE, AT, false>(a, grid, lds, st);
+static void (*conv5_wgrad_instance(int F))(WgradArgs) {
+  return F == 32 ? conv5_wgrad_kernel<MODE, AT, true> : conv5_wgrad_kernel<MODE, AT, false>;
 }
 
 static int launch_wgrad(int mode, int bf16, WgradArgs a, int n_zones, int cin_max, hipStream_t st) {   // `a` by value: the stage geometry chosen here must not leak into the caller's next launch
-  int64_t per_item = (int64_t)a.F * a.RSo + (int64_t)a.CW * a.RSi;
+  int64_t per_item = conv5_wgrad_item_floats(a.F, a.RSo, a.CW, a.RSi);
   int ips = (int)((96 * 1024 / 4 - 4) / per_item);
   if (ips < 1) ips = (int)((150 * 1024 / 4 - 4) / per_item);   // long windows: one item in the large LDS allocation
   a.seg_len = 0;
@@ -3667,7 +3736,7 @@ static int launch_wgrad(int mode, int bf16, WgradArgs a, int n_zones, int cin_ma
     a.RSo = seg;
     a.RSi = seg + kTaps - 1;
     a.lin = 0;
-    per_item = (int64_t)a.F * a.RSo + (int64_t)a.CW * a.RSi;
+    per_item = conv5_wgrad_item_floats(a.F, a.RSo, a.CW, a.RSi);
     ips = 1;
   }
   if (ips > 1 && per_item * 4 > 32 * 1024) ips = 1;           // big items: one per stage, 2-3 workgroups per CU
@@ -3678,12 +3747,12 @@ static int launch_wgrad(int mode, int bf16, WgradArgs a, int n_zones, int cin_ma
   a.IPS = ips;
   // (two LDS stages filled by LDS-DMA were measured here: 28.9 vs 28.4 ms/step on FAST B=4096 -- one stage and two
   // co-resident workgroups per CU hide the copy better than one workgroup with two stages)
-  const size_t lds = sizeof(float) * ((size_t)ips * per_item + 4);
   const int64_t wgs = cdiv(a.items, a.items_per_wg);
   const int zgroups = (cin_max + a.CW - 1) / a.CW;
-  const dim3 grid((unsigned)wgs, n_zones, zgroups);
-  if (mode == 0) return bf16 ? launch_wgrad_t<0, bf16_t>(a, grid, lds, st) : launch_wgrad_t<0, float>(a, grid, lds, st);
-  return bf16 ? launch_wgrad_t<1, bf16_t>(a, grid, lds, st) : launch_wgrad_t<1, float>(a, grid, lds, st);
+  void (*k)(WgradArgs);
+  if (mode == 0) k = bf16 ? conv5_wgrad_instance<0, bf16_t>(a.F) : conv5_wgrad_instance<0, float>(a.F);
+  else k = bf16 ? conv5_wgrad_instance<1, bf16_t>(a.F) : conv5_wgrad_instance<1, float>(a.F);
+  return launch_lds(k, dim3((unsigned)wgs, n_zones, zgroups), dim3(256), conv5_wgrad_lds(ips, per_item), st, a);
 }
 
 // cnn3 / cnn4 gradient in natural [F][F][5] layout -> flat gradient block
@@ -3697,18 +3766,13 @@ __global__ void scatter_conv_grad_kernel(const float* __restrict__ wg, const isd
 }
 
 // the chain dWeff -> (dW1, db1, dW2): 1024-thread workgroups for wide inputs, 256 for the zone shapes
-static inline void launch_fused_bwd(const isd_conv4_plan* p, const float* params, const float* dweff, float* dparams,
-                                    hipStream_t st) {
+static int launch_dweff_chain(const isd_conv4_plan* p, const float* params, const float* dweff, float* dparams,
+                              hipStream_t st) {
   const int F = p->F;
-  if (p->max_cz >= 64) {
-    const int nb2 = (int)cdiv((int64_t)F * F * p->max_cz, 1024);
-    hipLaunchKernelGGL(fused_bwd_kernel<1024>, dim3(nb2 + F * kTaps + F, p->Z), dim3(1024), 0, st, params, p->d_zones,
-                       dweff, dparams, F, nb2);
-  } else {
-    const int nb2 = (int)cdiv((int64_t)F * F * p->max_cz, 256);
-    hipLaunchKernelGGL(fused_bwd_kernel<256>, dim3(nb2 + F * kTaps + F, p->Z), dim3(256), 0, st, params, p->d_zones,
-                       dweff, dparams, F, nb2);
-  }
+  const int threads = p->max_cz >= 64 ? 1024 : 256;
+  const int nb2 = (int)cdiv((int64_t)F * F * p->max_cz, threads);
+  return launch_lds(threads == 1024 ? fused_bwd_kernel<1024> : fused_bwd_kernel<256>, dim3(nb2 + F * kTaps + F, p->Z),
+                    dim3(threads), 0, st, params, p->d_zones, dweff, dparams, F, nb2);
 }
 
 // cnn1 o cnn2 backward: dWeff (+ dbeff in the ones channel) from g2 = dL/dA2, then the chain to W1, b1, W2
@@ -3717,59 +3781,42 @@ static int first_layer_backward(const isd_conv4_plan* p, const Geo& g, const flo
                                 bool in16 = false) {
   const int F = p->F;
   int rc;
-  WgradArgs w = {};
-  w.zones = p->d_zones; w.chan_idx = p->d_idx; w.items = g.items;
-  w.Z = p->Z; w.F = F; w.Tout = g.T1; w.part = ws + g.o_part;
-  w.Ctot = p->Ctot; w.Tx = (int)T; w.N = g.N; w.S = p->S;
+  WgradArgs w = make_wgrad_args(p, g, T, ws);
   w.dout = g2; w.in = x; w.Tin = p->W; w.pad = 0;
   w.RSo = g.T1; w.lin = g.lin0;
   w.RSi = g.lin0 ? p->W : (p->W | 1);
   w.slab_size = g.slab0; w.wz_stride = 0; w.items_per_wg = g.ipw0; w.CW = g.cw0;
   int n_slabs0 = g.ns0;
-  {
-    // wide inputs: LDS-DMA double-buffered variant, ~3 workgroups per CU
-    const int zg = (p->max_cz + 63) / 64;
-    int64_t r_target = (256 * 3) / ((int64_t)zg * p->Z);
-    if (r_target < 1) r_target = 1;
-    if (r_target > g.ns0) r_target = g.ns0;
-    const int ipw = (int)cdiv(g.items, r_target);
-    const int R = (int)cdiv(g.items, ipw);
-    const int item_len = (F * g.T1 + 64 * p->W + 3) & ~3;
-    int ips = 4;
-    while (ips > 1 && (size_t)(2 * (ips * item_len + 32) + 8) * 4 > 48 * 1024) --ips;
-    const size_t lds = sizeof(float) * (size_t)(2 * (ips * item_len + 32) + 8);
-    if (tap16) {
-      // bf16 matrix cores: gradient images of 16 x 32 bf16 (1 KiB) + 64 input rows per item, item pairs per K step
-      const int item16 = (16 * F / 2 + 64 * p->W + 3) & ~3;
-      const int ips16 = 4;
-      const size_t lds16 = sizeof(float) * (size_t)(2 * (ips16 * item16 + 32) + 8);
-      w.items_per_wg = ipw; w.IPS = ips16;
-      const dim3 grid((unsigned)R, p->Z, zg);
-      if (in16) hipLaunchKernelGGL((conv5_wgrad_wide_bf16_kernel<2, true>), grid, dim3(256), lds16, st, w);
-      else hipLaunchKernelGGL((conv5_wgrad_wide_bf16_kernel<2, false>), grid, dim3(256), lds16, st, w);
-      ISD_LAUNCH_CHECK();
-      n_slabs0 = R;
-      rc = ISD_OK;
-    } else if (g.lin0 && p->dma_ok && !p->act_bf16 && p->max_cz >= 64 && (F * g.T1) % 4 == 0 && lds <= 64 * 1024 &&
-        ((uintptr_t)x & 15) == 0 && ((uintptr_t)g2 & 15) == 0) {
-      w.items_per_wg = ipw; w.IPS = ips;
-      const dim3 grid((unsigned)R, p->Z, zg);
-      if (F == 32) hipLaunchKernelGGL(conv5_wgrad_wide_kernel<2>, grid, dim3(256), lds, st, w);
-      else hipLaunchKernelGGL(conv5_wgrad_wide_kernel<1>, grid, dim3(256), lds, st, w);
-      ISD_LAUNCH_CHECK();
-      n_slabs0 = R;
-      rc = ISD_OK;
-    } else {
-      rc = launch_wgrad(0, p->act_bf16, w, p->Z, p->max_cz + 1, st);
-    }
+  // wide inputs: LDS-DMA double-buffered variants, ~3 workgroups per CU
+  const int zg = (p->max_cz + 63) / 64;
+  int64_t r_target = (256 * 3) / ((int64_t)zg * p->Z);
+  if (r_target < 1) r_target = 1;
+  if (r_target > g.ns0) r_target = g.ns0;
+  const int ipw = (int)cdiv(g.items, r_target);
+  const int R = (int)cdiv(g.items, ipw);
+  const dim3 grid((unsigned)R, p->Z, zg);
+  const int item_len = conv5_wgrad_wide_item_floats(F, g.T1, p->W);
+  int ips = 4;
+  while (ips > 1 && conv5_wgrad_wide_lds(ips, item_len) > 48 * 1024) --ips;
+  const size_t lds = conv5_wgrad_wide_lds(ips, item_len);
+  if (tap16) {
+    // bf16 matrix cores: item pairs per K step
+    const int ips16 = 4;
+    w.items_per_wg = ipw; w.IPS = ips16;
+    rc = launch_lds(in16 ? conv5_wgrad_wide_bf16_kernel<2, true> : conv5_wgrad_wide_bf16_kernel<2, false>, grid, dim3(256),
+                    conv5_wgrad_wide_lds(ips16, conv5_wgrad_wide_bf16_item_floats(F, p->W)), st, w);
+    n_slabs0 = R;
+  } else if (g.lin0 && p->dma_ok && !p->act_bf16 && p->max_cz >= 64 && (F * g.T1) % 4 == 0 && lds <= 64 * 1024 &&
+             ((uintptr_t)x & 15) == 0 && ((uintptr_t)g2 & 15) == 0) {
+    w.items_per_wg = ipw; w.IPS = ips;
+    rc = launch_lds(F == 32 ? conv5_wgrad_wide_kernel<2> : conv5_wgrad_wide_kernel<1>, grid, dim3(256), lds, st, w);
+    n_slabs0 = R;
+  } else {
+    rc = launch_wgrad(0, p->act_bf16, w, p->Z, p->max_cz + 1, st);
   }
   if (rc) return rc;
   launch_reduce_slabs(ws + g.o_part, ws + g.o_wg, g.slab0, n_slabs0, st);
-  {
-    launch_fused_bwd(p, params, ws + g.o_wg, dparams, st);
-  }
-  ISD_LAUNCH_CHECK();
-  return ISD_OK;
+  return launch_dweff_chain(p, params, ws + g.o_wg, dparams, st);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -3828,30 +3875,24 @@ static int featcnn_step_impl(const isd_conv4_plan* p, const float* x, const floa
   t.items = g.items; t.T1 = g.T1; t.n_cls = n_cls; t.train = train ? 1 : 0; t.grad_scale = grad_scale;
   const int n34 = 2 * F * F * kTaps, nfc = n_cls * (F + 1);
   t.slab = n34 + nfc + 1;
+  auto tail_blocks = [&](int items_per_wg) {                      // persistent workgroups, one slab of partial sums each
+    const int64_t b = cdiv(g.items, items_per_wg);
+    return b > 256 ? 256 : b < 1 ? 1 : (int)b;
+  };
   constexpr int TNW = 4;                                          // waves per workgroup (measured: 4 -> 107 us; 8 -> 135 us, 256 VGPRs + 133 spills)
-  int blocks = (int)cdiv(g.items, TNW * kTailNI * 2);             // two rounds of NI items per wave
-  if (blocks > 256) blocks = 256;
-  if (blocks < 1) blocks = 1;
-  const int tile = (F * g.T1 + 3) & ~3;
-  size_t lds = sizeof(float) * (size_t)(4 * 8 * kTaps * 2 * 64 + kTailMaxCls * (F + 1) + TNW * kTailNI * (4 * tile + 64) + 16);
-  if (lds < sizeof(float) * 2 * kTailCombCopy) lds = sizeof(float) * 2 * kTailCombCopy;           // two accumulator copies (epilogue)
+  constexpr int BNW = 8;                                          // bf16 matrix cores: eight waves, an item per wave and round
+  int blocks = tail_blocks(TNW * kTailNI * 2);                    // two rounds of NI items per wave
+  size_t lds = featcnn_tail_lds(TNW, F, g.T1);
   ISD_CHECK_ARG(lds <= 160 * 1024 && (int64_t)blocks * t.slab <= g.total - g.o_part, "isd_featcnn_step: workspace");
   if (tap16) {
-    // bf16 matrix cores: eight waves per workgroup, an item per wave and round
-    constexpr int BNW = 8;
-    blocks = (int)cdiv(g.items, BNW * 2);
-    if (blocks > 256) blocks = 256;
-    if (blocks < 1) blocks = 1;
-    size_t lds16 = (size_t)4 * kTaps * 2 * 64 * 16 + sizeof(float) * kTailMaxCls * (F + 1) + (size_t)BNW * (4 * 40 * 64 + 256) + 64;
-    if (lds16 < sizeof(float) * 3 * kTailCombCopy) lds16 = sizeof(float) * 3 * kTailCombCopy;     // three accumulator copies (epilogue)
-    ISD_CHECK_ARG(lds16 <= 160 * 1024 && (int64_t)blocks * t.slab <= g.total - g.o_part, "isd_featcnn_step: workspace");
-    ISD_HIP_TRY(hipFuncSetAttribute((const void*)featcnn_tail_bf16_kernel<BNW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16));
-    hipLaunchKernelGGL((featcnn_tail_bf16_kernel<BNW>), dim3(blocks), dim3(BNW * 64), lds16, st, t);
+    blocks = tail_blocks(BNW * 2);
+    lds = featcnn_tail_bf16_lds(BNW, F);
+    ISD_CHECK_ARG(lds <= 160 * 1024 && (int64_t)blocks * t.slab <= g.total - g.o_part, "isd_featcnn_step: workspace");
+    rc = launch_lds(featcnn_tail_bf16_kernel<BNW>, dim3(blocks), dim3(BNW * 64), lds, st, t);
   } else {
-    ISD_HIP_TRY(hipFuncSetAttribute((const void*)featcnn_tail_kernel<TNW, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((featcnn_tail_kernel<TNW, false>), dim3(blocks), dim3(TNW * 64), lds, st, t);
+    rc = launch_lds(featcnn_tail_kernel<TNW, false>, dim3(blocks), dim3(TNW * 64), lds, st, t);
   }
-  ISD_LAUNCH_CHECK();
+  if (rc) return rc;
   if (!labels) return ISD_OK;
   if (train) {
     // the slab sums go straight to their places: cnn3 / cnn4 gradients (back to back in the flat block), the FC
@@ -3885,6 +3926,37 @@ extern "C" int isd_featcnn_step_bf16(const isd_conv4_plan* p, const uint16_t* x,
                            logits, pred, loss, workspace, B, T, n_cls, grad_scale, stream, true);
 }
 
+// One fused kernel for the whole backward of the stack, then the slab sums and the chain to W1, b1, W2.  Per workgroup
+// the kernel leaves `slabs34` slabs for cnn3 / cnn4 each and `slabs0` for Weff.
+static int launch_fused_backward(void (*kernel)(FusedBwdArgs), int slabs34, int slabs0, const isd_conv4_plan* p,
+                                 const Geo& g, const FusedBwdArgs& fb, const float* params, float* dparams, float* ws,
+                                 hipStream_t st) {
+  int rc = launch_lds(kernel, dim3(g.bwd_per_zone, p->Z), dim3(kFusedNW * 64), g.bwd_lds, st, fb);
+  if (rc) return rc;
+  rc = launch_reduce_fused_bwd(fb.part4, fb.part3, fb.part0, g.slab1, g.bwd_per_zone * slabs34, g.slab0,
+                               g.bwd_per_zone * slabs0, dparams, ws + g.o_wg, p->d_zones, p->F, st);
+  if (rc) return rc;
+  return launch_dweff_chain(p, params, ws + g.o_wg, dparams, st);
+}
+
+// the fp32 kernel leaves two slabs per workgroup for cnn3 / cnn4 and four for Weff, the bf16 kernel four and one per wave
+static int fused_backward(const isd_conv4_plan* p, const Geo& g, const float* x, const float* params, const float* dfeat,
+                          float* dparams, float* ws, int64_t T, hipStream_t st) {
+  const FusedBwdArgs fb = make_fused_bwd_args(p, g, x, dfeat, ws, T);
+  if (g.route == Route::kFusedBf16)
+    return launch_fused_backward(conv4_fused_bwd_bf16_kernel<kFusedNW>, 4, kFusedNW, p, g, fb, params, dparams, ws, st);
+  return launch_fused_backward(conv4_fused_bwd_kernel<kFusedNW>, 2, 4, p, g, fb, params, dparams, ws, st);
+}
+
+// dfeat -> gradient of the activation that fed GELU + mean, in place; `pre`: the buffer already holds GELU'(A)
+static int launch_gelu_mean_bwd(const isd_conv4_plan* p, const Geo& g, float* top, const float* dfeat, bool pre,
+                                hipStream_t st) {
+  const int64_t rows = g.items * p->Z * p->F;
+  void (*k)(void*, const float*, int64_t, int) = gelu_mean_bwd_kernel<bf16_t>;
+  if (!p->act_bf16) k = pre ? gelu_mean_bwd_kernel<float, true> : gelu_mean_bwd_kernel<float>;
+  return launch_lds(k, dim3((unsigned)cdiv(rows * 16, 256)), dim3(256), 0, st, top, dfeat, rows, g.T1);
+}
+
 static int conv4_backward_impl(const isd_conv4_plan* p, const float* x, const float* params, const float* dfeat,
                                float* dparams, float* dx, void* workspace, int64_t B, int64_t T, void* stream) {
   ISD_CHECK_ARG(p, "isd_conv4_backward: null plan");
@@ -3902,93 +3974,15 @@ static int conv4_backward_impl(const isd_conv4_plan* p, const float* x, const fl
   ISD_CHECK_ARG(!dx || !p->act_bf16, "isd_conv4_backward_x: fp32 activations only");
   float* ws = (float*)workspace;
   const int F = p->F;
-  const int64_t rows = g.items * p->Z * F;
-  bool kept_dgelu = false;                                 // the forward of this step ran fused and kept GELU'(A4)
-  if (fused16_ok(p, g) && fused16_lds(p, g, true) <= 160 * 1024) {
-    ISD_CHECK_ARG(!dx, "isd_conv4_backward_x: fp32 activations only");
-    constexpr int NW = 8;
-    const size_t lds = fused16_lds(p, g, true);
-    int per_zone = 256 / p->Z;
-    if (per_zone < 1) per_zone = 1;
-    if (per_zone > g.items) per_zone = (int)g.items;
-    FusedBwdArgs fb = {};
-    fb.x = x; fb.dfeat = dfeat; fb.a2 = ws + g.o_a2; fb.a3 = ws + g.o_a3; fb.a4 = ws + g.o_a4;
-    fb.w3t = ws + g.o_w3t; fb.w4t = ws + g.o_w4t;
-    fb.part4 = ws + g.o_part;
-    fb.part3 = fb.part4 + (int64_t)per_zone * 4 * g.slab1;
-    fb.part0 = fb.part3 + (int64_t)per_zone * 4 * g.slab1;
-    fb.zones = p->d_zones; fb.chan_idx = p->d_idx; fb.wz_stride = p->conv_zstride; fb.items = g.items;
-    fb.slab1 = g.slab1; fb.slab0 = g.slab0;
-    fb.Z = p->Z; fb.W = p->W; fb.T1 = g.T1; fb.TT = g.TT;
-    fb.Ctot = p->Ctot; fb.Tx = (int)T; fb.N = g.N; fb.S = p->S;
-    ISD_HIP_TRY(hipFuncSetAttribute((const void*)conv4_fused_bwd_bf16_kernel<NW>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((conv4_fused_bwd_bf16_kernel<NW>), dim3(per_zone, p->Z), dim3(NW * 64), lds, st, fb);
-    ISD_LAUNCH_CHECK();
-    rc = launch_reduce_fused_bwd(fb.part4, fb.part3, fb.part0, g.slab1, per_zone * 4, g.slab0, per_zone * NW, dparams,
-                                 ws + g.o_wg, p->d_zones, F, st);
-    if (rc) return rc;
-    launch_fused_bwd(p, params, ws + g.o_wg, dparams, st);
-    ISD_LAUNCH_CHECK();
-    return ISD_OK;
-  }
-  if (p->n_layers == 4 && F == 32 && !p->act_bf16 && p->max_cz <= 16 && g.TT <= 16 && (F * g.T1) % 4 == 0 &&
-      g.TT >= 4) {
-    // reference-native shape: one persistent fused kernel; gradient tiles stay in LDS, weight gradients in registers
-    constexpr int NW = 8;
-    const size_t lds = fused_bwd_lds(p, g);
-    const size_t lds_fwd = sizeof(float) * (size_t)(4 + ((16 * p->W + 3) & ~3) + 2 * ((F * g.T1 + 3) & ~3) + 8 * F +
-                                                     (4 + 8 + 8) * kTaps * 2 * 64 + 64);
-    kept_dgelu = lds <= 160 * 1024 && lds_fwd <= 150 * 1024;
-    if (kept_dgelu && !dx) {                              // (the input gradient needs G2 in memory: layer-wise path)
-      int per_zone = 256 / p->Z;
-      if (per_zone < 1) per_zone = 1;
-      if (per_zone > g.items) per_zone = (int)g.items;
-      FusedBwdArgs fb = {};
-      fb.x = x; fb.dfeat = dfeat; fb.a2 = ws + g.o_a2; fb.a3 = ws + g.o_a3; fb.a4 = ws + g.o_a4;
-      fb.w3t = ws + g.o_w3t; fb.w4t = ws + g.o_w4t;
-      fb.part4 = ws + g.o_part;
-      fb.part3 = fb.part4 + (int64_t)per_zone * 4 * g.slab1;
-      fb.part0 = fb.part3 + (int64_t)per_zone * 4 * g.slab1;
-      fb.zones = p->d_zones; fb.chan_idx = p->d_idx; fb.wz_stride = p->conv_zstride; fb.items = g.items;
-      fb.slab1 = g.slab1; fb.slab0 = g.slab0;
-      fb.Z = p->Z; fb.W = p->W; fb.T1 = g.T1; fb.TT = g.TT;
-      fb.Ctot = p->Ctot; fb.Tx = (int)T; fb.N = g.N; fb.S = p->S;
-      ISD_HIP_TRY(hipFuncSetAttribute((const void*)conv4_fused_bwd_kernel<NW>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)lds));
-      hipLaunchKernelGGL((conv4_fused_bwd_kernel<NW>), dim3(per_zone, p->Z), dim3(NW * 64), lds, st, fb);
-      ISD_LAUNCH_CHECK();
-      // the fp32 kernel leaves two slabs per workgroup for cnn3 / cnn4 and four for Weff (the buffers are sized for the
-      // bf16 twin's four and eight)
-      rc = launch_reduce_fused_bwd(fb.part4, fb.part3, fb.part0, g.slab1, per_zone * 2, g.slab0, per_zone * 4, dparams,
-                                   ws + g.o_wg, p->d_zones, F, st);
-      if (rc) return rc;
-      launch_fused_bwd(p, params, ws + g.o_wg, dparams, st);
-      ISD_LAUNCH_CHECK();
-      return ISD_OK;
-    }
-  }
+  // the input gradient needs G2 in memory: with dx a fused forward is followed by the layer-wise chain, which then
+  // finds GELU'(A4) in the A4 buffer (g.keep_dgelu)
+  if (g.route != Route::kLayerwise && !dx) return fused_backward(p, g, x, params, dfeat, dparams, ws, T, st);
   float* top = ws + (p->n_layers == 4 ? g.o_a4 : g.o_a2);        // activation that fed GELU
-  if (p->act_bf16)
-    hipLaunchKernelGGL((gelu_mean_bwd_kernel<bf16_t>), dim3((unsigned)cdiv(rows * 16, 256)), dim3(256), 0, st, top,
-                       dfeat, rows, g.T1);
-  else if (kept_dgelu)
-    hipLaunchKernelGGL((gelu_mean_bwd_kernel<float, true>), dim3((unsigned)cdiv(rows * 16, 256)), dim3(256), 0, st, top,
-                       dfeat, rows, g.T1);
-  else
-    hipLaunchKernelGGL((gelu_mean_bwd_kernel<float>), dim3((unsigned)cdiv(rows * 16, 256)), dim3(256), 0, st, top, dfeat,
-                       rows, g.T1);
-  ISD_LAUNCH_CHECK();
-  WgradArgs w = {};
-  w.zones = p->d_zones; w.chan_idx = p->d_idx; w.items = g.items;
-  w.Z = p->Z; w.F = F; w.Tout = g.T1; w.part = ws + g.o_part;
-  w.Ctot = p->Ctot; w.Tx = (int)T; w.N = g.N; w.S = p->S;
-  ConvArgs a = {};
-  a.zones = p->d_zones; a.chan_idx = p->d_idx; a.items = g.items; a.Z = p->Z; a.F = F;
-  a.TT = g.TT; a.IPW = g.IPW; a.Tout = g.T1; a.Tin = g.T1; a.pad = 2; a.RS = g.RS_b; a.wz_stride = p->conv_zstride;
-  a.CK = g.CK;
-  a.lin = 1;
-  a.Ctot = p->Ctot; a.Tx = (int)T; a.N = g.N; a.S = p->S;
+  rc = launch_gelu_mean_bwd(p, g, top, dfeat, g.keep_dgelu, st);
+  if (rc) return rc;
+  WgradArgs w = make_wgrad_args(p, g, T, ws);
+  ConvArgs a = make_conv_args(p, g, T);
+  a.Tin = g.T1; a.pad = 2; a.RS = g.RS_b; a.wz_stride = p->conv_zstride; a.lin = 1;
   const float* g2 = top;                                          // gradient w.r.t. the cnn2 output
   if (p->n_layers == 4) {
     w.dout = ws + g.o_a4; w.in = ws + g.o_a3; w.Tin = g.T1; w.pad = 2; w.RSo = g.T1; w.RSi = g.T1; w.lin = 1;
@@ -4015,16 +4009,12 @@ static int conv4_backward_impl(const isd_conv4_plan* p, const float* x, const fl
   }
   rc = first_layer_backward(p, g, x, T, params, g2, dparams, ws, st);
   if (rc || !dx) return rc;
-  const size_t lds = sizeof(float) * (size_t)F * g.T1;
+  const size_t lds = conv5_dx_lds(F, g.T1);
   ISD_CHECK_ARG(lds <= 150 * 1024, "isd_conv4_backward_x: window_len=%d is too long for the gradient tile", p->W);
   ISD_CHECK_ARG(g.items <= 0x7fffffffLL, "isd_conv4_backward_x: too many items");
   ISD_HIP_TRY(hipMemsetAsync(dx, 0, sizeof(float) * (size_t)B * p->Ctot * T, st));
-  if (lds > 48 * 1024)
-    ISD_HIP_TRY(hipFuncSetAttribute((const void*)conv5_dx_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(conv5_dx_kernel, dim3((unsigned)g.items, p->Z), dim3(256), lds, st, g2, ws + g.o_eff, p->d_zones,
-                     p->d_idx, dx, p->Z, F, g.T1, p->W, p->Ctot, (int)T, g.N, p->S);
-  ISD_LAUNCH_CHECK();
-  return ISD_OK;
+  return launch_lds(conv5_dx_kernel, dim3((unsigned)g.items, p->Z), dim3(256), lds, st, g2, ws + g.o_eff, p->d_zones,
+                    p->d_idx, dx, p->Z, F, g.T1, p->W, p->Ctot, (int)T, g.N, p->S);
 }
 
 extern "C" int isd_conv4_backward(const isd_conv4_plan* p, const float* x, const float* params, const float* dfeat,
