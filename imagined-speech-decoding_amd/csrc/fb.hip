@@ -1110,6 +1110,11 @@ void fused_long_kernel(const FbSec* __restrict__ secs, const FbBand* __restrict_
   }
 }
 
+// Dynamic LDS of fused_long_kernel: block sums [KB][64] and twiddles, then the carried states and the per-lane M^i
+static size_t fused_long_lds(int KB) {
+  return sizeof(float2) * ((size_t)KB * 64 + 64) + sizeof(double) * (2 * kMaxSec + 64 * kMaxSec);
+}
+
 // Real sample x complex twiddle into a (re, im) accumulator, the sample taken from the LOW / HIGH half of a register
 // pair and the twiddle from an SGPR pair.  Written as (f2){s, s} * t the compiler materialises the duplicated pairs
 // (a v_mov per sample and 64 more live registers); the packed FMA's operand selects do the broadcast for nothing.
@@ -1399,6 +1404,14 @@ void fused_rows4_kernel(const FbSec* __restrict__ secs, const FbBand* __restrict
     }
   }
 }
+
+// Dynamic LDS of fused_rows4_kernel: the block ring of four rows and the twiddles, then the carried states and the
+// per-lane M^i of every section.  At most 8 (4 5 32 + 64) + 8 72 8 = 10240 bytes (KB <= 5, n_sections <= 8): far below
+// the 48 KiB a kernel may use without raising its limit, so no launch sets the attribute.
+static size_t fused_rows4_lds(int KB, int n_sections) {
+  return sizeof(float2) * ((size_t)4 * KB * 32 + 64) + sizeof(double) * (8 + 64) * (size_t)n_sections;
+}
+static_assert(sizeof(float2) * (4 * 5 * 32 + 64) + sizeof(double) * (8 + 64) * kMaxSec == 10240, "rows4 LDS bound");
 
 // ---------------------------------------------------------------------------------------------------------------
 // Round 4: the fused spec-S extractor with ONE ROW PER LANE (rows of whole 32-sample chunks, nperseg 64 / hop 32).
@@ -1691,6 +1704,9 @@ void fused_serial_kernel(const SerSec* __restrict__ secs, const FbBand* __restri
   }
 }
 
+// Dynamic LDS of fused_serial_kernel: two 64 x 32 tiles per row group
+static size_t fused_serial_lds(int groups) { return sizeof(float) * (size_t)groups * 2 * kSerRows * kL; }
+
 static void mat2_mul(const double* a, const double* b, double* o) {
   double r[4] = {a[0] * b[0] + a[1] * b[2], a[0] * b[1] + a[1] * b[3], a[2] * b[0] + a[3] * b[2],
                  a[2] * b[1] + a[3] * b[3]};
@@ -1702,6 +1718,33 @@ static void mat2_mul(const double* a, const double* b, double* o) {
 using namespace isd;
 
 extern "C" int isd_fb_plan_destroy(isd_fb_plan* p);
+
+// The extractor's environment switches: A/B measurements, and the tests that hold two routes against each other
+// (DESIGN.md 3.2a has the table).  They are read here and nowhere else.
+// Once per process -- ISD_FUSED_ROWS4_OFF: long rows go to the one-row-per-wave kernels; ISD_ROWS4_LDS_CARRY: the fp32
+// rows4 kernel keeps its carried section states in LDS
+static bool env_rows4_off() { static const bool v = getenv("ISD_FUSED_ROWS4_OFF") != nullptr; return v; }
+static bool env_rows4_lds_carry() { static const bool v = getenv("ISD_ROWS4_LDS_CARRY") != nullptr; return v; }
+// Per call, so that a test can switch them -- ISD_FUSED_SERIAL=0: short rows stay on fused_kernel; ISD_SERIAL_BPW (1..3)
+// and ISD_SERIAL_GROUPS: the serial kernel's bands per wave and row groups per workgroup, 0 when unset
+static bool env_fused_serial() { const char* e = getenv("ISD_FUSED_SERIAL"); return !(e && e[0] == '0'); }
+static int env_serial_bpw() { const char* e = getenv("ISD_SERIAL_BPW"); return e ? atoi(e) : 0; }
+static int env_serial_groups() { const char* e = getenv("ISD_SERIAL_GROUPS"); return e ? atoi(e) : 0; }
+// Per plan -- ISD_FB_AUTO_LIMIT replaces the AUTO threshold on the round-off amplification estimate: a positive number,
+// or the call fails (atof("") = 0 would silently send every band to the fp64 kernels)
+static int env_fb_auto_limit(double* limit) {
+  const char* e = getenv("ISD_FB_AUTO_LIMIT");
+  char* end = nullptr;
+  const double v = e ? strtod(e, &end) : *limit;
+  ISD_CHECK_ARG(!e || (end != e && *end == '\0' && v > 0.0 && v < 1e300),
+                "isd_fb_plan_create: ISD_FB_AUTO_LIMIT='%s' is not a positive number", e);
+  *limit = v;
+  return ISD_OK;
+}
+
+static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// float4 accesses: rows of a multiple of four samples behind 16-byte aligned bases
+static bool vec_ok(int T, const void* a, const void* b = nullptr) { return (T & 3) == 0 && aligned16(a) && aligned16(b); }
 
 // Workgroups that share a quad of rows in the rows4 kernels: the count in [4, 8] (8 preferred) that wastes the fewest
 // band slots -- ceil(nb / s) s / nb -- and keeps a workgroup's bands within its carry slots.
@@ -1715,18 +1758,6 @@ static int rows4_share(int nb) {
     if (w < best_w - 1e-9) { best_w = w; best = s; }
   }
   return best;
-}
-
-// ISD_FUSED_ROWS4_OFF=1 sends long rows to the one-row-per-wave kernels (A/B measurements); read once
-static bool rows4_enabled() {
-  static const bool on = getenv("ISD_FUSED_ROWS4_OFF") == nullptr;
-  return on;
-}
-
-// ISD_ROWS4_LDS_CARRY=1 keeps the carried section states of the fp32 rows4 kernel in LDS (A/B measurements); read once
-static bool rows4_reg_carry() {
-  static const bool on = getenv("ISD_ROWS4_LDS_CARRY") == nullptr;
-  return on;
 }
 
 // The constants of one biquad section (wave-uniform tables of the kernels) and its 16 per-lane matrices M^i
@@ -1797,12 +1828,6 @@ extern "C" int isd_fb_plan_create(isd_fb_plan** out, int n_bands, int n_sections
       }
     }
   }
-  isd_fb_plan* p = new isd_fb_plan();
-  p->n_bands = n_bands; p->n_sections = n_sections;
-  for (int k = 0; k < 2; ++k) {
-    p->set[k] = FbSet{0, nullptr, nullptr, nullptr, nullptr, nullptr};
-    p->host_map[k] = nullptr;
-  }
   // per-band arithmetic: AUTO sends a band to the fp64 set when one of its poles is too close to z = 1.  The threshold
   // on the round-off amplification estimate was 2000 until round 3; measured at the stress set (tools/
   // auto_limit_probe.py, |feature - scipy fp64| / max(1, |feature|), gate 1e-4): the bands between 2000 and 6000
@@ -1813,14 +1838,13 @@ extern "C" int isd_fb_plan_create(isd_fb_plan** out, int n_bands, int n_sections
   // (20 900) misses both.  A host replay of the fp32 chunk arithmetic as the criterion was tried and dropped: it
   // ranks the five like the estimate does (rms error 2.9e-5 / 1.3e-5 / 1.9e-5 / 1.4e-5 / 7e-6 of the signal) and
   // separates the 5-band set's 0.5 - 4 Hz band (1.4e-4) no better.  ISD_FB_AUTO_LIMIT overrides.
-  const char* lim_env = getenv("ISD_FB_AUTO_LIMIT");
   double auto_limit = 6000.0;
-  if (lim_env) {                                            // a positive number, or the call fails (atof("") = 0 would
-    char* end = nullptr;                                    // silently send every band to the fp64 kernels)
-    const double v = strtod(lim_env, &end);
-    ISD_CHECK_ARG(end != lim_env && *end == '\0' && v > 0.0 && v < 1e300,
-                  "isd_fb_plan_create: ISD_FB_AUTO_LIMIT='%s' is not a positive number", lim_env);
-    auto_limit = v;
+  if (const int rc = env_fb_auto_limit(&auto_limit)) return rc;
+  isd_fb_plan* p = new isd_fb_plan();
+  p->n_bands = n_bands; p->n_sections = n_sections;
+  for (int k = 0; k < 2; ++k) {
+    p->set[k] = FbSet{0, nullptr, nullptr, nullptr, nullptr, nullptr};
+    p->host_map[k] = nullptr;
   }
   std::vector<int> idx[2];
   for (int b = 0; b < n_bands; ++b) {
@@ -1895,49 +1919,74 @@ extern "C" int isd_fb_plan_destroy(isd_fb_plan* p) {
 
 extern "C" int isd_fb_plan_precision(const isd_fb_plan* p) { return p ? p->precision : ISD_ERR_INVALID; }
 
-template <typename VT, int GPR>
-static int fb_launch(const isd_fb_plan* p, const FbSet& fs, const float* x, float* y, int64_t R, int C, int T,
-                     hipStream_t st) {
-  const int64_t items = cdiv(R, (int64_t)(4 / GPR));
-  const int vec = ((T & 3) == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0) &&
-                  ((reinterpret_cast<uintptr_t>(y) & 15) == 0);
-  if (vec && T == GPR * kSeg && R % (4 / GPR) == 0)   // whole waves of whole segments: the branch-free store path
-    hipLaunchKernelGGL((fb_kernel<VT, GPR, true>), dim3((unsigned)items), dim3(64), 0, st, fs.d_sec, fs.d_band, fs.d_Q, x,
-                       y, (int)R, C, T, fs.nb, p->n_sections, vec, fs.d_map, p->n_bands);
-  else
-    hipLaunchKernelGGL((fb_kernel<VT, GPR>), dim3((unsigned)items), dim3(64), 0, st, fs.d_sec, fs.d_band, fs.d_Q, x, y,
-                       (int)R, C, T, fs.nb, p->n_sections, vec, fs.d_map, p->n_bands);
-  ISD_LAUNCH_CHECK();
-  return ISD_OK;
+// One launch of the filterbank or of the fused extractor: the kernel family, the template selectors of the instance and
+// what the launch derives from the shape.  choose_fb_route / choose_fused_route fill it and hold every shape, alignment,
+// band-count and environment test (DESIGN.md 3.2a has the table); the launch functions only read it.
+enum Family {
+  kFbShort, kFbLong, kFbRows4,               // isd_fb_forward: fb_kernel, fb_long_kernel_*, fb_rows4_kernel_*
+  kDirect16, kSerial, kLong, kRows4          // the fused call: fused_kernel, fused_serial_, fused_long_, fused_rows4_kernel
+};
+struct Route {
+  Family family;
+  dim3 grid, block;
+  size_t lds;                  // dynamic LDS bytes
+  // Template selectors.  f64: VT double (the plan's fp64 set) or float | gpr: GPR, 16-lane groups per row | full: FULL,
+  // whole waves of whole segments | mag: MAG | vec: VEC and the kernels' `vec` argument, float4 row accesses | kb: KB,
+  // bin slots (blocksum_plan) | carry_n: NS of fused_rows4_kernel, 4 = carried states in registers, 0 = in LDS | bpw:
+  // BPW, bands per wave of the serial kernel | fullq: FULLQ, every quad of rows is whole
+  bool f64, full, mag, fullq;
+  int gpr, vec, kb, carry_n, bpw;
+  int share_n, nw, groups, log2_nblk;   // scalar launch arguments derived from the shape
+};
+
+static Route choose_fb_route(const isd_fb_plan* p, int k, const float* x, const float* y, int64_t R, int T) {
+  const FbSet& fs = p->set[k];
+  Route r = {};
+  r.f64 = k == 1;
+  r.block = dim3(64);
+  r.vec = vec_ok(T, x, y);
+  if (T <= 2 * kSeg) {
+    r.family = kFbShort;
+    r.gpr = T <= kSeg ? 1 : 2;
+    r.full = r.vec && T == r.gpr * kSeg && R % (4 / r.gpr) == 0;
+    r.grid = dim3((unsigned)cdiv(R, 4 / r.gpr));
+  } else if (r.vec && T % kSeg == 0 && fs.nb <= kMaxBands && !env_rows4_off()) {
+    r.family = kFbRows4;                     // four rows per wave, group-local carries (carry slots for kMaxBands bands)
+    r.share_n = rows4_share(fs.nb);
+    r.fullq = R % 4 == 0;
+    r.grid = dim3((unsigned)(cdiv(cdiv(R, 4), 8) * 8 * r.share_n));
+  } else {
+    r.family = kFbLong;
+    r.grid = dim3((unsigned)(cdiv(R, 8) * 8 * kLongShare));
+  }
+  return r;
 }
 
-template <typename VT>
-static int fb_launch_t(const isd_fb_plan* p, const FbSet& fs, const float* x, float* y, int64_t R, int C, int T,
-                       hipStream_t st) {
-  if (T <= kSeg) return fb_launch<VT, 1>(p, fs, x, y, R, C, T, st);
-  if (T <= 2 * kSeg) return fb_launch<VT, 2>(p, fs, x, y, R, C, T, st);
-  const int vec = ((T & 3) == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0) &&
-                  ((reinterpret_cast<uintptr_t>(y) & 15) == 0);
-  if (vec && T % kSeg == 0 && fs.nb <= kMaxBands && rows4_enabled()) {   // four rows per wave, group-local carries (carry slots for kMaxBands bands)
-    const int share_n = rows4_share(fs.nb);
-    const dim3 grid4((unsigned)(cdiv(cdiv(R, 4), 8) * 8 * share_n));
-#define ISD_R4(K) hipLaunchKernelGGL(K, grid4, dim3(64), 0, st, fs.d_sec, fs.d_band, fs.d_Q, x, y, C, T, fs.nb, \
-                                     p->n_sections, fs.d_map, p->n_bands, (int)R, share_n)
-    const bool fullq = R % 4 == 0;
-    if (std::is_same<VT, float>::value) { if (fullq) ISD_R4(fb_rows4_kernel_f32<true>); else ISD_R4(fb_rows4_kernel_f32<false>); }
-    else { if (fullq) ISD_R4(fb_rows4_kernel_f64<true>); else ISD_R4(fb_rows4_kernel_f64<false>); }
-#undef ISD_R4
-    ISD_LAUNCH_CHECK();
-    return ISD_OK;
+static int fb_launch(const isd_fb_plan* p, int k, const Route& r, const float* x, float* y, int64_t R, int C, int T,
+                     hipStream_t st) {
+  const FbSet& fs = p->set[k];
+  switch (r.family) {
+    case kFbShort: {
+      static constexpr decltype(&fb_kernel<float, 1, false>) kern[2][2][2] = {   // [f64][gpr - 1][full]
+          {{fb_kernel<float, 1, false>, fb_kernel<float, 1, true>}, {fb_kernel<float, 2, false>, fb_kernel<float, 2, true>}},
+          {{fb_kernel<double, 1, false>, fb_kernel<double, 1, true>},
+           {fb_kernel<double, 2, false>, fb_kernel<double, 2, true>}}};
+      return launch_lds(kern[r.f64][r.gpr - 1][r.full], r.grid, r.block, 0, st, fs.d_sec, fs.d_band, fs.d_Q, x, y, (int)R,
+                        C, T, fs.nb, p->n_sections, r.vec, fs.d_map, p->n_bands);
+    }
+    case kFbRows4: {
+      static constexpr decltype(&fb_rows4_kernel_f32<false>) kern[2][2] = {      // [f64][fullq]
+          {fb_rows4_kernel_f32<false>, fb_rows4_kernel_f32<true>}, {fb_rows4_kernel_f64<false>, fb_rows4_kernel_f64<true>}};
+      return launch_lds(kern[r.f64][r.fullq], r.grid, r.block, 0, st, fs.d_sec, fs.d_band, fs.d_Q, x, y, C, T, fs.nb,
+                        p->n_sections, fs.d_map, p->n_bands, (int)R, r.share_n);
+    }
+    default: {
+      static constexpr decltype(&fb_long_kernel_f32<false>) kern[2][2] = {       // [f64][vec]
+          {fb_long_kernel_f32<false>, fb_long_kernel_f32<true>}, {fb_long_kernel_f64<false>, fb_long_kernel_f64<true>}};
+      return launch_lds(kern[r.f64][r.vec], r.grid, r.block, 0, st, fs.d_sec, fs.d_band, fs.d_Q, x, y, C, T, fs.nb,
+                        p->n_sections, fs.d_map, p->n_bands, (int)R);
+    }
   }
-  const dim3 grid((unsigned)(cdiv(R, 8) * 8 * kLongShare));
-#define ISD_FBL(K) hipLaunchKernelGGL(K, grid, dim3(64), 0, st, fs.d_sec, fs.d_band, fs.d_Q, x, y, C, T, fs.nb, \
-                                      p->n_sections, fs.d_map, p->n_bands, (int)R)
-  if (std::is_same<VT, float>::value) { if (vec) ISD_FBL(fb_long_kernel_f32<true>); else ISD_FBL(fb_long_kernel_f32<false>); }
-  else { if (vec) ISD_FBL(fb_long_kernel_f64<true>); else ISD_FBL(fb_long_kernel_f64<false>); }
-#undef ISD_FBL
-  ISD_LAUNCH_CHECK();
-  return ISD_OK;
 }
 
 extern "C" int isd_fb_forward(const isd_fb_plan* p, const float* x, float* y, int64_t B, int64_t C, int64_t T,
@@ -1950,10 +1999,12 @@ extern "C" int isd_fb_forward(const isd_fb_plan* p, const float* x, float* y, in
   hipStream_t st = (hipStream_t)stream;
   const int64_t R = B * C;
   ISD_CHECK_ARG(R <= kMaxRows, "isd_fb_forward: too many rows (%lld)", (long long)R);
-  int rc = ISD_OK;
-  if (p->set[0].nb) rc = fb_launch_t<float>(p, p->set[0], x, y, R, (int)C, (int)T, st);
-  if (rc == ISD_OK && p->set[1].nb) rc = fb_launch_t<double>(p, p->set[1], x, y, R, (int)C, (int)T, st);
-  return rc;
+  for (int k = 0; k < 2; ++k) {
+    if (!p->set[k].nb) continue;
+    const int rc = fb_launch(p, k, choose_fb_route(p, k, x, y, R, (int)T), x, y, R, (int)C, (int)T, st);
+    if (rc) return rc;
+  }
+  return ISD_OK;
 }
 
 // host side of FusedBands: bin ranges plus 1 / (number of bins)
@@ -1963,17 +2014,22 @@ static void set_band(FusedBands& f, int i, int klo, int khi) {
   f.inv[i] = khi >= klo ? 1.f / (float)(khi - klo + 1) : 0.f;
 }
 
-// One row per lane (fused_serial_kernel): rows of whole 32-sample chunks, 16-byte aligned, four sections, every band of
-// the set with one or two interior bins.  ISD_FUSED_SERIAL=0 keeps the 16-lanes-per-row kernel (A/B measurements and the
-// test that holds the two against each other); read per call so that a test can switch it.
+// The bands of precision set k, in the set's order, out of the plan's
+static FusedBands set_bands(const isd_fb_plan* fb, int k, const FusedBands& all) {
+  FusedBands f = {};
+  for (int i = 0; i < fb->set[k].nb; ++i) set_band(f, i, all.klo[fb->host_map[k][i]], all.khi[fb->host_map[k][i]]);
+  return f;
+}
+
+// What isd_features_fused_last_path() reports: the family of the fp32 set's launch (1 fused_kernel, 2
+// fused_serial_kernel, 3 long rows); assigned once per call, in features_fused_impl
 static thread_local int g_fused_path = 0;
 extern "C" int isd_features_fused_last_path(void) { return g_fused_path; }
 
-static bool serial_wanted() {
-  const char* e = getenv("ISD_FUSED_SERIAL");
-  return !(e && e[0] == '0');
-}
-
+static constexpr decltype(&fused_serial_kernel<1, false>) kSerialKernels[3][2] = {   // [bpw - 1][mag]
+    {fused_serial_kernel<1, false>, fused_serial_kernel<1, true>},
+    {fused_serial_kernel<2, false>, fused_serial_kernel<2, true>},
+    {fused_serial_kernel<3, false>, fused_serial_kernel<3, true>}};
 // Tiles above 48 KiB (four row groups: 64 KiB) need the kernels' dynamic-LDS limit raised: once per process and device,
 // to the largest tile the launcher builds, instead of twice in front of every launch.
 static void serial_lds_limit() {
@@ -1982,82 +2038,136 @@ static void serial_lds_limit() {
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
   const unsigned long long bit = 1ull << dev;
   if (done.load(std::memory_order_relaxed) & bit) return;
-  const int lds = (int)(sizeof(float) * kSerMaxGroups * 2 * kSerRows * kL);
-  const void* k[] = {(const void*)fused_serial_kernel<1, false>, (const void*)fused_serial_kernel<1, true>,
-                     (const void*)fused_serial_kernel<2, false>, (const void*)fused_serial_kernel<2, true>,
-                     (const void*)fused_serial_kernel<3, false>, (const void*)fused_serial_kernel<3, true>};
-  for (const void* f : k) (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  for (const auto& per_bpw : kSerialKernels)
+    for (const auto f : per_bpw)
+      (void)hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)fused_serial_lds(kSerMaxGroups));
   done.fetch_or(bit, std::memory_order_relaxed);
 }
 
-static bool fused_serial_launch(const isd_fb_plan* fb, const FbSet& fs, const isd_stft_plan* st, const float* x,
-                                float* feat, int64_t R, int C, const FusedBands& fbnd, int mode, float eps,
-                                hipStream_t stream, int out16) {
-  if (!serial_wanted() || !st->d_sym || !fs.d_ser || st->n != 64 || st->hop != 32 || st->T % kL != 0 || st->T < kL) return false;
-  if (st->J != st->T / kL + 1 || fb->n_sections != 4 || (reinterpret_cast<uintptr_t>(x) & 15) != 0) return false;
-  if (fs.nb < 1 || fs.nb > 12) return false;
-  if (cdiv(R, C) * (int64_t)fb->n_bands * C * st->J * 4 >= (1LL << 31)) return false;   // 32-bit byte offsets into the map
-  for (int i = 0; i < fs.nb; ++i) {
-    const int nbin = fbnd.khi[i] - fbnd.klo[i] + 1;
-    if (nbin < 1 || nbin > kSerBins - 2 || fbnd.klo[i] < 1 || fbnd.khi[i] > st->n / 2 - 1) return false;
-  }
-  // bands per wave: 1 (five waves per SIMD), 2 (four) or 3 (three); ISD_SERIAL_BPW overrides the choice
-  int bpw = 3;
-  if (const char* e = getenv("ISD_SERIAL_BPW")) { const int v = atoi(e); if (v >= 1 && v <= 3) bpw = v; }
-  while (bpw < 3 && (fs.nb + bpw - 1) / bpw > kSerMaxWaves) ++bpw;
-  const int nw = (fs.nb + bpw - 1) / bpw;                             // waves per row group
-  bpw = (fs.nb + nw - 1) / nw;
-  int groups = nw % 4 == 0 ? 1 : nw % 2 == 0 ? 2 : 4;                 // waves per workgroup: a multiple of four
-  while (groups > 1 && groups * nw > kSerMaxWaves) groups >>= 1;
-  if (const char* e = getenv("ISD_SERIAL_GROUPS")) { const int v = atoi(e); if (v >= 1 && v <= kSerMaxGroups && v * nw <= kSerMaxWaves) groups = v; }
-  const dim3 grid((unsigned)cdiv(R, (int64_t)kSerRows * groups));
-  const size_t lds = sizeof(float) * (size_t)groups * 2 * kSerRows * kL;
-  const bool mag = mode == ISD_BP_MAGNITUDE;
-  if (lds > 48 * 1024) serial_lds_limit();
-#define ISD_SER(BPW_)                                                                                                   \
-  do {                                                                                                                  \
-    if (mag)                                                                                                            \
-      hipLaunchKernelGGL((fused_serial_kernel<BPW_, true>), grid, dim3(64 * nw * groups), lds, stream, fs.d_ser,        \
-                         fs.d_band, st->d_sym, x, feat, (int)R, C, st->T, fs.nb, st->J, st->scale * st->scale, fbnd,    \
-                         mode, eps, fs.d_map, fb->n_bands, out16, nw);                                                  \
-    else                                                                                                                \
-      hipLaunchKernelGGL((fused_serial_kernel<BPW_, false>), grid, dim3(64 * nw * groups), lds, stream, fs.d_ser,       \
-                         fs.d_band, st->d_sym, x, feat, (int)R, C, st->T, fs.nb, st->J, st->scale * st->scale, fbnd,    \
-                         mode, eps, fs.d_map, fb->n_bands, out16, nw);                                                  \
-  } while (0)
-  if (bpw == 1) ISD_SER(1);
-  else if (bpw == 2) ISD_SER(2);
-  else ISD_SER(3);
-#undef ISD_SER
-  return true;
+// The two row shapes the fused call serves
+static bool fused_short_rows(const isd_stft_plan* st) {
+  return st->n == 64 && st->hop == 32 && st->T <= 2 * kSeg && st->d_dft;
 }
+static bool fused_long_rows(const isd_stft_plan* st) { return st->d_blk && st->hop == 64 && st->T <= 64 * 64; }
 
-template <typename VT>
-static int fused_launch(const isd_fb_plan* fb, const FbSet& fs, const isd_stft_plan* st, const float* x, float* feat,
-                        int64_t R, int C, const FusedBands& fbnd, int mode, float eps, hipStream_t stream, int out16) {
-  if (std::is_same<VT, float>::value &&
-      fused_serial_launch(fb, fs, st, x, feat, R, C, fbnd, mode, eps, stream, out16)) {
-    g_fused_path = 2;
-    ISD_LAUNCH_CHECK();
+// The route of precision set k of a fused call over R rows; `all` holds the plan's bands in the caller's order
+static int choose_fused_route(const isd_fb_plan* fb, int k, const isd_stft_plan* st, const float* x, int64_t R, int C,
+                              const FusedBands& all, int mode, Route& r) {
+  const FbSet& fs = fb->set[k];
+  r = Route{};
+  r.f64 = k == 1;
+  r.mag = mode == ISD_BP_MAGNITUDE;
+  r.block = dim3(64);
+  r.vec = vec_ok(st->T, x);
+  if (!fused_short_rows(st)) {
+    // long rows, heavily overlapped frames: filterbank + block sums in one kernel per band set
+    r.family = kLong;
+    const int bad = blocksum_plan(st, all.klo, all.khi, fb->n_bands, &r.kb, &r.log2_nblk);
+    if (bad >= 0) {
+      set_error("isd_features_fused: band %d needs 1..6 interior bins for the block-sum path (bins %d..%d)", bad,
+                all.klo[bad], all.khi[bad]);
+      return ISD_ERR_UNSUPPORTED;
+    }
+    // rows of whole 512-sample passes covering all 64 blocks: four rows per wave, no cross-group chain.  Its instances
+    // stop at KB = 5; wider bands stay on the one-row-per-wave kernel.
+    if (r.vec && st->T % kSeg == 0 && r.log2_nblk <= 4 && r.log2_nblk >= 1 && !env_rows4_off() && r.kb <= 5) {
+      r.family = kRows4;
+      // fp32 with the usual four sections (order-4 Butterworth band-pass): the carried states in registers
+      r.carry_n = !r.f64 && fb->n_sections == 4 && !env_rows4_lds_carry() ? 4 : 0;
+      r.share_n = rows4_share(fs.nb);
+      r.grid = dim3((unsigned)(cdiv(cdiv(R, 4), 8) * 8 * r.share_n));
+      r.lds = fused_rows4_lds(r.kb, fb->n_sections);
+    } else {
+      r.grid = dim3((unsigned)(cdiv(R, 8) * 8 * kLongShare));
+      r.lds = fused_long_lds(r.kb);
+    }
     return ISD_OK;
   }
-  if (std::is_same<VT, float>::value) g_fused_path = 1;
-  const bool two = st->T > kSeg;                          // rows of 513..1024 samples: two 16-lane groups per row
-  const int64_t items = cdiv(R, two ? 2 : 4);
-  const int vec = ((st->T & 3) == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0);
-  const int gpr = two ? 2 : 1;
-  const bool full = vec && st->T == gpr * kSeg && R % (4 / gpr) == 0;   // whole waves of whole segments (tile_load<FULL>)
-#define ISD_FUSED3(M, G, F)                                                                                          \
-  hipLaunchKernelGGL((fused_kernel<VT, M, G, F>), dim3((unsigned)items), dim3(64), 0, stream, fs.d_sec, fs.d_band,   \
-                     fs.d_Q, st->d_dft, x, feat, (int)R, C, st->T, fs.nb, fb->n_sections, st->J,                     \
-                     st->scale * st->scale, fbnd, mode, eps, vec, fs.d_map, fb->n_bands, out16)
-#define ISD_FUSED(M, G) do { if (full) ISD_FUSED3(M, G, true); else ISD_FUSED3(M, G, false); } while (0)
-  if (mode == ISD_BP_MAGNITUDE) { if (two) ISD_FUSED(true, 2); else ISD_FUSED(true, 1); }
-  else { if (two) ISD_FUSED(false, 2); else ISD_FUSED(false, 1); }
-#undef ISD_FUSED3
-#undef ISD_FUSED
-  ISD_LAUNCH_CHECK();
+  // One row per lane (fused_serial_kernel): the fp32 set of at most 12 bands, each of one or two interior bins, four
+  // sections, 16-byte aligned rows of whole 32-sample chunks, and 32-bit byte offsets into the feature map
+  bool serial = !r.f64 && env_fused_serial() && st->d_sym && fs.d_ser && st->n == 64 && st->hop == 32 &&
+                st->T % kL == 0 && st->T >= kL && st->J == st->T / kL + 1 && fb->n_sections == 4 && aligned16(x) &&
+                fs.nb >= 1 && fs.nb <= 12 && cdiv(R, C) * (int64_t)fb->n_bands * C * st->J * 4 < (1LL << 31);
+  for (int i = 0; serial && i < fs.nb; ++i) {
+    const int klo = all.klo[fb->host_map[k][i]], khi = all.khi[fb->host_map[k][i]], nbin = khi - klo + 1;
+    serial = nbin >= 1 && nbin <= kSerBins - 2 && klo >= 1 && khi <= st->n / 2 - 1;
+  }
+  if (serial) {
+    r.family = kSerial;
+    // bands per wave: 1 (five waves per SIMD), 2 (four) or 3 (three); ISD_SERIAL_BPW overrides the choice
+    const int want = env_serial_bpw(), g = env_serial_groups();
+    int bpw = want >= 1 && want <= 3 ? want : 3;
+    while (bpw < 3 && (fs.nb + bpw - 1) / bpw > kSerMaxWaves) ++bpw;
+    r.nw = (fs.nb + bpw - 1) / bpw;                                       // waves per row group
+    r.bpw = (fs.nb + r.nw - 1) / r.nw;
+    r.groups = r.nw % 4 == 0 ? 1 : r.nw % 2 == 0 ? 2 : 4;                 // waves per workgroup: a multiple of four
+    while (r.groups > 1 && r.groups * r.nw > kSerMaxWaves) r.groups >>= 1;
+    if (g >= 1 && g <= kSerMaxGroups && g * r.nw <= kSerMaxWaves) r.groups = g;
+    r.grid = dim3((unsigned)cdiv(R, (int64_t)kSerRows * r.groups));
+    r.block = dim3(64 * r.nw * r.groups);
+    r.lds = fused_serial_lds(r.groups);
+  } else {
+    r.family = kDirect16;
+    r.gpr = st->T > kSeg ? 2 : 1;                                         // rows of 513..1024 samples: two 16-lane groups
+    r.full = r.vec && st->T == r.gpr * kSeg && R % (4 / r.gpr) == 0;
+    r.grid = dim3((unsigned)cdiv(R, 4 / r.gpr));
+  }
   return ISD_OK;
+}
+
+static int fused_launch(const isd_fb_plan* fb, int k, const isd_stft_plan* st, const Route& r, const float* x,
+                        float* feat, int64_t R, int C, const FusedBands& fbnd, int mode, float eps, hipStream_t s,
+                        int out16) {
+  const FbSet& fs = fb->set[k];
+  const float scale2 = st->scale * st->scale;
+  const int kbi = r.kb == 8 ? 3 : r.kb - 4;                               // KB 4, 5, 6, 8
+  switch (r.family) {
+    case kSerial: {
+      if (r.lds > 48 * 1024) serial_lds_limit();      // not launch_lds: it would raise the limit before every launch
+      hipLaunchKernelGGL(kSerialKernels[r.bpw - 1][r.mag], r.grid, r.block, r.lds, s, fs.d_ser, fs.d_band, st->d_sym, x, feat,
+                         (int)R, C, st->T, fs.nb, st->J, scale2, fbnd, mode, eps, fs.d_map, fb->n_bands, out16, r.nw);
+      ISD_LAUNCH_CHECK();
+      return ISD_OK;
+    }
+    case kRows4: {                           // KB 4 or 5; fp64 has no register-carry instance
+      using K = decltype(&fused_rows4_kernel<float, 4, 0>);
+      static constexpr K f32[2][2] = {{fused_rows4_kernel<float, 4, 0>, fused_rows4_kernel<float, 4, 4>},
+                                      {fused_rows4_kernel<float, 5, 0>, fused_rows4_kernel<float, 5, 4>}};
+      static constexpr K f64[2] = {fused_rows4_kernel<double, 4, 0>, fused_rows4_kernel<double, 5, 0>};
+      return launch_lds(r.f64 ? f64[r.kb - 4] : f32[r.kb - 4][r.carry_n == 4], r.grid, r.block, r.lds, s, fs.d_sec,
+                        fs.d_band, fs.d_Q, st->d_blk, x, feat, C, st->T, fs.nb, fb->n_sections, st->J, r.log2_nblk,
+                        st->n / 2, scale2, fbnd, mode, eps, fs.d_map, fb->n_bands, (int)R, r.share_n, out16);
+    }
+    case kLong: {
+      static constexpr decltype(&fused_long_kernel<float, 4, false>) kern[2][4][2] = {   // [f64][KB: 4, 5, 6, 8][vec]
+          {{fused_long_kernel<float, 4, false>, fused_long_kernel<float, 4, true>},
+           {fused_long_kernel<float, 5, false>, fused_long_kernel<float, 5, true>},
+           {fused_long_kernel<float, 6, false>, fused_long_kernel<float, 6, true>},
+           {fused_long_kernel<float, 8, false>, fused_long_kernel<float, 8, true>}},
+          {{fused_long_kernel<double, 4, false>, fused_long_kernel<double, 4, true>},
+           {fused_long_kernel<double, 5, false>, fused_long_kernel<double, 5, true>},
+           {fused_long_kernel<double, 6, false>, fused_long_kernel<double, 6, true>},
+           {fused_long_kernel<double, 8, false>, fused_long_kernel<double, 8, true>}}};
+      return launch_lds(kern[r.f64][kbi][r.vec], r.grid, r.block, r.lds, s, fs.d_sec, fs.d_band, fs.d_Q, st->d_blk, x,
+                        feat, C, st->T, fs.nb, fb->n_sections, st->J, r.log2_nblk, st->n / 2, scale2, fbnd, mode, eps,
+                        fs.d_map, fb->n_bands, (int)R, out16);
+    }
+    default: {
+      static constexpr decltype(&fused_kernel<float, false, 1, false>) kern[2][2][2][2] = {   // [f64][mag][gpr - 1][full]
+          {{{fused_kernel<float, false, 1, false>, fused_kernel<float, false, 1, true>},
+            {fused_kernel<float, false, 2, false>, fused_kernel<float, false, 2, true>}},
+           {{fused_kernel<float, true, 1, false>, fused_kernel<float, true, 1, true>},
+            {fused_kernel<float, true, 2, false>, fused_kernel<float, true, 2, true>}}},
+          {{{fused_kernel<double, false, 1, false>, fused_kernel<double, false, 1, true>},
+            {fused_kernel<double, false, 2, false>, fused_kernel<double, false, 2, true>}},
+           {{fused_kernel<double, true, 1, false>, fused_kernel<double, true, 1, true>},
+            {fused_kernel<double, true, 2, false>, fused_kernel<double, true, 2, true>}}}};
+      return launch_lds(kern[r.f64][r.mag][r.gpr - 1][r.full], r.grid, r.block, 0, s, fs.d_sec, fs.d_band, fs.d_Q,
+                        st->d_dft, x, feat, (int)R, C, st->T, fs.nb, fb->n_sections, st->J, scale2, fbnd, mode, eps, r.vec,
+                        fs.d_map, fb->n_bands, out16);
+    }
+  }
 }
 
 static int features_fused_impl(const isd_fb_plan* fb, const isd_stft_plan* st, const float* x, float* feat,
@@ -2068,9 +2178,7 @@ static int features_fused_impl(const isd_fb_plan* fb, const isd_stft_plan* st, c
   ISD_CHECK_ARG(B >= 0 && C >= 1 && C <= (1 << 20), "isd_features_fused: bad shape B=%lld C=%lld", (long long)B,
                 (long long)C);
   ISD_CHECK_ARG(mode >= ISD_BP_MAGNITUDE && mode <= ISD_BP_LOGPOWER, "isd_features_fused: bad mode %d", mode);
-  const bool short_rows = st->n == 64 && st->hop == 32 && st->T <= 2 * kSeg && st->d_dft;
-  const bool long_rows = st->d_blk && st->hop == 64 && st->T <= 64 * 64;
-  if (!short_rows && !long_rows) {
+  if (!fused_short_rows(st) && !fused_long_rows(st)) {
     set_error("isd_features_fused: needs nperseg=64/noverlap=32/T<=1024, or hop 64 with nperseg = 2^a*64 and T<=4096 "
               "(got nperseg=%d hop=%d T=%d)", st->n, st->hop, st->T);
     return ISD_ERR_UNSUPPORTED;
@@ -2079,88 +2187,17 @@ static int features_fused_impl(const isd_fb_plan* fb, const isd_stft_plan* st, c
   int rc = fill_band_args(st, fb->n_bands, klo, khi, all.klo, all.khi, "isd_features_fused");
   if (rc) return rc;
   if (B == 0) return ISD_OK;
-  ISD_CHECK_ARG(B * C <= kMaxRows, "isd_features_fused: too many rows (%lld)", (long long)(B * C));
-  hipStream_t s = (hipStream_t)stream;
-  if (!short_rows) {
-    g_fused_path = 3;
-    // long rows, heavily overlapped frames: filterbank + block sums in one kernel per band set
-    int nbmax = 0;
-    for (int b = 0; b < fb->n_bands; ++b) {
-      const int nbin = all.khi[b] - all.klo[b] + 1;
-      if (nbin < 1 || nbin > 6 || all.klo[b] < 1 || all.khi[b] > st->n / 2 - 1) {
-        set_error("isd_features_fused: band %d needs 1..6 interior bins for the block-sum path (bins %d..%d)", b,
-                  all.klo[b], all.khi[b]);
-        return ISD_ERR_UNSUPPORTED;
-      }
-      if (nbin > nbmax) nbmax = nbin;
-    }
-    const int64_t rows = B * C;
-    int log2_nblk = 0;
-    while ((64 << log2_nblk) < st->n) ++log2_nblk;
-    const int KB = nbmax + 2 <= 4 ? 4 : nbmax + 2 <= 5 ? 5 : nbmax + 2 <= 6 ? 6 : 8;   // band bins + two neighbours
-    const int n_iter = (st->T + 4 * kSeg - 1) / (4 * kSeg);
-    const int vec = ((st->T & 3) == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0);
-    for (int k = 0; k < 2; ++k) {
-      const FbSet& fs = fb->set[k];
-      if (!fs.nb) continue;
-      FusedBands fbnd = {};
-      for (int i = 0; i < fs.nb; ++i) set_band(fbnd, i, all.klo[fb->host_map[k][i]], all.khi[fb->host_map[k][i]]);
-      const size_t lds = sizeof(float2) * ((size_t)KB * 64 + 64) + sizeof(double) * (2 * kMaxSec + 64 * kMaxSec);
-#define ISD_FL_LAUNCH2(VT, K, V)                                                                                      \
-  hipLaunchKernelGGL((fused_long_kernel<VT, K, V>), dim3((unsigned)(cdiv(rows, 8) * 8 * kLongShare)), dim3(64), lds, s, \
-                     fs.d_sec, fs.d_band, fs.d_Q, st->d_blk, x, feat, (int)C, st->T, fs.nb, fb->n_sections, st->J,      \
-                     log2_nblk, st->n / 2, st->scale * st->scale, fbnd, mode, eps, fs.d_map, fb->n_bands, (int)rows, \
-                     out16)
-      // rows of whole 512-sample passes covering all 64 blocks: four rows per wave, no cross-group chain
-      const bool rows4 = vec && st->T % kSeg == 0 && log2_nblk <= 4 && log2_nblk >= 1 && rows4_enabled();
-      const size_t lds4 = sizeof(float2) * ((size_t)4 * KB * 32 + 64) + sizeof(double) * (8 + 64) * (size_t)fb->n_sections;
-      const int share4 = rows4_share(fs.nb);
-#define ISD_FL_LAUNCH4N(VT, K, N)                                                                                     \
-  do {                                                                                                                \
-    ISD_HIP_TRY(hipFuncSetAttribute((const void*)fused_rows4_kernel<VT, K, N>,                                        \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds4));                          \
-    hipLaunchKernelGGL((fused_rows4_kernel<VT, K, N>), dim3((unsigned)(cdiv(cdiv(rows, 4), 8) * 8 * share4)), dim3(64),   \
-                       lds4, s, fs.d_sec, fs.d_band, fs.d_Q, st->d_blk, x, feat, (int)C, st->T, fs.nb, fb->n_sections,  \
-                       st->J, log2_nblk, st->n / 2, st->scale * st->scale, fbnd, mode, eps, fs.d_map, fb->n_bands,      \
-                       (int)rows, share4, out16);                                                                     \
-  } while (0)
-      // fp32 instance with the usual four sections (order-4 Butterworth band-pass): the carried states in registers
-#define ISD_FL_LAUNCH4(VT, K)                                                                           \
-  do {                                                                                                  \
-    if (std::is_same<VT, float>::value && fb->n_sections == 4 && rows4_reg_carry())                     \
-      ISD_FL_LAUNCH4N(VT, K, (std::is_same<VT, float>::value ? 4 : 0));                                 \
-    else ISD_FL_LAUNCH4N(VT, K, 0);                                                                     \
-  } while (0)
-#define ISD_FL_LAUNCH(VT, K)                                        \
-  do {                                                              \
-    if (rows4 && K <= 5) ISD_FL_LAUNCH4(VT, (K <= 5 ? K : 5));      \
-    else if (vec) ISD_FL_LAUNCH2(VT, K, true);                      \
-    else ISD_FL_LAUNCH2(VT, K, false);                              \
-  } while (0)
-      if (k == 0) {
-        if (KB == 4) ISD_FL_LAUNCH(float, 4); else if (KB == 5) ISD_FL_LAUNCH(float, 5);
-        else if (KB == 6) ISD_FL_LAUNCH(float, 6); else ISD_FL_LAUNCH(float, 8);
-      } else {
-        if (KB == 4) ISD_FL_LAUNCH(double, 4); else if (KB == 5) ISD_FL_LAUNCH(double, 5);
-        else if (KB == 6) ISD_FL_LAUNCH(double, 6); else ISD_FL_LAUNCH(double, 8);
-      }
-#undef ISD_FL_LAUNCH2
-#undef ISD_FL_LAUNCH4
-#undef ISD_FL_LAUNCH
-      ISD_LAUNCH_CHECK();
-    }
-    return ISD_OK;
-  }
-  for (int k = 0; k < 2; ++k) {
-    const FbSet& fs = fb->set[k];
-    if (!fs.nb) continue;
-    FusedBands fbnd = {};                                  // the set's bands, in the set's order
-    for (int i = 0; i < fs.nb; ++i) set_band(fbnd, i, all.klo[fb->host_map[k][i]], all.khi[fb->host_map[k][i]]);
-    rc = k ? fused_launch<double>(fb, fs, st, x, feat, B * C, (int)C, fbnd, mode, eps, s, out16)
-           : fused_launch<float>(fb, fs, st, x, feat, B * C, (int)C, fbnd, mode, eps, s, out16);
-    if (rc) return rc;
-  }
-  return ISD_OK;
+  const int64_t R = B * C;
+  ISD_CHECK_ARG(R <= kMaxRows, "isd_features_fused: too many rows (%lld)", (long long)R);
+  Route route[2] = {};
+  for (int k = 0; k < 2 && rc == ISD_OK; ++k)
+    if (fb->set[k].nb) rc = choose_fused_route(fb, k, st, x, R, (int)C, all, mode, route[k]);
+  g_fused_path = !fused_short_rows(st) ? 3 : route[0].family == kSerial ? 2 : 1;
+  for (int k = 0; k < 2 && rc == ISD_OK; ++k)
+    if (fb->set[k].nb)
+      rc = fused_launch(fb, k, st, route[k], x, feat, R, (int)C, set_bands(fb, k, all), mode, eps, (hipStream_t)stream,
+                        out16);
+  return rc;
 }
 
 extern "C" int isd_features_fused(const isd_fb_plan* fb, const isd_stft_plan* st, const float* x, float* feat,
@@ -2182,16 +2219,13 @@ int isd::bandpower_direct(const isd_stft_plan* st, const float* y, float* feat, 
   for (int b = 0; b < nb; ++b) set_band(fbnd, b, klo[b], khi[b]);
   const int64_t items = cdiv(R, 4);
   ISD_CHECK_ARG(R <= kMaxRows, "isd_stft_bandpower: too many rows (%lld)", (long long)R);
-  const int vec = ((st->T & 3) == 0) && ((reinterpret_cast<uintptr_t>(y) & 15) == 0);
+  const int vec = vec_ok(st->T, y);
   const bool full = vec && st->T == kSeg && R % 4 == 0;        // whole waves of whole segments: branch-free loads
-#define ISD_BPD(M, F) hipLaunchKernelGGL((bandpower_direct_kernel<M, F>), dim3((unsigned)items), dim3(64), 0, stream, \
-                                         st->d_dft, y, feat, (int)R, C, st->T, nb, st->J, st->scale * st->scale, fbnd, \
-                                         mode, eps, vec)
-  if (mode == ISD_BP_MAGNITUDE) { if (full) ISD_BPD(true, true); else ISD_BPD(true, false); }
-  else { if (full) ISD_BPD(false, true); else ISD_BPD(false, false); }
-#undef ISD_BPD
-  ISD_LAUNCH_CHECK();
-  return ISD_OK;
+  static constexpr decltype(&bandpower_direct_kernel<false, false>) kern[2][2] = {   // [magnitude][full]
+      {bandpower_direct_kernel<false, false>, bandpower_direct_kernel<false, true>},
+      {bandpower_direct_kernel<true, false>, bandpower_direct_kernel<true, true>}};
+  return launch_lds(kern[mode == ISD_BP_MAGNITUDE][full], dim3((unsigned)items), dim3(64), 0, stream, st->d_dft, y, feat,
+                    (int)R, C, st->T, nb, st->J, st->scale * st->scale, fbnd, mode, eps, vec);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -2487,14 +2521,12 @@ extern "C" int isd_features_backward(const isd_fb_plan* fb, const isd_stft_plan*
       if (!fs.nb) continue;
       const int first = done == 0, last = done == nsets - 1;
       const dim3 grid((unsigned)cdiv(n, 64));
-#define ISD_GRAD(VT) hipLaunchKernelGGL((features_grad_kernel<VT>), grid, dim3(64), 0, s, fs.d_sec, fs.d_ser, fs.d_band, \
-                                        gb[k], fs.nb, fb->n_sections, st->d_win, st->d_tw, x, dfeat, dx, ws, r0, n, RS, \
-                                        (int)C, st->T, st->n, st->hop, st->J, fb->n_bands, nkmax, st->scale, mode, eps, \
-                                        first, last)
-      if (k == 0) ISD_GRAD(float);
-      else ISD_GRAD(double);
-#undef ISD_GRAD
-      ISD_LAUNCH_CHECK();
+static constexpr decltype(&features_grad_kernel<float>) kern[2] = {features_grad_kernel<float>,
+                                                                        features_grad_kernel<double>};
+      const int rc_k = launch_lds(kern[k], grid, dim3(64), 0, s, fs.d_sec, fs.d_ser, fs.d_band, gb[k], fs.nb,
+                                  fb->n_sections, st->d_win, st->d_tw, x, dfeat, dx, ws, r0, n, RS, (int)C, st->T, st->n,
+                                  st->hop, st->J, fb->n_bands, nkmax, st->scale, mode, eps, first, last);
+      if (rc_k) return rc_k;
       ++done;
     }
   }

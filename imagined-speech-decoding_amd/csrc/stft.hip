@@ -359,32 +359,17 @@ extern "C" int isd_stft_bandpower(const isd_stft_plan* p, const float* y, float*
                             (hipStream_t)stream);
   if (p->d_blk && n_bands_in == n_bands) {
     // per-band rows, every band 1..6 interior bins: block sums instead of one FFT per frame
-    int nbmax = 0;
-    bool ok = true;
-    for (int b = 0; b < n_bands; ++b) {
-      const int nbin = ba.khi[b] - ba.klo[b] + 1;
-      if (nbin < 1 || nbin > 6 || ba.klo[b] < 1 || ba.khi[b] > p->n / 2 - 1) ok = false;
-      if (nbin > nbmax) nbmax = nbin;
-    }
+    int KB = 0, log2_nblk = 0;
     const int64_t rows = B * n_bands * C;
-    if (ok && rows <= 0x7fffffffLL) {
-      int log2_nblk = 0;
-      while ((p->hop << log2_nblk) < p->n) ++log2_nblk;
-      const int KB = nbmax + 2 <= 4 ? 4 : nbmax + 2 <= 5 ? 5 : nbmax + 2 <= 6 ? 6 : 8;
-      hipStream_t st = (hipStream_t)stream;
-#define ISD_BS_LAUNCH(H, K)                                                                                        \
-  hipLaunchKernelGGL((bandpower_blocksum_kernel<H, K>), dim3((unsigned)rows), dim3(64), 0, st, p->d_blk, y, feat, rows, \
-                     (int)C, p->T, n_bands, p->J, p->n, log2_nblk, p->scale * p->scale, ba, mode, eps)
-      if (p->hop == 64) {
-        if (KB == 4) ISD_BS_LAUNCH(64, 4); else if (KB == 5) ISD_BS_LAUNCH(64, 5);
-        else if (KB == 6) ISD_BS_LAUNCH(64, 6); else ISD_BS_LAUNCH(64, 8);
-      } else {
-        if (KB == 4) ISD_BS_LAUNCH(32, 4); else if (KB == 5) ISD_BS_LAUNCH(32, 5);
-        else if (KB == 6) ISD_BS_LAUNCH(32, 6); else ISD_BS_LAUNCH(32, 8);
-      }
-#undef ISD_BS_LAUNCH
-      ISD_LAUNCH_CHECK();
-      return ISD_OK;
+    if (blocksum_plan(p, ba.klo, ba.khi, n_bands, &KB, &log2_nblk) < 0 && rows <= 0x7fffffffLL) {
+      static constexpr decltype(&bandpower_blocksum_kernel<64, 4>) kern[2][4] = {   // [hop == 64 ? 0 : 1][KB: 4, 5, 6, 8]
+          {bandpower_blocksum_kernel<64, 4>, bandpower_blocksum_kernel<64, 5>, bandpower_blocksum_kernel<64, 6>,
+           bandpower_blocksum_kernel<64, 8>},
+          {bandpower_blocksum_kernel<32, 4>, bandpower_blocksum_kernel<32, 5>, bandpower_blocksum_kernel<32, 6>,
+           bandpower_blocksum_kernel<32, 8>}};
+      return launch_lds(kern[p->hop == 64 ? 0 : 1][KB == 8 ? 3 : KB - 4], dim3((unsigned)rows), dim3(64), 0,
+                        (hipStream_t)stream, p->d_blk, y, feat, rows, (int)C, p->T, n_bands, p->J, p->n, log2_nblk,
+                        p->scale * p->scale, ba, mode, eps);
     }
   }
   return stft_launch(p, 1, y, feat, B * n_bands_in * C, (int)C, n_bands_in, n_bands, ba, mode, eps,

@@ -90,6 +90,23 @@ __device__ __forceinline__ void blocksum_finish(const float2 (&S)[KB], const flo
   }
 }
 #endif
+// The block-sum band power (stft.hip bandpower_blocksum_kernel, fb.hip fused_long_kernel / fused_rows4_kernel) serves
+// bands of 1..6 interior bins (neither DC nor Nyquist).  Returns -1 and the kernels' two shape parameters -- KB: slots
+// for the widest band's bins and their two Hann neighbours (4, 5, 6 or 8); log2_nblk: log2 of the blocks of `hop`
+// samples per frame -- or the first band outside that rule.
+static inline int blocksum_plan(const isd_stft_plan* st, const int* klo, const int* khi, int n_bands, int* KB,
+                                int* log2_nblk) {
+  int nbmax = 0;
+  for (int b = 0; b < n_bands; ++b) {
+    const int nbin = khi[b] - klo[b] + 1;
+    if (nbin < 1 || nbin > 6 || klo[b] < 1 || khi[b] > st->n / 2 - 1) return b;
+    if (nbin > nbmax) nbmax = nbin;
+  }
+  *log2_nblk = 0;
+  while ((st->hop << *log2_nblk) < st->n) ++*log2_nblk;
+  *KB = nbmax + 2 <= 4 ? 4 : nbmax + 2 <= 5 ? 5 : nbmax + 2 <= 6 ? 6 : 8;
+  return -1;
+}
 // direct-DFT band aggregation (fb.hip) for nperseg 64 / hop 32 / T <= 512, per-band input
 int bandpower_direct(const isd_stft_plan* st, const float* y, float* feat, int64_t R, int C, int nb, const int* klo,
                      const int* khi, int mode, float eps, hipStream_t stream);

@@ -131,7 +131,8 @@ int isd_features_fused_bf16(const isd_fb_plan* fb, const isd_stft_plan* st, cons
  * (diagnostic; the tests that hold the two extractors against each other read it):
  *   0 none yet, 1 sixteen lanes per row (fused_kernel), 2 one row per lane (fused_serial_kernel: rows of whole
  *   32-sample chunks, bands of one or two bins; ISD_FUSED_SERIAL=0 in the environment selects 1), 3 the long-row
- *   block-sum kernels. */
+ *   block-sum kernels.
+ * A plan without fp32 bands reports the family of its fp64 bands: 1 on short rows (fused_kernel), 3 on long rows. */
 int isd_features_fused_last_path(void);
 
 /* Input gradient of the extractor (spec S backward): dx = d<dfeat, feat(x)>/dx for the feature map that

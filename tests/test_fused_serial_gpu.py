@@ -162,3 +162,46 @@ def test_serial_kernel_empty_batch_and_bands_per_wave_overrides(isd):
                 os.environ.pop(k, None)
             else:
                 os.environ[k] = v
+
+
+_X13 = tuple(odsp.BANDS_9) + (("x1", 10.0, 14.0), ("x2", 18.0, 22.0), ("x3", 26.0, 30.0), ("x4", 34.0, 38.0))
+# (case, T, fs, bands, nperseg, noverlap, precision, ISD_FUSED_SERIAL, x one float off a 16-byte boundary, expected path)
+_ROUTES = [
+    ("serial", 512, 256.0, odsp.BANDS_9, 64, 32, "auto", True, False, 2),
+    ("serial switched off", 512, 256.0, odsp.BANDS_9, 64, 32, "auto", False, False, 1),
+    ("rows of 250 samples", 250, 256.0, odsp.BANDS_9, 64, 32, "auto", True, False, 1),
+    ("unaligned x", 512, 256.0, odsp.BANDS_9, 64, 32, "auto", True, True, 1),
+    ("a band of three bins", 512, 256.0, tuple(odsp.BANDS_9[:3]) + (("w", 20.0, 28.0),), 64, 32, "auto", True, False, 1),
+    ("thirteen fp32 bands", 512, 256.0, _X13, 64, 32, "auto", True, False, 1),
+    ("all-fp64 plan after a serial call", 512, 256.0, odsp.BANDS_9, 64, 32, "f64", True, False, 1),
+    ("long rows, whole passes", 1536, 1024.0, odsp.BANDS_40[20:23], 1024, 960, "auto", True, False, 3),
+    ("long rows, ragged", 3000, 1024.0, odsp.BANDS_40[20:23], 1024, 960, "auto", True, False, 3),
+]
+
+
+def test_reported_route_for_a_table_of_small_inputs(isd):
+    """isd_features_fused_last_path() for 2 trials x 3 channels on every side of the extractor's route conditions, each
+    map held against the fp64 oracle at this file's gate so that a wrong route cannot pass by reporting the right number.
+    The all-fp64 plan runs directly after a serial call: it reports 1 (the family of its own launch), not the 2 the
+    previous call left behind."""
+    for case, T, fs, bands, nperseg, noverlap, precision, serial, off, want in _ROUTES:
+        X, _ = odsp.synth_trials(2, 3, T, fs, seed=T)
+        buf = torch.empty(X.size + 4, device="cuda")
+        x = buf[1 if off else 0:][:X.size].view(X.shape)
+        x.copy_(torch.from_numpy(X))
+        assert (x.data_ptr() % 16 != 0) == off, case
+        fx = isd.FeatureExtractor(T, fs, bands, nperseg=nperseg, noverlap=noverlap, precision=precision)
+        assert fx.can_fuse, case
+        if case == "a band of three bins":
+            assert max(hi - lo + 1 for lo, hi in fx.bins) == 3
+        if precision == "f64":
+            assert fx.fb.precision == "f64"
+            _, before = _run(isd.FeatureExtractor(T, fs, bands), x, True)
+            assert before == 2, case
+        elif nperseg == 64:
+            assert fx.fb.precision == "f32", case
+        got, path = _run(fx, x, serial)
+        assert path == want, (case, path)
+        ref = odsp.extract_features_scipy(X, fs=fs, bands=bands, nperseg=nperseg, noverlap=noverlap).astype(np.float64)
+        got = got.cpu().numpy().astype(np.float64)
+        assert (np.abs(got - ref) <= 1e-4 * np.maximum(1.0, np.abs(ref))).all(), case
