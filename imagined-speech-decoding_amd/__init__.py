@@ -15,9 +15,10 @@ from . import csp, data, experiment, explain  # noqa: F401
 from .optim import FusedAdamW  # noqa: F401
 from .classifier import (EEGNetPath, FASTHeadClassifier, FilterbankCNNClassifier,  # noqa: F401
                          FilterbankEEGNetClassifier, GradientBucket, HotPath, NotFittedError, Trainer,
-                         cosine_scheduler, lr_multiplier, smoke_classifier)
+                         TSceptionClassifier, TSceptionPath, cosine_scheduler, lr_multiplier, smoke_classifier)
+from . import nn  # noqa: F401
 
-__all__ = ["FusedAdamW", "FilterbankCNNClassifier", "FilterbankEEGNetClassifier", "FASTHeadClassifier", "EEGNetPath", "NotFittedError", "Trainer", "HotPath", "GradientBucket",
+__all__ = ["TSceptionClassifier", "TSceptionPath", "nn", "FusedAdamW", "FilterbankCNNClassifier", "FilterbankEEGNetClassifier", "FASTHeadClassifier", "EEGNetPath", "NotFittedError", "Trainer", "HotPath", "GradientBucket",
            "cosine_scheduler", "lr_multiplier", "extract_features", "FeatureExtractor", "Filterbank", "Stft", "band_bins", "butter_bandpass_sos",
            "butter_bandpass_resonators", "BANDS_5", "BANDS_9", "BANDS_40", "CLASSES", "ELECTRODES", "ZONES",
            "zone_index_lists", "data", "experiment", "explain", "FirFilter", "filter_data", "fir_design", "CSP", "csp"]

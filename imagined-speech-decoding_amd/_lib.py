@@ -133,6 +133,14 @@ SIGNATURES = {
     "isd_eegnet_sync_block": (_i, [_p, _i64, _i, _i, C.POINTER(_i64), C.POINTER(_i64)]),
     "isd_softmax_ce_workspace_bytes": (_i64, [_i64]),
     "isd_softmax_ce": (_i, [_p, _p, _i, _p, _p, _p, _p, _i64, _i, _i, _f, _p, _p]),
+    "isd_tsception_plan_create": (_i, [C.POINTER(_p), _i, _i, _i, _i, _i, _i, _i, _i, _i]),
+    "isd_tsception_plan_destroy": (_i, [_p]),
+    "isd_tsception_param_count": (_i64, [_p]),
+    "isd_tsception_buffer_count": (_i64, [_p]),
+    "isd_tsception_workspace_bytes": (_i64, [_p, _i64]),
+    "isd_tsception_forward": (_i, [_p, _p, _p, _p, _p, _p, _i64, _i, _f, _f, _f, C.c_uint64, _p]),
+    "isd_tsception_backward": (_i, [_p, _p, _p, _p, _p, _p, _i64, _f, C.c_uint64, _p]),
+    "isd_tsception_temporal_probe": (_i, [_p, _p, _p, _p, _i64, _i, _p]),
 }
 
 _lib = None

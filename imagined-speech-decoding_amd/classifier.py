@@ -15,8 +15,8 @@ import torch.nn as nn
 from . import _lib
 from .constants import BANDS_9, BANDS_40, CLASSES, ELECTRODES, ZONES
 from .features import FeatureExtractor
-from .nn import (FAST, EEGNet_Encoder, FeatureCNN, _FlatParamMixin, _stream, bn_head_backward, bn_head_forward,
-                 bn_head_workspace_floats, fast_config, token_mean_predict)
+from .nn import (FAST, EEGNet_Encoder, FeatureCNN, TSception, _bn_sync_world, _FlatParamMixin, _stream,
+                 bn_head_backward, bn_head_forward, bn_head_workspace_floats, fast_config, token_mean_predict)
 
 
 def cosine_scheduler(base_value, final_value, epochs, niter_per_ep, warmup_epochs=0, start_warmup_value=0):
@@ -311,6 +311,54 @@ class EEGNetPath(HotPath):
         out, dh = self._dense_tail(h, B, 1, call.plan.F, flat, offs, labels, global_batch, gflat)
         if dh is not None:
             bn_head_backward(call, x, dh, gflat, ws, world)
+        return out
+
+
+class TSceptionPath(HotPath):
+    """Autograd-free step of  ``nn.TSception`` -> softmax-CE  (the ``EEGNetPath`` contract: ``dict(loss, logits,
+    pred)``; training mode -- batch statistics, running buffers, dropout -- exactly when gradients are wanted).
+    ``model`` is the ``nn.TSception`` itself: its flat blocks are the step's parameters and gradients.  Single device:
+    with torch.distributed running more than one rank a training step refuses (no synchronised BatchNorm for this
+    model; eval-mode passes need none and run).  At most ``MAX_BATCH`` trials per pass, the largest batch the kernels
+    have been run and checked at: a larger one is refused here, before the library is."""
+    MAX_BATCH = TSception.MAX_BATCH
+
+    def _takes_bf16(self):
+        return False
+
+    def _forward(self, x, labels, global_batch, want_grad):
+        m, L = self.model, _lib.lib()
+        B, _, T = x.shape
+        if B > self.MAX_BATCH:
+            raise ValueError(f"TSception takes at most {self.MAX_BATCH} trials per pass (got {B}): split the batch")
+        dev, st, n_cls = x.device, _stream(), m.num_classes
+        training = want_grad and labels is not None
+        if _bn_sync_world(True, training) > 1:
+            raise NotImplementedError("TSception trains on one device: data parallelism would need synchronised "
+                                      "BatchNorm, which this model does not have")
+        flat = m.flat_params()
+        gflat = m.flat_grads() if want_grad else None
+        with torch.no_grad():
+            call = m._head_call(T, x.dtype, training=training)._replace(theta=flat)
+        ws = self._buf("ts", bn_head_workspace_floats(call, B), dev)
+        lg = self._buf("lg", B * n_cls, dev)
+        bn_head_forward(call, x, lg, ws)
+        logits = torch.empty((B, n_cls), dtype=torch.float32, device=dev)
+        pred = torch.empty((B,), dtype=torch.int64, device=dev)
+        out = {"logits": logits, "pred": pred}
+        if labels is None:
+            _lib.check(L.isd_softmax_ce(lg.data_ptr(), 0, 0, logits.data_ptr(), 0, 0, pred.data_ptr(), B, 1, n_cls, 1.0,
+                                        0, st))
+            return out
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        dlt = self._buf("dlt", B * n_cls, dev)
+        cws = self._buf("cews", int(L.isd_softmax_ce_workspace_bytes(B)) // 4 + 1, dev)
+        _lib.check(L.isd_softmax_ce(lg.data_ptr(), labels.data_ptr(), labels.element_size(), logits.data_ptr(),
+                                    loss.data_ptr(), dlt.data_ptr() if training else 0, pred.data_ptr(), B, 1, n_cls,
+                                    1.0 / float(global_batch or B), cws.data_ptr(), st))
+        out["loss"] = loss
+        if training:
+            bn_head_backward(call, x, dlt, gflat, ws, 1)
         return out
 
 
@@ -797,6 +845,37 @@ class FASTHeadClassifier(_Estimator):
         if missing:
             raise KeyError(f"state_dict lacks hot-path parameters: {missing}")
         return unexpected
+
+
+class TSceptionClassifier(_Estimator):
+    """The reference's deep comparison model on raw trials ``[n, C, T]``: ``nn.TSception`` trained by the estimator's
+    loop (scripts/train_tsception.py without its leave-one-fold-out driver).  fp32 on one device; ``input_gradient``
+    and ``explain`` raise ``NotImplementedError`` (the model has no input gradient)."""
+
+    _param_names = _Estimator._param_names + ("sampling_rate", "num_T", "num_S", "hidden", "dropout_rate", "n_classes")
+
+    def __init__(self, sampling_rate=250.0, num_T=15, num_S=15, hidden=32, dropout_rate=0.5, n_classes=5, **kw):
+        super().__init__(**kw)
+        self.sampling_rate, self.num_T, self.num_S, self.hidden = sampling_rate, num_T, num_S, hidden
+        self.dropout_rate, self.n_classes = dropout_rate, n_classes
+
+    def _n_classes(self):
+        return int(self.n_classes)
+
+    def _build(self, X):
+        return TSception(self.n_classes, (1, int(X.shape[1]), int(X.shape[2])), self.sampling_rate, self.num_T,
+                         self.num_S, self.hidden, self.dropout_rate)
+
+    def decision_function(self, X, batch_size=256):
+        """Logits [n, n_classes]; 256 trials per pass by default (a pass takes at most ``TSceptionPath.MAX_BATCH``
+        trials, and the plan's workspace is about 2.3 MB per trial at 64 x 800: 0.6 GB)."""
+        return super().decision_function(X, batch_size)
+
+    def predict(self, X, batch_size=256):
+        return super().predict(X, batch_size)
+
+    def _differentiable_logits(self, what):
+        raise NotImplementedError(f"{what}: TSception has no input gradient (parameter gradients only)")
 
 
 def smoke_classifier():

@@ -9,6 +9,7 @@
 namespace isd {
 
 void set_error(const char* fmt, ...);
+bool zone_batch_open();             // a zone batch is recording on this thread (zonebatch.hip)
 
 #define ISD_CHECK_ARG(cond, ...)                 \
   do {                                           \

@@ -9,6 +9,7 @@ ZoneRecorder& zone_recorder() {
   static thread_local ZoneRecorder r;
   return r;
 }
+bool zone_batch_open() { return zone_recorder().active; }
 
 std::unordered_map<const void*, hipError_t (*)(int, const ZoneOp* const*, hipStream_t)>& zone_registry() {
   static std::unordered_map<const void*, hipError_t (*)(int, const ZoneOp* const*, hipStream_t)> m;

@@ -233,6 +233,17 @@ class PaperHeadPlan(_lib.Handle):
         self.F = int(feature_dim)
 
 
+class TSceptionPlan(_lib.Handle):
+    """isd_tsception_plan wrapper; ``F`` is the width of the output (the logits)."""
+    _destroy = "isd_tsception_plan_destroy"
+
+    def __init__(self, in_channels, T, taps, num_T, num_S, hidden, n_classes):
+        self._create("isd_tsception_plan_create", int(in_channels), int(T), *(int(k) for k in taps), int(num_T),
+                     int(num_S), int(hidden), int(n_classes))
+        self.n_params = int(_lib.lib().isd_tsception_param_count(self._h))
+        self.F = int(n_classes)
+
+
 class _HeadKind(NamedTuple):
     """What tells the two C-ABI families of BatchNorm heads apart: the entry points by name, and the four things
     their argument lists differ in.  Everything else about driving a head is shared (``bn_head_forward`` /
@@ -264,6 +275,11 @@ _PAPER_KIND = _HeadKind(                                    # HeadConv_Paper_Ver
     "isd_paperhead_forward", "isd_paperhead_forward_stage", "isd_paperhead_backward", "isd_paperhead_backward_stage",
     "isd_paperhead_backward_x", "isd_paperhead_sync_block", "isd_paperhead_sync_block_kind",
     "isd_paperhead_workspace_bytes", stages=5, dropout=False, bf16_x=False, eval_keep=0)
+
+
+_TSCEPTION_KIND = _HeadKind(                                # TSception: single device, parameter gradients only
+    "isd_tsception_forward", None, "isd_tsception_backward", None, None, None, None, "isd_tsception_workspace_bytes",
+    stages=1, dropout=True, bf16_x=False, eval_keep=0)
 
 
 class _HeadCall(NamedTuple):
@@ -410,6 +426,33 @@ class _BNHeadFn(torch.autograd.Function):
             bn_head_backward(ctx.call, x, dout, dflat, ctx.ws, ctx.world, dx)
         ctx.ws = None
         return dx if ctx.needs_input_grad[0] else None, dflat, None
+
+
+class _TSceptionFn(torch.autograd.Function):
+    """TSception's logits; differentiable w.r.t. the parameters only (batch statistics after a train-mode forward,
+    running statistics after an eval-mode one: the library remembers which)."""
+
+    @staticmethod
+    def forward(ctx, x, theta, call):
+        x = _f32c(x, "x")
+        call = call._replace(theta=_f32c(theta, "params"))
+        B = x.shape[0]
+        out = torch.empty((B, call.plan.F), dtype=torch.float32, device=x.device)
+        ws = torch.empty(bn_head_workspace_floats(call, B), dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            bn_head_forward(call, x, out, ws)
+        ctx.call, ctx.ws = call, ws
+        ctx.save_for_backward(x, call.theta)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, flat = ctx.saved_tensors
+        dflat = torch.empty_like(flat)
+        with torch.cuda.device(x.device):
+            bn_head_backward(ctx.call, x, _f32c(dout, "dout"), dflat, ctx.ws, 1)
+        ctx.ws = None
+        return None, dflat, None
 
 
 class _BNZonesFn(torch.autograd.Function):
@@ -1014,6 +1057,102 @@ class HeadConv_Paper_Version(nn.Module, _BNStackMixin):
 
     def forward(self, x):
         return self._run(x)
+
+
+class TSception(nn.Module, _BNStackMixin):
+    """Drop-in for the reference's comparison model ``TSception(num_classes, input_size, sampling_rate, num_T, num_S,
+    hidden, dropout_rate)`` (scripts/train_tsception.py:39-119): same sub-module / parameter / buffer names, so state
+    dicts load strictly in both directions.  ``forward(x[B, C, T] or [B, 1, C, T]) -> logits [B, num_classes]`` in one
+    library pass; parameter gradients only.  fp32, one device: no input gradient, no bfloat16 input, no synchronised
+    BatchNorm, no zone batching, no graph capture, at most ``MAX_BATCH`` trials per pass (each refused by name)."""
+    _kind = _TSCEPTION_KIND
+    sync_bn = False
+    MAX_BATCH = 350          # trials per pass: the largest batch the kernels have been run and checked at
+    _windows = (0.5, 0.25, 0.125)
+    _limits = dict(channels=128, taps=512, filters=16, hidden=64, classes=16)
+
+    @staticmethod
+    def conv_block(i, o, k, s, pool):
+        return nn.Sequential(nn.Conv2d(i, o, kernel_size=k, stride=s), nn.LeakyReLU(), nn.AvgPool2d((1, pool), (1, pool)))
+
+    def __init__(self, num_classes, input_size, sampling_rate, num_T, num_S, hidden, dropout_rate):
+        super().__init__()
+        pool, C, T = 8, int(input_size[1]), int(input_size[2])
+        taps = tuple(int(w * sampling_rate) for w in self._windows)
+        lim = self._limits
+        if C < 2 or C == 3:
+            raise ValueError(f"TSception: {C} channels -- Sception2 must yield exactly two rows (C >= 2, C != 3)")
+        if min(taps) < 1:
+            raise ValueError(f"TSception: a sampling rate of {sampling_rate} leaves the shortest filter without taps")
+        for what, v, hi in (("channels", C, lim["channels"]), ("taps", taps[0], lim["taps"]),
+                            ("num_T", num_T, lim["filters"]), ("num_S", num_S, lim["filters"]),
+                            ("hidden", hidden, lim["hidden"]), ("num_classes", num_classes, lim["classes"])):
+            if not 1 <= v <= hi:
+                raise NotImplementedError(f"TSception: {what}={v} is outside the kernels' envelope [1, {hi}]")
+        if T - taps[0] + 1 < pool:
+            raise ValueError(f"TSception: {T} samples leave fewer than {pool} valid ones for the {taps[0]}-tap filters")
+        pooled = sum((T - k + 1) // pool for k in taps)
+        if pooled // 2 // 4 < 1:
+            raise ValueError(f"TSception: {T} samples pool to {pooled}, too few for AvgPool(2) and the fusion AvgPool(4)")
+        self.in_channels, self.taps, self.num_classes, self.p = C, taps, int(num_classes), dropout_rate
+        self.num_T, self.num_S, self.hidden = int(num_T), int(num_S), int(hidden)
+        self.Tception1 = self.conv_block(1, num_T, (1, taps[0]), 1, pool)
+        self.Tception2 = self.conv_block(1, num_T, (1, taps[1]), 1, pool)
+        self.Tception3 = self.conv_block(1, num_T, (1, taps[2]), 1, pool)
+        self.Sception1 = self.conv_block(num_T, num_S, (int(C), 1), 1, int(pool * 0.25))
+        self.Sception2 = self.conv_block(num_T, num_S, (int(C * 0.5), 1), (int(C * 0.5), 1), int(pool * 0.25))
+        self.fusion_layer = self.conv_block(num_S, num_S, (3, 1), 1, 4)
+        self.BN_t = nn.BatchNorm2d(num_T)
+        self.BN_s = nn.BatchNorm2d(num_S)
+        self.BN_fusion = nn.BatchNorm2d(num_S)
+        self.fc = nn.Sequential(nn.Linear(num_S, hidden), nn.ReLU(), nn.Dropout(dropout_rate),
+                                nn.Linear(hidden, num_classes))
+        self._plans = {}
+        self._calls = 0
+        self._stream_id = _new_dropout_stream()
+
+    def _bns(self):
+        return [self.BN_t, self.BN_s, self.BN_fusion]
+
+    def _ordered_params(self):
+        ps = []
+        for blk in (self.Tception1, self.Tception2, self.Tception3, self.Sception1, self.Sception2, self.fusion_layer):
+            ps += [blk[0].weight, blk[0].bias]
+        for bn in self._bns():
+            ps += [bn.weight, bn.bias]
+        return ps + [self.fc[0].weight, self.fc[0].bias, self.fc[3].weight, self.fc[3].bias]
+
+    def _make_plan(self, T, dtype=torch.float32):
+        return TSceptionPlan(self.in_channels, T, self.taps, self.num_T, self.num_S, self.hidden, self.num_classes)
+
+    def set_seed_counter(self, counter):
+        if counter is not None:
+            raise NotImplementedError("TSception does not take a device-resident dropout counter: its step is not "
+                                      "captured into a HIP graph")
+
+    def _conv_channels(self):
+        return self.in_channels
+
+    def make_path(self):
+        from .classifier import TSceptionPath
+        return TSceptionPath(self)
+
+    def forward(self, x):
+        if x.dim() == 4 and x.shape[1] == 1:
+            x = x[:, 0]
+        if x.dim() != 3:
+            raise ValueError("expected [batch, channels, time] or [batch, 1, channels, time]")
+        if x.shape[1] != self.in_channels:
+            raise ValueError(f"expected {self.in_channels} channels, got {x.shape[1]}")
+        if not x.is_cuda:
+            raise TypeError("x must be a float32 CUDA tensor (the product has no CPU path)")
+        if x.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError("TSception has no input gradient: parameter gradients only (detach x)")
+        if x.shape[0] > self.MAX_BATCH:
+            raise ValueError(f"TSception takes at most {self.MAX_BATCH} trials per pass (got {x.shape[0]}): split "
+                             "the batch")
+        call = self._head_call(x.shape[-1], x.dtype)
+        return _TSceptionFn.apply(x, call.theta, call)
 
 
 class Head(nn.Module, _FlatParamMixin):

@@ -522,6 +522,50 @@ int isd_zone_batch_next(void);
 int isd_zone_batch_launch(void* stream);
 int isd_zone_batch_abort(void);
 
+/* ----------------------------------------------------------------------
+ * TSception, the deep comparison model (replaces the TSception class of scripts/train_tsception.py:39-119):
+ *   x [B][C][T] f32 -> three temporal filter banks (k1, k2, k3 taps; Conv2d(1, num_T, (1, k)) + bias + LeakyReLU(0.01)
+ *   + AvgPool(8), concatenated along time) -> BN_t -> Sception1 (all C rows) and Sception2 (two blocks of C / 2 rows) +
+ *   LeakyReLU + AvgPool(2) -> BN_s -> 3-row fusion conv + LeakyReLU + AvgPool(4) -> BN_fusion -> time mean ->
+ *   Linear(num_S, hidden) + ReLU + Dropout + Linear(hidden, n_classes) -> logits [B][n_classes].
+ * Flat parameter block (named_parameters() order):
+ *   Tception1.0.weight [num_T,1,1,k1] | Tception1.0.bias [num_T] | Tception2.0.* (k2) | Tception3.0.* (k3) |
+ *   Sception1.0.weight [num_S,num_T,C,1] | .bias [num_S] | Sception2.0.weight [num_S,num_T,C/2,1] | .bias |
+ *   fusion_layer.0.weight [num_S,num_S,3,1] | .bias | BN_t.weight | BN_t.bias [num_T] | BN_s.weight | BN_s.bias |
+ *   BN_fusion.weight | BN_fusion.bias [num_S] | fc.0.weight [hidden,num_S] | fc.0.bias | fc.3.weight
+ *   [n_classes,hidden] | fc.3.bias
+ * Buffer block: running_mean / running_var of BN_t, BN_s, BN_fusion (num_T, num_T, num_S, num_S, num_S, num_S floats),
+ *   updated when training (biased variance normalises, unbiased feeds running_var).
+ * Envelope: 2 <= C <= 128, C != 3; 1 <= taps <= 512; T with at least 8 valid samples at every tap count and at least
+ *   one sample after the fusion pool; num_T, num_S <= 16; hidden <= 64; n_classes <= 16.  Anything else:
+ *   ISD_ERR_INVALID from plan_create with the reason in isd_last_error().
+ * B <= 350 trials per pass (the largest batch the kernels have been run and checked at; workspace_bytes, forward and
+ *   backward return ISD_ERR_INVALID above it: split a larger batch).
+ * Dropout is counter-based on (seed, trial, unit): pass the same seed and probability to the backward.  backward:
+ *   parameter gradients only (dparams in the block's layout, overwritten), after a forward on the same workspace --
+ *   batch statistics after training != 0, running statistics otherwise.  No un-pooled temporal map is written in
+ *   either direction; every batch sum is exact or added in a fixed order: a step is bitwise repeatable.
+ * ---------------------------------------------------------------------- */
+typedef struct isd_tsception_plan isd_tsception_plan;
+int isd_tsception_plan_create(isd_tsception_plan** out, int in_channels, int T, int k1, int k2, int k3, int num_T,
+                              int num_S, int hidden, int n_classes);
+int isd_tsception_plan_destroy(isd_tsception_plan* plan);
+int64_t isd_tsception_param_count(const isd_tsception_plan* plan);
+int64_t isd_tsception_buffer_count(const isd_tsception_plan* plan);
+int64_t isd_tsception_workspace_bytes(const isd_tsception_plan* plan, int64_t B);
+int isd_tsception_forward(const isd_tsception_plan* plan, const float* x, const float* params, float* buffers,
+                          float* logits, void* workspace, int64_t B, int training, float momentum, float eps,
+                          float dropout_p, uint64_t seed, void* stream);
+int isd_tsception_backward(const isd_tsception_plan* plan, const float* x, const float* params, const float* dlogits,
+                           float* dparams, void* workspace, int64_t B, float dropout_p, uint64_t seed, void* stream);
+/* Measurement only (tools/bench_tsception.py): the temporal stage's kernels alone on a workspace that a forward and a
+ * backward of the same B have been run on (what they left there is read as the pooled map, its gradient and BN_t's
+ * backward coefficients; any finished pass will do for timing, the values are not meaningful) -- backward == 0 the
+ * fused filter + LeakyReLU + pool pass, else the three weight-gradient kernels (their partial sums are left in the
+ * workspace, not reduced).  Same refusals as forward (batch bound, an open zone batch). */
+int isd_tsception_temporal_probe(const isd_tsception_plan* plan, const float* x, const float* params, void* workspace,
+                                 int64_t B, int backward, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
