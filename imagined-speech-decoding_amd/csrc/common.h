@@ -108,6 +108,11 @@ __device__ __forceinline__ void wave_lds_sync() {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_wave_barrier();
 }
+// The same hand-over between the waves of a workgroup: every wave's LDS operations are complete before any wave goes
+// on.  Like wave_lds_sync() and unlike __syncthreads() it leaves global loads and stores in flight.
+__device__ __forceinline__ void wg_lds_sync() {
+  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+}
 
 // ------------------------------------------------------------------ host side, HIP sources
 // Launches `kernel` with `lds_bytes` of dynamic LDS and checks the launch.  A kernel may use up to 48 KiB without

@@ -1841,14 +1841,16 @@ static size_t conv4_fused_bwd_bf16_lds(int TT) {
 // Tail of the feature classifier (spec-S features: a handful of time steps, one zone) in ONE launch:
 //   A2 -> cnn3 -> cnn4 -> GELU -> mean -> Linear(F, n_cls) -> softmax cross-entropy / argmax
 //   and back: dLogits -> dFeat -> G4 -> (dW4, G3) -> (dW3, G2), dW_fc, db_fc, loss.
-// The layer-wise path spends 19 launches of 5-20 us on these [B, 32, 13] tensors.  Here one WAVE owns an item
-// end to end (T1 <= 16: one 16-column MFMA tile), its tiles live in a wave-private LDS region (no workgroup
-// barrier inside the item loop), the four weight fragment sets are shared by the workgroup in LDS, and the
-// weight gradients accumulate in registers over the wave's items (40 MFMA accumulators), are combined across
-// the 4 waves through LDS in wave order and leave as one slab per workgroup: [dW3 | dW4 | dW_fc | db_fc | loss].
+// The layer-wise path spends 19 launches of 5-20 us on these [B, 32, 13] tensors.  Here one WAVE owns an item's
+// chain end to end (T1 <= 16: one 16-column MFMA tile) on tiles in its own LDS region, the four weight fragment
+// sets are shared by the workgroup in LDS, and the weight gradients accumulate in registers over the items, are
+// combined across the waves through LDS in a fixed order and leave as one slab per workgroup:
+// [dW3 | dW4 | dW_fc | db_fc | loss].  The fp32 kernel runs eight waves, two per SIMD, which 40 weight-gradient
+// accumulators per wave do not allow: partner waves 2p and 2p + 1 split them by filter tile, and each adds both
+// partners' items to its half (two workgroup barriers per round of eight items).
 // ---------------------------------------------------------------------------------------
 struct TailArgs {
-  const void* a2;            // fp32 [items][F][T1], or (BF) bf16 [items][T1][F]
+  const void* a2;            // fp32 [items][F][T1], or (bf16 kernel) bf16 [items][T1][F]
   void* g2;                  // same layout: gradient w.r.t. A2 (training)
   const float* w3;           // frag-ordered cnn3 / cnn4 weights and their transposed + flipped copies (zone 0)
   const float* w4;
@@ -1865,48 +1867,43 @@ struct TailArgs {
   float grad_scale;
 };
 
-// NI items side by side (independent MFMA chains hide the LDS and MFMA latencies of a single wave per SIMD):
-// acc[i][gt] += W[gt] (x) in_i  for one 16-column tile per item (F = 32 input channels, pad 2); the A fragments
-// are shared by the items
-template <int NI>
-__device__ __forceinline__ void tail_conv(const float* __restrict__ wl, const float* const (&in)[NI], int T1, int q,
-                                          int jl, f32x4 (&acc)[NI][2]) {
+// The wave-private tiles [32 rows][T1 <= 16 columns] have a compile-time row of kTailRow = 18 floats: 16 columns and
+// two floats that stay zero, as do the columns from T1 on (the tiles are cleared once, and only columns < T1 are ever
+// written).  A tap that reaches two columns before a row reads the zeros behind the row above it (four zero floats
+// stand in front of the first tile), one that reaches past column T1 - 1 reads zero columns or the row's own two:
+// the convolutions' zero padding and the weight gradients' ragged last K-step come out of LDS, no lane needs a mask,
+// and every LDS offset in the item loop is an instruction immediate next to a handful of per-lane base addresses
+// (a row of T1 floats, a kernel argument, costs about 75 registers of tile addresses that stay live across the item
+// loop: the kernel then does not fit two waves per SIMD).  18 rather than 16 also spreads the weight gradients'
+// column reads (lane = row) over the banks: a row of 16 puts every fourth row on the same one.
+constexpr int kTailRow = 18;
+constexpr int kTailTile = 32 * kTailRow;                   // floats per tile
+
+// acc[gt] += W[gt] (x) in  for one 16-column tile (F = 32 input channels, pad 2).  `in`: the lane's address of tile
+// element (row q, column jl - 2)
+__device__ __forceinline__ void tail_conv(const float* __restrict__ wl, const float* __restrict__ in, f32x4 (&acc)[2]) {
   struct Frag {
     float af[kTaps][2];
-    float bf[NI][kTaps];
+    float bf[kTaps];
   };
-  bool ok[kTaps];
-  int off[kTaps];
-#pragma unroll
-  for (int k = 0; k < kTaps; ++k) {
-    const int idx = jl + k - 2;
-    ok[k] = idx >= 0 && idx < T1;
-    off[k] = ok[k] ? idx : 0;
-  }
   auto load = [&](int cg, Frag& f) {
 #pragma unroll
     for (int k = 0; k < kTaps; ++k) {
       f.af[k][0] = wl[((cg * kTaps + k) * 2 + 0) * 64];
       f.af[k][1] = wl[((cg * kTaps + k) * 2 + 1) * 64];
-#pragma unroll
-      for (int i = 0; i < NI; ++i) {
-        const float v = in[i][(cg * 4 + q) * T1 + off[k]];
-        f.bf[i][k] = ok[k] ? v : 0.f;
-      }
+      f.bf[k] = in[cg * 4 * kTailRow + k];
     }
   };
   auto mma = [&](const Frag& f) {
 #pragma unroll
-    for (int k = 0; k < kTaps; ++k)
-#pragma unroll
-      for (int i = 0; i < NI; ++i) {
-        acc[i][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.af[k][0], f.bf[i][k], acc[i][0], 0, 0, 0);
-        acc[i][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.af[k][1], f.bf[i][k], acc[i][1], 0, 0, 0);
-      }
+    for (int k = 0; k < kTaps; ++k) {
+      acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.af[k][0], f.bf[k], acc[0], 0, 0, 0);
+      acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.af[k][1], f.bf[k], acc[1], 0, 0, 0);
+    }
   };
   Frag f0, f1;
   load(0, f0);
-#pragma unroll 1
+#pragma unroll
   for (int cg = 0; cg < 8; cg += 2) {
     load(cg + 1, f1);
     mma(f0);
@@ -1915,57 +1912,37 @@ __device__ __forceinline__ void tail_conv(const float* __restrict__ wl, const fl
   }
 }
 
-// dW[gt][ct][k] += sum_i sum_t G_i[gt*16 + row][t] * In_i[ct*16 + col][t + k - 2]   (T1 <= 16: four K-steps per item)
-template <int NI>
-__device__ __forceinline__ void tail_wgrad(const float* const (&G)[NI], const float* const (&In)[NI], int T1, int q,
-                                           int jl, f32x4 (&acc)[2][2][kTaps]) {
-#pragma unroll 1
+// dW[ct][k] += sum_t G[row][t] * In[ct*16 + col][t + k - 2]  for ONE filter tile of one item (four K-steps).
+// `g`: the lane's address of G element (filter jl of the tile, step q); `in`: of In element (channel jl, step q - 2)
+__device__ __forceinline__ void tail_wgrad(const float* __restrict__ g, const float* __restrict__ in,
+                                           f32x4 (&acc)[2][kTaps]) {
+#pragma unroll
   for (int s = 0; s < 4; ++s) {
-    const int t = s * 4 + q;
-    const bool okA = t < T1;
-    const int tc = okA ? t : 0;
-    float a[NI][2], b[NI][2][kTaps];
+    const float a = g[s * 4];
+    float b[2][kTaps];
 #pragma unroll
-    for (int i = 0; i < NI; ++i) {
+    for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
-      for (int gt = 0; gt < 2; ++gt) {
-        const float v = G[i][(gt * 16 + jl) * T1 + tc];
-        a[i][gt] = okA ? v : 0.f;
-      }
+      for (int k = 0; k < kTaps; ++k) b[ct][k] = in[ct * 16 * kTailRow + s * 4 + k];
 #pragma unroll
-      for (int ct = 0; ct < 2; ++ct)
+    for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
-        for (int k = 0; k < kTaps; ++k) {
-          const int idx = t + k - 2;
-          const bool in = okA && idx >= 0 && idx < T1;
-          const float v = In[i][(ct * 16 + jl) * T1 + (in ? idx : 0)];
-          b[i][ct][k] = in ? v : 0.f;
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < NI; ++i)
-#pragma unroll
-      for (int gt = 0; gt < 2; ++gt)
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-          for (int k = 0; k < kTaps; ++k)
-            acc[gt][ct][k] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i][gt], b[i][ct][k], acc[gt][ct][k], 0, 0, 0);
+      for (int k = 0; k < kTaps; ++k)
+        acc[ct][k] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b[ct][k], acc[ct][k], 0, 0, 0);
   }
 }
 
-template <bool BF = false>
-__device__ __forceinline__ void tail_store_tile(const f32x4 (&acc)[2], float* __restrict__ tile, int T1, int q, int jl) {
-  if (jl < T1) {
+// the lane's eight values of a [32][16] MFMA result -> a tile.  `dst`: the lane's address of element (row 4 q, column jl)
+__device__ __forceinline__ void tail_store_tile(const f32x4 (&acc)[2], float* __restrict__ dst, bool col_ok) {
+  if (col_ok) {
 #pragma unroll
     for (int gt = 0; gt < 2; ++gt)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) tile[(gt * 16 + 4 * q + r) * T1 + jl] = BF ? bf16_round(acc[gt][r]) : acc[gt][r];
+      for (int r = 0; r < 4; ++r) dst[(gt * 16 + r) * kTailRow] = acc[gt][r];
   }
 }
 
 constexpr int kTailMaxCls = 16;
-constexpr int kTailNI = 1;        // items a wave carries side by side (measured at cfg 2: 1 -> 107 us, 2 -> 116 us: 512 VGPRs + spills)
 
 // Epilogue of the classifier-tail kernels: the waves' weight-gradient accumulators (cnn3 / cnn4: 40 f32x4 per lane),
 // FC gradients and loss shares are summed across the workgroup and leave as ONE slab in natural order
@@ -1980,6 +1957,22 @@ constexpr int kTailNI = 1;        // items a wave carries side by side (measured
 // the one permutation from register layout to natural order happens.
 constexpr int kTailCombV = 43;                            // f32x4 per lane: 20 + 20 accumulators, 2 x FC, {bias, loss}
 constexpr int kTailCombCopy = kTailCombV * 64 * 4;        // floats per copy
+// where slab element e sits inside a copy: float index (v * 64 + lane) * 4 + r
+__device__ __forceinline__ int tail_comb_src(int e, int n34, int o_b, int o_loss) {
+  constexpr int F = 32;
+  if (e < n34) {
+    const int layer = e >= F * F * kTaps, w = e - layer * F * F * kTaps;
+    const int g = w / (F * kTaps), rem = w - g * (F * kTaps), c = rem / kTaps, k = rem - c * kTaps;
+    const int v = ((layer * 2 + (g >> 4)) * 2 + (c >> 4)) * kTaps + k;
+    return (v * 64 + ((g & 15) >> 2) * 16 + (c & 15)) * 4 + (g & 3);
+  }
+  if (e < o_b) {
+    const int f = e - n34, j = f >> 6;                    // flat FC element f = lane + 64 j
+    return ((40 + (j >> 2)) * 64 + (f & 63)) * 4 + (j & 3);
+  }
+  if (e < o_loss) return (42 * 64 + (e - o_b)) * 4;       // bias gradient of class e - o_b: lane = class
+  return (42 * 64) * 4 + 1;                               // loss: lane 0
+}
 // W(layer, gt, ct, k): the lane's accumulator of (layer 0 = cnn3 / 1 = cnn4, filter tile, channel tile, tap)
 template <int NW, int NC, typename WF>
 __device__ __forceinline__ void tail_combine_store(float* __restrict__ smem, int wave, int lane, WF&& W,
@@ -2016,20 +2009,7 @@ __device__ __forceinline__ void tail_combine_store(float* __restrict__ smem, int
   constexpr int n_copy = NW < NC ? NW : NC;
   const int n34 = 2 * F * F * kTaps, o_b = n34 + n_cls * F, o_loss = o_b + n_cls;
   for (int e = threadIdx.x; e < slab_len; e += NW * 64) {
-    int src;                                              // float index inside a copy: (v * 64 + lane) * 4 + r
-    if (e < n34) {
-      const int layer = e >= F * F * kTaps, w = e - layer * F * F * kTaps;
-      const int g = w / (F * kTaps), rem = w - g * (F * kTaps), c = rem / kTaps, k = rem - c * kTaps;
-      const int v = ((layer * 2 + (g >> 4)) * 2 + (c >> 4)) * kTaps + k;
-      src = (v * 64 + ((g & 15) >> 2) * 16 + (c & 15)) * 4 + (g & 3);
-    } else if (e < o_b) {
-      const int f = e - n34, j = f >> 6;                  // flat FC element f = lane + 64 j
-      src = ((40 + (j >> 2)) * 64 + (f & 63)) * 4 + (j & 3);
-    } else if (e < o_loss) {
-      src = (42 * 64 + (e - o_b)) * 4;                    // bias gradient of class e - o_b: lane = class
-    } else {
-      src = (42 * 64) * 4 + 1;                            // loss: lane 0
-    }
+    const int src = tail_comb_src(e, n34, o_b, o_loss);
     float v = smem[src];
 #pragma unroll
     for (int c = 1; c < n_copy; ++c) v += smem[c * kTailCombCopy + src];
@@ -2037,33 +2017,80 @@ __device__ __forceinline__ void tail_combine_store(float* __restrict__ smem, int
   }
 }
 
-// BF (BASELINE config 3): A2 arrives and G2 leaves as bf16 in [item][t][filter] order (the bf16 first-layer kernels),
-// and every activation / activation gradient the tail hands from one layer to the next is rounded to bf16 (the
-// cnn3 / cnn4 fragment copies already are); the products are those of a bf16 MFMA, the accumulation is fp32.
-template <int NW, bool BF>
+// The same for waves that split the accumulators in pairs (the fp32 tail): wave 2p + h holds filter tile h of both
+// layers, summed over the items of both partners, and the even wave the pair's FC / bias / loss shares.  A pair fills
+// one copy exactly as a single wave with all 43 vectors would; pair p stores (p < 2) or adds (p >= 2) into copy p % 2
+// and the slab element is copy 0 + copy 1: the order of tail_combine_store<4, 2>.
+// W(layer, ct, k): the lane's accumulator of (layer, the wave's filter tile, channel tile, tap)
+template <int NW, typename WF>
+__device__ __forceinline__ void tail_combine_store_split(float* __restrict__ smem, int wave, int lane, WF&& W,
+                                                         const float (&accfc)[kTailMaxCls * 32 / 64], float accb,
+                                                         float loss_acc, float* __restrict__ slab, int slab_len,
+                                                         int n_cls) {
+  constexpr int F = 32, NC = 2, NP = NW / 2;
+  static_assert(NW % 2 == 0 && NP % NC == 0, "whole pairs, whole phases");
+  __syncthreads();                                        // the fragment sets and tiles are dead from here on
+  const int pair = wave >> 1, half = wave & 1;
+  f32x4* mine = reinterpret_cast<f32x4*>(smem + (pair % NC) * kTailCombCopy) + lane;
+#pragma unroll
+  for (int ph = 0; ph < NP / NC; ++ph) {
+    if (pair / NC == ph) {
+      auto put = [&](int v, f32x4 x) {
+        if (ph) {
+          const f32x4 o = mine[v * 64];
+          x[0] += o[0]; x[1] += o[1]; x[2] += o[2]; x[3] += o[3];
+        }
+        mine[v * 64] = x;
+      };
+#pragma unroll
+      for (int layer = 0; layer < 2; ++layer)
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+          for (int k = 0; k < kTaps; ++k) put(((layer * 2 + half) * 2 + ct) * kTaps + k, W(layer, ct, k));
+      if (half == 0) {
+        put(40, (f32x4){accfc[0], accfc[1], accfc[2], accfc[3]});
+        put(41, (f32x4){accfc[4], accfc[5], accfc[6], accfc[7]});
+        put(42, (f32x4){accb, loss_acc, 0.f, 0.f});
+      }
+    }
+    __syncthreads();
+  }
+  const int n34 = 2 * F * F * kTaps, o_b = n34 + n_cls * F, o_loss = o_b + n_cls;
+  for (int e = threadIdx.x; e < slab_len; e += NW * 64) {
+    const int src = tail_comb_src(e, n34, o_b, o_loss);
+    slab[e] = smem[src] + smem[kTailCombCopy + src];
+  }
+}
+
+// Eight waves, two per SIMD (a lone wave issues a vector instruction every four cycles and cannot put its LDS and index
+// work under its own MFMAs).  Every wave runs the chain of one item per round; for the weight gradients the partners
+// 2p / 2p + 1 read each other's tiles: wave 2p + h accumulates filter tile h of dW3 and dW4 (20 accumulators instead
+// of 40) over BOTH items, even wave's item first, and the even wave adds both items' FC / bias / loss shares.
+// Item order: with S = gridDim.x * NW / 2, pair p of workgroup b walks items b NW/2 + p + j S, j = 0, 1, 2, ... -- the
+// even wave takes j = 2 R in round R, the odd wave j = 2 R + 1.  So every accumulator sees its items one after the
+// other in ascending j, which is the order in which ONE wave per pair (four waves per workgroup, all 40 accumulators
+// each, the kernel's earlier shape) would add them: the slabs are bit for bit those of that kernel.  A slot past the
+// end recomputes the round's first item with zero dlogits: its G4 and G3 are zero and it adds exactly nothing.
+template <int NW>
 __global__ __launch_bounds__(NW * 64) void featcnn_tail_kernel(TailArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  constexpr int F = 32, NI = kTailNI, WF = 8 * kTaps * 2 * 64;              // 5120 floats per fragment set
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane >> 4, jl = lane & 15;
-  const int T1 = a.T1, n_cls = a.n_cls;
-  const int tile = F * T1, tpad = (tile + 3) & ~3;
+  constexpr int F = 32, WF = 8 * kTaps * 2 * 64;              // 5120 floats per fragment set
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), q = lane >> 4, jl = lane & 15;
+  const int T1 = a.T1, n_cls = a.n_cls, half = wave & 1, pair = wave >> 1;
+  const int tile = F * T1;
+  constexpr int SCR = 80;                                     // floats of per-wave scratch
   float* w3s = smem;                                          // fragment sets, shared by the workgroup
   float* w4s = w3s + WF;
   float* w3ts = w4s + WF;
   float* w4ts = w3ts + WF;
   float* fcs = w4ts + WF;                                     // [n_cls][F] then [n_cls]
-  float* priv = fcs + kTailMaxCls * (F + 1) + wave * NI * (4 * tpad + 64);
-  float *tA2[NI], *tA3[NI], *tG[NI], *tH[NI], *featL[NI], *logL[NI];   // wave-private tiles, per item slot
-#pragma unroll
-  for (int i = 0; i < NI; ++i) {
-    float* base = priv + i * (4 * tpad + 64);
-    tA2[i] = base;
-    tA3[i] = base + tpad;
-    tG[i] = base + 2 * tpad;                                  // G4, later G2
-    tH[i] = base + 3 * tpad;                                  // G3
-    featL[i] = base + 4 * tpad;                               // [32] pooled features, then [16] logits, [16] dlogits
-    logL[i] = featL[i] + 32;
-  }
+  float* featL = fcs + kTailMaxCls * (F + 1) + wave * SCR;    // per wave: [32] pooled features, [16] logits, [16] dlogits,
+  float* logL = featL + 32;                                   // [1] the item's loss term (featL[64])
+  float* tiles = fcs + kTailMaxCls * (F + 1) + NW * SCR + 4;  // four zero floats in front; per wave A2, A3, G4, G3
+  constexpr int tA2 = 0, tA3 = kTailTile, tG4 = 2 * kTailTile, tG3 = 3 * kTailTile, slot = 4 * kTailTile;
+  float* pairT = tiles + (wave & ~1) * slot;                  // the partners' tiles: wave 2p + s at s * slot
+  float* own = pairT + half * slot;
   for (int e = threadIdx.x; e < WF / 4; e += NW * 64) {      // float4: the sets are 16-byte aligned workspace blocks
     reinterpret_cast<float4*>(w3s)[e] = reinterpret_cast<const float4*>(a.w3)[e];
     reinterpret_cast<float4*>(w4s)[e] = reinterpret_cast<const float4*>(a.w4)[e];
@@ -2074,195 +2101,174 @@ __global__ __launch_bounds__(NW * 64) void featcnn_tail_kernel(TailArgs a) {
   }
   for (int e = threadIdx.x; e < n_cls * F; e += NW * 64) fcs[e] = a.fc_w[e];
   for (int e = threadIdx.x; e < n_cls; e += NW * 64) fcs[n_cls * F + e] = a.fc_b[e];
+  for (int e = lane; e < slot / 4; e += 64) reinterpret_cast<float4*>(own)[e] = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (threadIdx.x < 4) tiles[(int)threadIdx.x - 4] = 0.f;
   __syncthreads();
 
-  f32x4 accW4[2][2][kTaps], accW3[2][2][kTaps];
+  // the lane's places in the tiles (kTailRow): every access below is one of these plus a compile-time offset
+  const bool col = jl < T1;
+  const float* cv = own + q * kTailRow + jl - 2;              // conv B operand: (row q, column jl - 2)
+  float* put = own + q * kTailRow + jl;                       // A2 rows as they arrive: (row q, column jl)
+  float* res = own + 4 * q * kTailRow + jl;                   // MFMA result: (row 4 q, column jl)
+  const float* wgG = pairT + (half * 16 + jl) * kTailRow + q; // weight-gradient A operand: (filter jl of tile `half`, step q)
+  const float* wgI = pairT + jl * kTailRow + q - 2;           // weight-gradient B operand: (channel jl, step q - 2)
+
+  f32x4 accW[2][2][kTaps];                                    // [layer: cnn3, cnn4][channel tile][tap] of filter tile `half`
 #pragma unroll
-  for (int g = 0; g < 2; ++g)
+  for (int l = 0; l < 2; ++l)
 #pragma unroll
     for (int c = 0; c < 2; ++c)
 #pragma unroll
-      for (int k = 0; k < kTaps; ++k) {
-        accW4[g][c][k] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        accW3[g][c][k] = (f32x4){0.f, 0.f, 0.f, 0.f};
-      }
+      for (int k = 0; k < kTaps; ++k) accW[l][c][k] = (f32x4){0.f, 0.f, 0.f, 0.f};
   float accfc[kTailMaxCls * F / 64], accb = 0.f, loss_acc = 0.f;   // lane l owns flat fc elements l, l+64, ...
 #pragma unroll
   for (int i = 0; i < kTailMaxCls * F / 64; ++i) accfc[i] = 0.f;
-  const int n4 = tile >> 2;                                   // <= 128: two float4 per lane
   const float inv_t = 1.f / (float)T1;
-  const int64_t stride = (int64_t)gridDim.x * NW * NI;
+  const int64_t stride = (int64_t)gridDim.x * (NW / 2);       // S
+  const int lane_g = q * T1 + jl;                             // (row q, column jl) of an item in global memory
 
-  // item slot i of this wave walks items first + i, first + i + stride, ...; a slot past the end recomputes the
-  // last valid item (uniform control flow for the MFMAs) and contributes nothing
-  for (int64_t first = ((int64_t)blockIdx.x * NW + wave) * NI; first < a.items; first += stride) {
-    int64_t item[NI];
-    bool live[NI];
+  // A2 of the next round travels while this round computes: rows 4 r + q, this lane's column
+  float nx[8];
+  auto fetch = [&](int64_t first) {
+    const int64_t mine = first + pair + half * stride, it = mine < a.items ? mine : first;
+    const float* src = (const float*)a.a2 + it * tile + lane_g;
 #pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      live[i] = first + i < a.items;
-      item[i] = live[i] ? first + i : first;
-      if constexpr (BF) {
-        // [t][32] bf16: piece p = 8 consecutive filters of one step -> the fp32 [filter][t] tile
-        if (lane < 4 * T1) {
-          const uint4 w = reinterpret_cast<const uint4*>((const unsigned short*)a.a2 + item[i] * tile)[lane];
-          const int t = lane >> 2, g0 = (lane & 3) * 8;
-          float* d = tA2[i] + g0 * T1 + t;
-          d[0] = bf16_lo(w.x); d[T1] = bf16_hi(w.x); d[2 * T1] = bf16_lo(w.y); d[3 * T1] = bf16_hi(w.y);
-          d[4 * T1] = bf16_lo(w.z); d[5 * T1] = bf16_hi(w.z); d[6 * T1] = bf16_lo(w.w); d[7 * T1] = bf16_hi(w.w);
-        }
-      } else {
-        const float4* src = reinterpret_cast<const float4*>((const float*)a.a2 + item[i] * tile);
-        float4* dst = reinterpret_cast<float4*>(tA2[i]);
-        if (lane < n4) dst[lane] = src[lane];
-        if (lane + 64 < n4) dst[lane + 64] = src[lane + 64];
-      }
+    for (int r = 0; r < 8; ++r) nx[r] = col ? src[r * 4 * T1] : 0.f;
+  };
+  // the round's first item (pair 0, even wave): the same for every wave, so the trip count is uniform
+  int64_t first = (int64_t)blockIdx.x * (NW / 2);
+  if (first < a.items) fetch(first);
+  for (; first < a.items; first += 2 * stride) {
+    const int64_t mine = first + pair + half * stride;
+    const bool live = mine < a.items, live_odd = first + pair + stride < a.items;
+    const int64_t item = live ? mine : first;
+    if (col) {
+#pragma unroll
+      for (int r = 0; r < 8; ++r) put[tA2 + r * 4 * kTailRow] = nx[r];
     }
+    if (first + 2 * stride < a.items) fetch(first + 2 * stride);
     wave_lds_sync();
-    f32x4 acc[NI][2];
+    f32x4 acc[2];
     auto clear = [&]() {
-#pragma unroll
-      for (int i = 0; i < NI; ++i) {
-        acc[i][0] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        acc[i][1] = (f32x4){0.f, 0.f, 0.f, 0.f};
-      }
+      acc[0] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      acc[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
     };
     clear();
-    tail_conv<NI>(w3s + lane, tA2, T1, q, jl, acc);           // A3
-#pragma unroll
-    for (int i = 0; i < NI; ++i) tail_store_tile<BF>(acc[i], tA3[i], T1, q, jl);
+    tail_conv(w3s + lane, cv + tA2, acc);                     // A3
+    tail_store_tile(acc, res + tA3, col);
     wave_lds_sync();
     clear();
-    tail_conv<NI>(w4s + lane, tA3, T1, q, jl, acc);           // A4 stays in registers
-    if constexpr (BF) {
+    tail_conv(w4s + lane, cv + tA3, acc);                     // A4 stays in registers, then GELU'(A4)
+    // GELU + mean over time: row sums inside each 16-lane row; one erf for GELU and GELU'
 #pragma unroll
-      for (int i = 0; i < NI; ++i)
+    for (int gt = 0; gt < 2; ++gt)
 #pragma unroll
-        for (int gt = 0; gt < 2; ++gt)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) acc[i][gt][r] = bf16_round(acc[i][gt][r]);
-    }
-    // GELU + mean over time: row sums inside each 16-lane row
-#pragma unroll
-    for (int i = 0; i < NI; ++i)
-#pragma unroll
-      for (int gt = 0; gt < 2; ++gt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float sacc = jl < T1 ? gelu_f(acc[i][gt][r]) : 0.f;
-          sacc += row_shr<8>(sacc);
-          sacc += row_shr<4>(sacc);
-          sacc += row_shr<2>(sacc);
-          sacc += row_shr<1>(sacc);
-          if (jl == 15) featL[i][gt * 16 + 4 * q + r] = sacc * inv_t;
-        }
-    wave_lds_sync();
-#pragma unroll
-    for (int i = 0; i < NI; ++i)
-      if (lane < n_cls) {
-        float l = fcs[n_cls * F + lane];
-#pragma unroll
-        for (int g = 0; g < F; ++g) l = fmaf(fcs[lane * F + g], featL[i][g], l);
-        logL[i][lane] = l;
-        if (live[i]) a.logits[item[i] * n_cls + lane] = l;
+      for (int r = 0; r < 4; ++r) {
+        const float u = acc[gt][r];
+        float cdf, ez;
+        gelu_parts(u, cdf, ez);
+        acc[gt][r] = fmaf(u * 0.39894228040143267794f, ez, cdf);
+        float sacc = col ? u * cdf : 0.f;
+        sacc += row_shr<8>(sacc);
+        sacc += row_shr<4>(sacc);
+        sacc += row_shr<2>(sacc);
+        sacc += row_shr<1>(sacc);
+        if (jl == 15) featL[gt * 16 + 4 * q + r] = sacc * inv_t;
       }
     wave_lds_sync();
-    float lse[NI];
-    int yv[NI];
+    if (lane < n_cls) {
+      float l = fcs[n_cls * F + lane];
 #pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      float mx = -INFINITY;
-      int am = 0;
-      for (int c = 0; c < n_cls; ++c) {
-        const float v = logL[i][c];
-        if (v > mx) { mx = v; am = c; }                       // strict '>' keeps the lowest index on ties (torch.argmax)
-      }
-      if (lane == 0 && live[i]) a.pred[item[i]] = am;
-      lse[i] = 0.f;
-      yv[i] = 0;
-      if (a.labels) {
-        float se = 0.f;
-        for (int c = 0; c < n_cls; ++c) se += expf(logL[i][c] - mx);
-        yv[i] = a.label_bytes == 1 ? (int)((const unsigned char*)a.labels)[item[i]]
-                                   : (int)((const long long*)a.labels)[item[i]];
-        lse[i] = mx + logf(se);
-        if (lane == 0 && live[i]) loss_acc += (lse[i] - logL[i][yv[i]]) * a.grad_scale;
-      }
+      for (int g = 0; g < F; ++g) l = fmaf(fcs[lane * F + g], featL[g], l);
+      logL[lane] = l;
+      if (live) a.logits[item * n_cls + lane] = l;
     }
-    if (!a.labels || !a.train) continue;
+    wave_lds_sync();
+    float mx = -INFINITY, lse = 0.f;
+    int am = 0, yv = 0;
+    for (int c = 0; c < n_cls; ++c) {
+      const float v = logL[c];
+      if (v > mx) { mx = v; am = c; }                         // strict '>' keeps the lowest index on ties (torch.argmax)
+    }
+    if (lane == 0 && live) a.pred[item] = am;
+    if (a.labels) {
+      float se = 0.f;
+      for (int c = 0; c < n_cls; ++c) se += expf(logL[c] - mx);
+      yv = a.label_bytes == 1 ? (int)((const unsigned char*)a.labels)[item] : (int)((const long long*)a.labels)[item];
+      lse = mx + logf(se);
+      if (lane == 0) featL[64] = lse - logL[yv];
+    }
+    if (!a.labels) continue;
+    // the even wave adds the pair's loss terms, its own item first (after a workgroup barrier)
+    auto add_loss = [&]() {
+      if (half == 0 && lane == 0) {
+        if (live) loss_acc += featL[64] * a.grad_scale;
+        if (live_odd) loss_acc += featL[SCR + 64] * a.grad_scale;
+      }
+    };
+    if (!a.train) {
+      wg_lds_sync();
+      add_loss();
+      wg_lds_sync();                                          // read before the next round writes the terms again
+      continue;
+    }
     // dlogits -> LDS (zero for a dead slot); dfeat for this lane's 8 filters; G4 = dfeat/T1 * GELU'(A4)
-#pragma unroll
-    for (int i = 0; i < NI; ++i)
-      if (lane < n_cls)
-        logL[i][16 + lane] = live[i] ? (expf(logL[i][lane] - lse[i]) - (lane == yv[i] ? 1.f : 0.f)) * a.grad_scale : 0.f;
+    if (lane < n_cls) logL[16 + lane] = live ? (expf(logL[lane] - lse) - (lane == yv ? 1.f : 0.f)) * a.grad_scale : 0.f;
     wave_lds_sync();
 #pragma unroll
-    for (int i = 0; i < NI; ++i) {
+    for (int gt = 0; gt < 2; ++gt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int g = gt * 16 + 4 * q + r;
+        float d = 0.f;
+        for (int c = 0; c < n_cls; ++c) d = fmaf(fcs[c * F + g], logL[16 + c], d);
+        acc[gt][r] = d * inv_t * acc[gt][r];
+      }
+    tail_store_tile(acc, res + tG4, col);
+    wave_lds_sync();
+    clear();
+    tail_conv(w4ts + lane, cv + tG4, acc);                    // G3
+    tail_store_tile(acc, res + tG3, col);
+    wg_lds_sync();                                            // both partners' A2, A3, G4, G3, features and dlogits are in LDS
+    add_loss();
+    if (half == 0) {
+      // FC gradients of both items: flat element e = lane + 64 j of [n_cls][F]
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const float* fL = featL + s * SCR;
+#pragma unroll
+        for (int j = 0; j < kTailMaxCls * F / 64; ++j) {
+          const int e = lane + 64 * j;
+          if (e < n_cls * F) accfc[j] = fmaf(fL[48 + (e >> 5)], fL[e & 31], accfc[j]);
+        }
+        if (lane < n_cls) accb += fL[48 + lane];
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < 2; ++s) tail_wgrad(wgG + s * slot + tG4, wgI + s * slot + tA3, accW[1]);
+#pragma unroll
+    for (int s = 0; s < 2; ++s) tail_wgrad(wgG + s * slot + tG3, wgI + s * slot + tA2, accW[0]);
+    wg_lds_sync();                                            // the partner has read this wave's tiles: the next round may overwrite them
+    clear();
+    tail_conv(w3ts + lane, cv + tG3, acc);                    // G2 (from the wave's own G3) leaves from the registers
+    if (live && col) {
+      float* dst = (float*)a.g2 + item * tile + 4 * q * T1 + jl;      // (row 4 q, column jl)
 #pragma unroll
       for (int gt = 0; gt < 2; ++gt)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int g = gt * 16 + 4 * q + r;
-          float d = 0.f;
-          for (int c = 0; c < n_cls; ++c) d = fmaf(fcs[c * F + g], logL[i][16 + c], d);
-          acc[i][gt][r] = d * inv_t * gelu_grad_f(acc[i][gt][r]);
-        }
-      tail_store_tile<BF>(acc[i], tG[i], T1, q, jl);
-      // FC gradients: flat element e = lane + 64 j of [n_cls][F]
-#pragma unroll
-      for (int j = 0; j < kTailMaxCls * F / 64; ++j) {
-        const int e = lane + 64 * j;
-        if (e < n_cls * F) accfc[j] = fmaf(logL[i][16 + (e >> 5)], featL[i][e & 31], accfc[j]);
-      }
-      if (lane < n_cls) accb += logL[i][16 + lane];
+        for (int r = 0; r < 4; ++r) dst[(gt * 16 + r) * T1] = acc[gt][r];
     }
-    wave_lds_sync();
-    tail_wgrad<NI>(tG, tA3, T1, q, jl, accW4);
-    clear();
-    tail_conv<NI>(w4ts + lane, tG, T1, q, jl, acc);           // G3
-#pragma unroll
-    for (int i = 0; i < NI; ++i) tail_store_tile<BF>(acc[i], tH[i], T1, q, jl);
-    wave_lds_sync();
-    tail_wgrad<NI>(tH, tA2, T1, q, jl, accW3);
-    clear();
-    tail_conv<NI>(w3ts + lane, tH, T1, q, jl, acc);           // G2
-    wave_lds_sync();                                          // every read of tG (wgrad4, cnn4 data gradient) is done
-#pragma unroll
-    for (int i = 0; i < NI; ++i) tail_store_tile(acc[i], tG[i], T1, q, jl);
-    wave_lds_sync();
-#pragma unroll
-    for (int i = 0; i < NI; ++i)
-      if (live[i]) {
-        if constexpr (BF) {
-          if (lane < 4 * T1) {
-            const int t = lane >> 2, g0 = (lane & 3) * 8;
-            const float* sp = tG[i] + g0 * T1 + t;
-            uint4 w;
-            w.x = bf16_pack(sp[0], sp[T1]); w.y = bf16_pack(sp[2 * T1], sp[3 * T1]);
-            w.z = bf16_pack(sp[4 * T1], sp[5 * T1]); w.w = bf16_pack(sp[6 * T1], sp[7 * T1]);
-            reinterpret_cast<uint4*>((unsigned short*)a.g2 + item[i] * tile)[lane] = w;
-          }
-        } else {
-          float4* dst = reinterpret_cast<float4*>((float*)a.g2 + item[i] * tile);
-          const float4* src = reinterpret_cast<const float4*>(tG[i]);
-          if (lane < n4) dst[lane] = src[lane];
-          if (lane + 64 < n4) dst[lane + 64] = src[lane + 64];
-        }
-      }
-    wave_lds_sync();                                          // tiles are reused by the next items
   }
   if (!a.labels) return;
-  // the waves' accumulators -> one slab per workgroup (tail_combine_store: two copies, two phases)
-  tail_combine_store<NW, 2>(smem, wave, lane,
-                            [&](int layer, int gt, int ct, int k) -> f32x4 { return layer ? accW4[gt][ct][k] : accW3[gt][ct][k]; },
-                            accfc, accb, loss_acc, a.part + (int64_t)blockIdx.x * a.slab, a.slab, n_cls);
+  // the waves' accumulators -> one slab per workgroup
+  tail_combine_store_split<NW>(smem, wave, lane, [&](int layer, int ct, int k) -> f32x4 { return accW[layer][ct][k]; },
+                               accfc, accb, loss_acc, a.part + (int64_t)blockIdx.x * a.slab, a.slab, n_cls);
 }
 
-// dynamic LDS of featcnn_tail_kernel<NW, false> (w3s .. priv at its top): four fragment sets, the FC weights and bias,
-// per wave and item slot four tiles [F][T1] + 64 floats; at least the epilogue's two accumulator copies
-static size_t featcnn_tail_lds(int NW, int F, int T1) {
-  const int tile = (F * T1 + 3) & ~3;
-  const size_t lds = sizeof(float) * (size_t)(4 * 8 * kTaps * 2 * 64 + kTailMaxCls * (F + 1) + NW * kTailNI * (4 * tile + 64) + 16);
+// dynamic LDS of featcnn_tail_kernel<NW> (w3s .. tiles at its top): four fragment sets, the FC weights and bias, 80
+// floats per wave, four zero floats and four tiles per wave; the epilogue's two accumulator copies fit inside
+static size_t featcnn_tail_lds(int NW, int F) {
+  const size_t lds = sizeof(float) * (size_t)(4 * 8 * kTaps * 2 * 64 + kTailMaxCls * (F + 1) + NW * 80 + 4 + NW * 4 * kTailTile);
   return lds < sizeof(float) * 2 * kTailCombCopy ? sizeof(float) * 2 * kTailCombCopy : lds;
 }
 
@@ -3879,10 +3885,10 @@ static int featcnn_step_impl(const isd_conv4_plan* p, const float* x, const floa
     const int64_t b = cdiv(g.items, items_per_wg);
     return b > 256 ? 256 : b < 1 ? 1 : (int)b;
   };
-  constexpr int TNW = 4;                                          // waves per workgroup (measured: 4 -> 107 us; 8 -> 135 us, 256 VGPRs + 133 spills)
+  constexpr int TNW = 8;                                          // waves per workgroup: two per SIMD, partners split the weight gradients
   constexpr int BNW = 8;                                          // bf16 matrix cores: eight waves, an item per wave and round
-  int blocks = tail_blocks(TNW * kTailNI * 2);                    // two rounds of NI items per wave
-  size_t lds = featcnn_tail_lds(TNW, F, g.T1);
+  int blocks = tail_blocks(TNW);                                  // one round of eight items until every CU has a workgroup
+  size_t lds = featcnn_tail_lds(TNW, F);
   ISD_CHECK_ARG(lds <= 160 * 1024 && (int64_t)blocks * t.slab <= g.total - g.o_part, "isd_featcnn_step: workspace");
   if (tap16) {
     blocks = tail_blocks(BNW * 2);
@@ -3890,7 +3896,7 @@ static int featcnn_step_impl(const isd_conv4_plan* p, const float* x, const floa
     ISD_CHECK_ARG(lds <= 160 * 1024 && (int64_t)blocks * t.slab <= g.total - g.o_part, "isd_featcnn_step: workspace");
     rc = launch_lds(featcnn_tail_bf16_kernel<BNW>, dim3(blocks), dim3(BNW * 64), lds, st, t);
   } else {
-    rc = launch_lds(featcnn_tail_kernel<TNW, false>, dim3(blocks), dim3(TNW * 64), lds, st, t);
+    rc = launch_lds(featcnn_tail_kernel<TNW>, dim3(blocks), dim3(TNW * 64), lds, st, t);
   }
   if (rc) return rc;
   if (!labels) return ISD_OK;
