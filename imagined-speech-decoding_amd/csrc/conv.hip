@@ -21,6 +21,7 @@
 namespace isd {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kTaps = 5;
 constexpr int kCK = 32;          // input channels staged per chunk
@@ -428,7 +429,10 @@ static size_t conv5_fwd_lds(int IPW, int CK, int RS, int GT) {
 // double-buffered in LDS and filled by LDS-DMA (global_load_lds_dwordx4), so the copy of chunk c+1 runs under
 // the MFMAs of chunk c.  One workgroup per CU (1 wave per SIMD, 4 column tiles x 2 filter tiles of
 // accumulators per wave); one barrier per chunk: it retires this wave's DMA (vmcnt(0)) for chunk c and, being
-// passed by every wave, frees the buffer chunk c-1 was read from.
+// passed by every wave, frees the buffer chunk c-1 was read from.  Within a full chunk of the 32-filter instances
+// the fragments of channel group cg + 1 are fetched by hand-issued ds_reads in front of the MFMAs of group cg, with
+// a counted wait for the older set in between (FragSet / issue / take below); a ragged last chunk and the 16-filter
+// instances use plain loads, which the compiler prefetches for every second group only.
 // Preconditions (checked on the host): fp32, contiguous zone channels, whole-row windows, cin % 4 == 0,
 // 16-byte aligned rows blocks.
 // ---------------------------------------------------------------------------------------
@@ -506,14 +510,96 @@ __global__ __launch_bounds__(256) void conv5_fwd_glds_kernel(ConvArgs a) {
     float af[kTaps][GT];
     float bf[NT][kTaps];
   };
+  // Full chunks of 32 filters (GT == 2): the eight channel groups are software-pipelined over two fragment sets.  The
+  // ds_reads are issued by hand, because the compiler sinks a prefetch it schedules itself next to its first use and
+  // waits lgkmcnt(0): the reads of group cg + 1 go out in front of the MFMAs of group cg, and the wait in between is
+  // for the older set only (LDS returns in order: lgkmcnt(n), n = the reads issued behind that set; at most 15).
+  // A set is 5 ds_read2st64 (A: taps x two filter tiles, 64 floats apart) and per column tile one ds_read + two
+  // ds_read2 (B: the five tap samples); addresses advance by a group per issue, offsets are immediates.
+  struct FragSet {
+    f32x2 a[kTaps];
+    float b0[NT];
+    f32x2 b12[NT], b34[NT];
+  };
+  constexpr int kSetReads = kTaps + 3 * NT;
+  auto issue = [&](FragSet& f, unsigned& a_addr, unsigned (&b_addr)[NT]) {
+    asm volatile(
+        "ds_read2st64_b32 %0, %5 offset1:1\n\tds_read2st64_b32 %1, %5 offset0:2 offset1:3\n\t"
+        "ds_read2st64_b32 %2, %5 offset0:4 offset1:5\n\tds_read2st64_b32 %3, %5 offset0:6 offset1:7\n\t"
+        "ds_read2st64_b32 %4, %5 offset0:8 offset1:9"
+        : "=&v"(f.a[0]), "=&v"(f.a[1]), "=&v"(f.a[2]), "=&v"(f.a[3]), "=&v"(f.a[4])
+        : "v"(a_addr)
+        : "memory");
+#pragma unroll
+    for (int jj = 0; jj < NT; ++jj)
+      asm volatile("ds_read_b32 %0, %3\n\tds_read2_b32 %1, %3 offset0:1 offset1:2\n\tds_read2_b32 %2, %3 offset0:3 offset1:4"
+                   : "=&v"(f.b0[jj]), "=&v"(f.b12[jj]), "=&v"(f.b34[jj])
+                   : "v"(b_addr[jj])
+                   : "memory");
+    a_addr += kTaps * GT * 64 * 4;
+#pragma unroll
+    for (int jj = 0; jj < NT; ++jj) b_addr[jj] += 4 * a.RS * 4;
+  };
+  // wait until at most `behind` LDS reads are outstanding, then take the set: its registers pass through the
+  // statements, so nothing that uses them is scheduled above the wait
+  auto take = [&](FragSet& f, auto behind) {
+    constexpr int n = decltype(behind)::value > 15 ? 15 : decltype(behind)::value;
+    asm volatile("s_waitcnt lgkmcnt(%5)"
+                 : "+v"(f.a[0]), "+v"(f.a[1]), "+v"(f.a[2]), "+v"(f.a[3]), "+v"(f.a[4])
+                 : "i"(n)
+                 : "memory");
+#pragma unroll
+    for (int jj = 0; jj < NT; ++jj) asm volatile("" : "+v"(f.b0[jj]), "+v"(f.b12[jj]), "+v"(f.b34[jj]));
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  auto mma_set = [&](const FragSet& f) {
+#pragma unroll
+    for (int k = 0; k < kTaps; ++k)
+#pragma unroll
+      for (int jj = 0; jj < NT; ++jj) {
+        const float b = k == 0 ? f.b0[jj] : k == 1 ? f.b12[jj][0] : k == 2 ? f.b12[jj][1] : k == 3 ? f.b34[jj][0] : f.b34[jj][1];
+#pragma unroll
+        for (int g = 0; g < GT; ++g)
+          acc[jj][g] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.a[k][g], b, acc[jj][g], 0, 0, 0);
+      }
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  const unsigned smem_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) float*)smem;
   stage(0, 0);
-  for (int ch = 0; ch < n_chunks; ++ch) {
-    __syncthreads();                                        // drains this wave's DMA of chunk ch; all waves left chunk ch-1
+  int ch = 0;
+  if constexpr (GT == 2) {
+    for (; ch < cin / kCK; ++ch) {                          // the full chunks
+      __syncthreads();                                      // drains this wave's DMA of chunk ch; all waves left chunk ch-1
+      unsigned a_addr = smem_base + (unsigned)(4 + (ch & 1) * buf_len + in_len + lane) * 4;
+      unsigned b_addr[NT];
+#pragma unroll
+      for (int jj = 0; jj < NT; ++jj) b_addr[jj] = smem_base + (unsigned)(4 + (ch & 1) * buf_len + boff[jj]) * 4;
+      FragSet f0, f1;
+      issue(f0, a_addr, b_addr);                            // the one read per chunk that no MFMA covers: the DMA issue does
+#pragma unroll
+      for (int cg = 0; cg < kCK / 4; cg += 2) {
+        issue(f1, a_addr, b_addr);
+        if (cg == 0 && ch + 1 < n_chunks) stage(ch + 1, (ch + 1) & 1);
+        take(f0, std::integral_constant<int, kSetReads>{});
+        mma_set(f0);
+        if (cg + 2 < kCK / 4) {
+          issue(f0, a_addr, b_addr);
+          take(f1, std::integral_constant<int, kSetReads>{});
+        } else {
+          take(f1, std::integral_constant<int, 0>{});
+        }
+        mma_set(f1);
+      }
+    }
+  }
+  for (; ch < n_chunks; ++ch) {
+    __syncthreads();
+    const int c_lo = ch * kCK;
+    const int ncg = ((cin - c_lo) < kCK ? (cin - c_lo) : kCK) / 4;
+    // a ragged last chunk, and 16 filters: fragments of group cg + 1 are loaded in plain C++ around the MFMAs of group cg
     if (ch + 1 < n_chunks) stage(ch + 1, (ch + 1) & 1);
     const float* in_tile = smem + 4 + (ch & 1) * buf_len;
     const float* w_tile = in_tile + in_len + lane;
-    const int c_lo = ch * kCK;
-    const int ncg = ((cin - c_lo) < kCK ? (cin - c_lo) : kCK) / 4;
     auto load = [&](int cg, Frag& f) {
       const float* rowp = in_tile + cg * 4 * a.RS;
 #pragma unroll
@@ -2767,9 +2853,12 @@ static size_t conv5_wgrad_lds(int ips, int64_t per_item) { return sizeof(float) 
 
 // First-layer weight gradient for wide inputs (companion of conv5_fwd_glds_kernel; same preconditions).
 // A workgroup owns 64 input channels (one 16-channel tile per wave, all GT filter tiles) and a range of items;
-// dOut [F][Tout] and the 64 input rows of IPS items are double-buffered in LDS by LDS-DMA; the MFMA loop is
-// branch-free with register-prefetched fragments (K = 4 time steps, one accumulator per tap).  The dbias
-// column (virtual all-ones channel `cin`) rides along in wave 0 of channel group 0.
+// dOut [F][Tout] and the 64 input rows of IPS items are double-buffered in LDS by LDS-DMA (K = 4 time steps, one
+// accumulator per tap).  With Tout >= 4 a stage is one loop of K-step pairs over two fragment sets: the ds_reads of
+// step st + 1 are issued by hand in front of the MFMAs of step st and the wait in between is lgkmcnt(reads of one set),
+// the odd last step is peeled, and lanes past the stage's last (item, step) pair read zero words the DMA never
+// writes instead of being masked after the load.  The dbias column (virtual all-ones channel `cin`, B fragment 1.0f)
+// rides along in wave 0 of channel group 0, which runs its own copy of the loop.
 template <int GT>
 __global__ __launch_bounds__(256) void conv5_wgrad_wide_kernel(WgradArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -2782,15 +2871,15 @@ __global__ __launch_bounds__(256) void conv5_wgrad_wide_kernel(WgradArgs a) {
   const int q = lane >> 4, jl = lane & 15;
   const int cw = (cin - c_base) < 64 ? (cin - c_base) : 64;         // real rows of this channel group (multiple of 4)
   const int c_mine = c_base + wave * 16 + jl;
-  const bool wave_live = c_base + wave * 16 < cin;
-  const bool with_bias = blockIdx.z == 0 && wave == 0;
+  const int wave_s = __builtin_amdgcn_readfirstlane(wave);           // (scalar: the wave's role is a branch, not a mask)
+  const bool wave_live = c_base + wave_s * 16 < cin;
+  const bool with_bias = blockIdx.z == 0 && wave_s == 0;
   const int do_len = a.F * a.Tout, in_len = 64 * a.Tin;             // per item (in_len: stride; cw*Tin are filled)
   const int item_len = (do_len + in_len + 3) & ~3;
   const int buf_len = a.IPS * item_len + 32;
   const int64_t i_lo = (int64_t)blockIdx.x * a.items_per_wg;
   const int64_t i_hi = (i_lo + a.items_per_wg) < a.items ? (i_lo + a.items_per_wg) : a.items;
   const int chan0 = a.chan_idx[zd.idx_off];
-  const int nks = (a.Tout + 3) >> 2;
   // the tail of both buffers is read (masked) by the last rows' junk columns: keep it finite
   for (int e = threadIdx.x; e < 2 * buf_len + 8; e += 256) smem[e] = 0.f;
   __syncthreads();
@@ -2820,34 +2909,96 @@ __global__ __launch_bounds__(256) void conv5_wgrad_wide_kernel(WgradArgs a) {
   };
   const int a_off = jl * a.Tout + q;                                   // dOut[g = jl (+16 gt)][t0 + q]
   const int b_off = do_len + (wave * 16 + jl) * a.Tin + q;             // In[c][t0 + q + k]
-  int s = 0;
-  if (i_lo < i_hi) stage(i_lo, 0);
-  for (int64_t is = i_lo; is < i_hi; is += a.IPS, s ^= 1) {
-    __syncthreads();                                                   // DMA of this stage retired; previous stage consumed
-    if (is + a.IPS < i_hi) stage(is + a.IPS, s ^ 1);
-    if (!wave_live) continue;
-    const float* buf = smem + s * buf_len;
-    const int n_it = (int)((i_hi - is) < a.IPS ? (i_hi - is) : a.IPS);
-    // The reduction runs over (item, output step) pairs four at a time.  With Tout >= 4 the stage's pairs are taken
-    // back to back -- K index 4 st + q is step f % Tout of item f / Tout, kept per lane and advanced by four per load
-    // (the loads are issued in step order) -- so 13 output steps cost 13/4 K steps per item instead of 4.
-    const bool packed = a.Tout >= 4;
-    const int n_step = packed ? (n_it * a.Tout + 3) >> 2 : n_it * nks;
-    int p_ii = 0, p_t = q;                                              // this lane's next (item, step)
-    auto load = [&](int st, Frag& f) {
-      int ii, t0;
-      bool ok;
-      if (packed) {
-        ii = p_ii; t0 = p_t - q;                                        // (a_off / b_off carry the + q)
-        ok = p_ii < n_it;
-        if (!ok) { ii = 0; t0 = -q; }                                   // past the stage's last pair: any valid address
-        p_t += 4;
-        if (p_t >= a.Tout) { p_t -= a.Tout; ++p_ii; }
-      } else {
-        ii = st / nks; t0 = (st - ii * nks) * 4;
-        ok = t0 + q < a.Tout;
+  // The packed loop (Tout >= 4): K index 4 st + q of a stage is step f % Tout of item f / Tout, f = 4 st + q, kept per
+  // lane as three byte addresses that advance by four steps per issue.  A set is GT ds_read (dOut) + two ds_read2 and
+  // one ds_read (the five tap samples).
+  struct FragSet {
+    float af[GT];
+    f32x2 b01, b23;
+    float b4;
+  };
+  constexpr int kSetReads = GT + 3;
+  const unsigned smem_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) float*)smem;
+  const unsigned zero_addr = smem_base + (unsigned)(2 * buf_len) * 4;   // 8 floats behind the buffers: cleared above, never staged
+  auto run_packed = [&](auto bias, int sbuf, int n_it) {
+    const unsigned buf_addr = smem_base + (unsigned)(sbuf * buf_len) * 4;
+    unsigned a0 = buf_addr + (unsigned)a_off * 4, a1 = a0 + (unsigned)(16 * a.Tout) * 4, b = buf_addr + (unsigned)b_off * 4;
+    int p_ii = 0, p_t = q;                                             // this lane's next (item, step)
+    const unsigned wrap = (unsigned)(item_len - a.Tout + 4) * 4;
+    auto issue = [&](FragSet& f) {
+      const bool dead = p_ii >= n_it;                                  // past the stage's last pair: zeros for A and B
+      const unsigned ra0 = dead ? zero_addr : a0, ra1 = dead ? zero_addr : a1, rb = dead ? zero_addr : b;
+      if constexpr (GT == 2)
+        asm volatile("ds_read_b32 %0, %5\n\tds_read_b32 %1, %6\n\tds_read2_b32 %2, %7 offset1:1\n\t"
+                     "ds_read2_b32 %3, %7 offset0:2 offset1:3\n\tds_read_b32 %4, %7 offset:16"
+                     : "=&v"(f.af[0]), "=&v"(f.af[GT - 1]), "=&v"(f.b01), "=&v"(f.b23), "=&v"(f.b4)
+                     : "v"(ra0), "v"(ra1), "v"(rb)
+                     : "memory");
+      else
+        asm volatile("ds_read_b32 %0, %4\n\tds_read2_b32 %1, %5 offset1:1\n\t"
+                     "ds_read2_b32 %2, %5 offset0:2 offset1:3\n\tds_read_b32 %3, %5 offset:16"
+                     : "=&v"(f.af[0]), "=&v"(f.b01), "=&v"(f.b23), "=&v"(f.b4)
+                     : "v"(ra0), "v"(rb)
+                     : "memory");
+      p_t += 4;
+      const bool w = p_t >= a.Tout;
+      const unsigned d = w ? wrap : 16u;
+      a0 += d; a1 += d; b += d;
+      if (w) { p_t -= a.Tout; ++p_ii; }
+    };
+    // wait until at most `behind` LDS reads are outstanding, then take the set (its registers pass through the statement)
+    auto take = [&](FragSet& f, auto behind) {
+      if constexpr (GT == 2)
+        asm volatile("s_waitcnt lgkmcnt(%5)" : "+v"(f.af[0]), "+v"(f.af[GT - 1]), "+v"(f.b01), "+v"(f.b23), "+v"(f.b4)
+                     : "i"(decltype(behind)::value) : "memory");
+      else
+        asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(f.af[0]), "+v"(f.b01), "+v"(f.b23), "+v"(f.b4)
+                     : "i"(decltype(behind)::value) : "memory");
+      __builtin_amdgcn_sched_barrier(0);
+    };
+    auto mma_set = [&](const FragSet& f) {
+      const float bf[kTaps] = {f.b01[0], f.b01[1], f.b23[0], f.b23[1], f.b4};
+#pragma unroll
+      for (int k = 0; k < kTaps; ++k)
+#pragma unroll
+        for (int g = 0; g < GT; ++g) acc[g][k] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.af[g], bf[k], acc[g][k], 0, 0, 0);
+      if constexpr (decltype(bias)::value) {
+#pragma unroll
+        for (int g = 0; g < GT; ++g) accb[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.af[g], 1.f, accb[g], 0, 0, 0);
       }
-      const float* ib = buf + ii * item_len + t0;
+      __builtin_amdgcn_sched_barrier(0);
+    };
+    const int n_step = (n_it * a.Tout + 3) >> 2;
+    const std::integral_constant<int, kSetReads> one_set;
+    const std::integral_constant<int, 0> none;
+    FragSet f0, f1;
+    issue(f0);
+    int st = 1;
+    for (; st + 1 < n_step; st += 2) {                                 // f0 holds step st - 1; steps st and st + 1 exist
+      issue(f1);
+      take(f0, one_set);
+      mma_set(f0);
+      issue(f0);
+      take(f1, one_set);
+      mma_set(f1);
+    }
+    if (st < n_step) {                                                 // two steps left
+      issue(f1);
+      take(f0, one_set);
+      mma_set(f0);
+      take(f1, none);
+      mma_set(f1);
+    } else {                                                           // the odd last step
+      take(f0, none);
+      mma_set(f0);
+    }
+  };
+  // Tout < 4: one K step per item, masked after the load (plain C++ loads, the compiler's schedule)
+  auto run_single = [&](int sbuf, int n_it) {
+    const float* buf = smem + sbuf * buf_len;
+    auto load = [&](int ii, Frag& f) {
+      const bool ok = q < a.Tout;
+      const float* ib = buf + ii * item_len;
 #pragma unroll
       for (int g = 0; g < GT; ++g) {
         const float v = ib[a_off + g * 16 * a.Tout];
@@ -2872,15 +3023,34 @@ __global__ __launch_bounds__(256) void conv5_wgrad_wide_kernel(WgradArgs a) {
     };
     Frag f0, f1;
     load(0, f0);
-    for (int st = 0; st < n_step; st += 2) {
-      if (st + 1 < n_step) load(st + 1, f1);
+    for (int st = 0; st < n_it; st += 2) {
+      if (st + 1 < n_it) load(st + 1, f1);
       mma(f0);
-      if (st + 1 < n_step) {
-        if (st + 2 < n_step) load(st + 2, f0);
+      if (st + 1 < n_it) {
+        if (st + 2 < n_it) load(st + 2, f0);
         mma(f1);
       }
     }
-  }
+  };
+  // The reduction runs over (item, output step) pairs four at a time.  With Tout >= 4 a stage's pairs are taken back
+  // to back, so 13 output steps cost 13/4 K steps per item instead of 4.  Each kind of wave runs its own copy of the
+  // stage loop (mode 0: Tout < 4, 1: packed, 2: packed with the dbias column, 3: a wave past the last channel, which
+  // only stages), so the accumulators stay in one register set and no branch sits between the MFMA groups.
+  auto run_stages = [&](auto mode) {
+    int s = 0;
+    if (i_lo < i_hi) stage(i_lo, 0);
+    for (int64_t is = i_lo; is < i_hi; is += a.IPS, s ^= 1) {
+      __syncthreads();                                                 // DMA of this stage retired; previous stage consumed
+      if (is + a.IPS < i_hi) stage(is + a.IPS, s ^ 1);
+      const int n_it = (int)((i_hi - is) < a.IPS ? (i_hi - is) : a.IPS);
+      if constexpr (decltype(mode)::value == 0) run_single(s, n_it);
+      else if constexpr (decltype(mode)::value != 3) run_packed(std::integral_constant<bool, decltype(mode)::value == 2>{}, s, n_it);
+    }
+  };
+  if (!wave_live) run_stages(std::integral_constant<int, 3>{});
+  else if (a.Tout < 4) run_stages(std::integral_constant<int, 0>{});
+  else if (!with_bias) run_stages(std::integral_constant<int, 1>{});
+  else run_stages(std::integral_constant<int, 2>{});
   if (!wave_live) return;
   float* slab = a.part + (int64_t)blockIdx.x * a.slab_size + zd.wg_off;
 #pragma unroll
