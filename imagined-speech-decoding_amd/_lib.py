@@ -68,6 +68,11 @@ SIGNATURES = {
     "isd_cov_group_mean": (_i, [_p, _i, _p, _p, _i, _p, _i64, _i, _i, _p]),
     "isd_csp_power_f32": (_i, [_p, _p, _p, _i64, _i, _i, _i, _i, _p]),
     "isd_csp_power_f64": (_i, [_p, _p, _p, _i64, _i, _i, _i, _i, _p]),
+    "isd_ica_step_work_bytes": (_i64, [_i64, _i, _i, _i, _i]),
+    "isd_ica_step_f32": (_i, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i, _i, _i, _p]),
+    "isd_ica_step_f64": (_i, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i, _i, _i, _p]),
+    "isd_spatial_apply_f32": (_i, [_p, _p, _p, _p, _i64, _i, _i, _i, _p]),
+    "isd_spatial_apply_f64": (_i, [_p, _p, _p, _p, _i64, _i, _i, _i, _p]),
     "isd_conv4_plan_create": (_i, [C.POINTER(_p), _i, _i, _pi, _pi, _i, _i, _i, _i]),
     "isd_conv4_plan_destroy": (_i, [_p]),
     "isd_conv4_plan_set_activation_dtype": (_i, [_p, _i]),

@@ -218,6 +218,33 @@ int isd_csp_power_f64(const double* x, const double* w, double* out, int64_t n, 
                       void* stream);
 
 /* ------------------------------------------------------------------------
+ * Independent component analysis: the data-sized steps of parallel FastICA with the logcosh contrast (alpha = 1), the
+ * default method of the reference's artifact removal
+ *   ICA(n_components, method='fastica').fit(epochs); ica.apply(epochs)   scripts/artifact_analysis.py:61
+ * (mne.preprocessing.ICA -> sklearn.decomposition.FastICA).  Centring, whitening and the symmetric decorrelation work
+ * on [m][C] matrices and are host work: isd_amd.ica.fastica.  All pointers are device memory; no call synchronises
+ * with the host; 1 <= C <= 128, T >= 1.
+ *
+ * ica_step:       x [n][C][T], U [m][C], b [m] (1 <= m <= 64, same dtype) -> P [m][C], s [m], q [m], all double:
+ *                 with G_i = tanh(U x_i - b) per sample,  P = sum_i G_i x_i^T,  s = sum G,  q = sum (1 - G^2), over
+ *                 all n * T samples.  One pass over x; neither the projection nor G is written.  The _f32 entry does
+ *                 the per-sample arithmetic and each workgroup's partial sums in fp32 on the fp32-input matrix cores,
+ *                 the _f64 entry in fp64; the partials are then added in fp64 in a fixed order (no atomics): bitwise
+ *                 repeatable.  `work`: isd_ica_step_work_bytes(n, C, T, m, is_f64) bytes of scratch (-1 on a bad shape).
+ * spatial_apply:  x [n][C][T], M [R][C] (1 <= R <= 128), bias [R] or NULL -> out [n][R][T],
+ *                 out_i = M x_i + bias[:, None].  out must not overlap x.
+ * ---------------------------------------------------------------------- */
+int64_t isd_ica_step_work_bytes(int64_t n, int C, int T, int m, int is_f64);
+int isd_ica_step_f32(const float* x, const float* U, const float* b, double* P, double* s, double* q, void* work,
+                     int64_t work_bytes, int64_t n, int C, int T, int m, void* stream);
+int isd_ica_step_f64(const double* x, const double* U, const double* b, double* P, double* s, double* q, void* work,
+                     int64_t work_bytes, int64_t n, int C, int T, int m, void* stream);
+int isd_spatial_apply_f32(const float* x, const float* M, const float* bias, float* out, int64_t n, int C, int T,
+                          int R, void* stream);
+int isd_spatial_apply_f64(const double* x, const double* M, const double* bias, double* out, int64_t n, int C, int T,
+                          int R, void* stream);
+
+/* ------------------------------------------------------------------------
  * Zone-wise Conv4Layers stack over sliding windows: the reference's
  *   FAST.forward_head   src/fast/models/fast.py:242-252  (unfold window_len / slide_step)
  *   Head.forward        src/fast/models/fast.py:209-210  (zone gather, one encoder per zone, stack)
