@@ -103,6 +103,7 @@ SIGNATURES = {
     "isd_linear_backward": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _i, _i, _p]),
     "isd_eegnet_plan_create": (_i, [C.POINTER(_p), _i, _i, _i, _i]),
     "isd_featcnn_supported": (_i, [_p, _i64, _i64, _i]),
+    "isd_first_layer_last_path": (_i, []),
     "isd_featcnn_step": (_i, [_p, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _i64, _i64, _i, _f, _p]),
     "isd_featcnn_step_bf16": (_i, [_p, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _i64, _i64, _i, _f, _p]),
     "isd_paperhead_plan_create": (_i, [C.POINTER(_p), _i, _i, _i]),

@@ -230,6 +230,77 @@ __device__ __forceinline__ void glds_copy16_strided(const float* __restrict__ sr
   }
 }
 
+// LDS-DMA as straight-line code (the wide first-layer kernels): N pieces of 1 KiB, the first OFF
+// bytes in.  `base` (source) and `lds` (destination byte address) are wave-uniform and stay in scalar registers, `voff`
+// is the lane's byte offset into the source (16 * lane, plus whatever the caller advances it by), and the piece is an
+// immediate offset, which the instruction applies to both sides.  Issued from inline asm like dma16_async below: the
+// compiler neither tracks it against later LDS accesses nor wraps it in a loop of its own; the caller retires it with
+// s_waitcnt vmcnt(0) in front of its barrier.  (s_nop 3: M0 needs one wait state, a scalar base that a VALU wrote five.)
+template <int N, int OFF>
+__device__ __forceinline__ void glds_lines(unsigned lds, const void* base, unsigned voff) {
+  static_assert(N >= 1 && N <= 4 && OFF >= 0 && OFF + (N - 1) * 1024 < 4096, "13-bit signed immediate offset");
+  if constexpr (N == 1)
+    asm volatile("s_mov_b32 m0, %0\n\ts_nop 3\n\tglobal_load_lds_dwordx4 %1, %2 offset:%3"
+                 :: "s"(lds), "v"(voff), "s"(base), "i"(OFF) : "memory", "m0");
+  else if constexpr (N == 2)
+    asm volatile("s_mov_b32 m0, %0\n\ts_nop 3\n\tglobal_load_lds_dwordx4 %1, %2 offset:%3\n\t"
+                 "global_load_lds_dwordx4 %1, %2 offset:%4"
+                 :: "s"(lds), "v"(voff), "s"(base), "i"(OFF), "i"(OFF + 1024) : "memory", "m0");
+  else if constexpr (N == 3)
+    asm volatile("s_mov_b32 m0, %0\n\ts_nop 3\n\tglobal_load_lds_dwordx4 %1, %2 offset:%3\n\t"
+                 "global_load_lds_dwordx4 %1, %2 offset:%4\n\tglobal_load_lds_dwordx4 %1, %2 offset:%5"
+                 :: "s"(lds), "v"(voff), "s"(base), "i"(OFF), "i"(OFF + 1024), "i"(OFF + 2048) : "memory", "m0");
+  else
+    asm volatile("s_mov_b32 m0, %0\n\ts_nop 3\n\tglobal_load_lds_dwordx4 %1, %2 offset:%3\n\t"
+                 "global_load_lds_dwordx4 %1, %2 offset:%4\n\tglobal_load_lds_dwordx4 %1, %2 offset:%5\n\t"
+                 "global_load_lds_dwordx4 %1, %2 offset:%6"
+                 :: "s"(lds), "v"(voff), "s"(base), "i"(OFF), "i"(OFF + 1024), "i"(OFF + 2048), "i"(OFF + 3072)
+                 : "memory", "m0");
+}
+
+// NF whole pieces and the lanes of `tail` (a lane mask, wave-uniform) of one more, as one statement: the partial piece
+// is issued under exec & tail, which the statement restores (an empty mask issues nothing).
+template <int NF>
+__device__ __forceinline__ void glds_item(uint64_t tail, unsigned lds, const void* base, unsigned voff) {
+  static_assert(NF >= 0 && NF <= 3, "13-bit signed immediate offset");
+  uint64_t keep;
+  if constexpr (NF == 0)
+    asm volatile("s_mov_b32 m0, %1\n\ts_nop 3\n\ts_and_saveexec_b64 %0, %4\n\t"
+                 "global_load_lds_dwordx4 %2, %3\n\ts_mov_b64 exec, %0"
+                 : "=&s"(keep) : "s"(lds), "v"(voff), "s"(base), "s"(tail) : "memory", "m0", "scc");
+  else if constexpr (NF == 1)
+    asm volatile("s_mov_b32 m0, %1\n\ts_nop 3\n\tglobal_load_lds_dwordx4 %2, %3\n\ts_and_saveexec_b64 %0, %4\n\t"
+                 "global_load_lds_dwordx4 %2, %3 offset:1024\n\ts_mov_b64 exec, %0"
+                 : "=&s"(keep) : "s"(lds), "v"(voff), "s"(base), "s"(tail) : "memory", "m0", "scc");
+  else if constexpr (NF == 2)
+    asm volatile("s_mov_b32 m0, %1\n\ts_nop 3\n\tglobal_load_lds_dwordx4 %2, %3\n\t"
+                 "global_load_lds_dwordx4 %2, %3 offset:1024\n\ts_and_saveexec_b64 %0, %4\n\t"
+                 "global_load_lds_dwordx4 %2, %3 offset:2048\n\ts_mov_b64 exec, %0"
+                 : "=&s"(keep) : "s"(lds), "v"(voff), "s"(base), "s"(tail) : "memory", "m0", "scc");
+  else
+    asm volatile("s_mov_b32 m0, %1\n\ts_nop 3\n\tglobal_load_lds_dwordx4 %2, %3\n\t"
+                 "global_load_lds_dwordx4 %2, %3 offset:1024\n\tglobal_load_lds_dwordx4 %2, %3 offset:2048\n\t"
+                 "s_and_saveexec_b64 %0, %4\n\tglobal_load_lds_dwordx4 %2, %3 offset:3072\n\ts_mov_b64 exec, %0"
+                 : "=&s"(keep) : "s"(lds), "v"(voff), "s"(base), "s"(tail) : "memory", "m0", "scc");
+}
+
+// The same copy as glds_copy16 for at most 511 float4 (n_full = n4 >> 6 whole pieces, tail = the lanes below n4 & 63).
+// The wave-uniform n_full is taken apart into 4 + 2 + 1 pieces behind three scalar branches and the two addresses
+// move on by scalar adds.
+__device__ __forceinline__ void glds_run(int n_full, uint64_t tail, unsigned lds, const char* base, unsigned voff) {
+  if (n_full & 4) {
+    glds_lines<4, 0>(lds, base, voff);
+    lds += 4096; base += 4096;
+  }
+  if (n_full & 2) {
+    glds_lines<2, 0>(lds, base, voff);
+    lds += 2048; base += 2048;
+  }
+  if (n_full & 1) glds_item<1>(tail, lds, base, voff);
+  else glds_item<0>(tail, lds, base, voff);
+}
+constexpr int kGldsRunMax4 = 511;
+
 // ---------------------------------------------------------------------------------------
 // Forward convolution (also used as dgrad with transposed weights).
 // ---------------------------------------------------------------------------------------
@@ -471,6 +542,46 @@ __global__ __launch_bounds__(256) void conv5_fwd_glds_kernel(ConvArgs a) {
     if (w0 < wlen4)
       glds_copy16(wbase + (int64_t)ch * (kCK / 4) * kTaps * GT * 64 + (int64_t)w0 * 4, w_tile + w0 * 4, w1 - w0, lane);
   };
+  // The same staging of a FULL chunk as straight-line code (glds_item, glds_lines).  What `stage` works out per chunk and per piece
+  // -- source addresses, the wave's share of the weight chunk, the piece loops -- is wave-uniform and the same for every
+  // chunk, so it is computed here once and kept in scalar registers: for the wave's first item the source base of chunk
+  // 0 and the LDS address inside buffer 0 (it stages items wave, wave + 4, ..., a constant step apart on both sides),
+  // and the same pair for its quarter of the weight chunk (20 pieces, 5 a wave).  A chunk moves the two lane offsets on
+  // and picks the buffer.  Taken when an item's chunk is at most 4 pieces (17 frames: 2 and 8 lanes of a third); other
+  // shapes, the ragged last chunk, chunk 0 and the 16-filter instances use `stage`.
+  const unsigned smem_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) float*)smem;
+  const int wave_s = __builtin_amdgcn_readfirstlane(wave);
+  const int cnt4_full = (kCK * a.Tin) >> 2;
+  const bool fast = GT == 2 && cnt4_full < 256;
+  const int n_mine = n_items > wave_s ? (n_items - wave_s + 3) >> 2 : 0;
+  const uint64_t tail_lanes = __builtin_amdgcn_ballot_w64(lane < (cnt4_full & 63));
+  const char* const it_src = (const char*)a.in + ((item0 + wave_s) * a.Ctot + chan0) * (int64_t)a.Tx * 4;
+  const unsigned it_lds = smem_base + (unsigned)(4 + wave_s * kCK * a.RS) * 4;
+  const int64_t it_step = (int64_t)4 * a.Ctot * a.Tx * 4;
+  const unsigned it_lds_step = (unsigned)(4 * kCK * a.RS) * 4;
+  static_assert(GT != 2 || w_len == 4 * 5 * 256, "a full 32-filter weight chunk is 20 pieces of 1 KiB");
+  const char* const w_src = (const char*)wbase + wave_s * (w_len / 4) * 4;
+  const unsigned w_lds = smem_base + (unsigned)(4 + in_len + wave_s * (w_len / 4)) * 4;
+  unsigned in_voff = lane * 16, w_voff = lane * 16;           // chunk 0 (they stay below one item's / one zone's bytes)
+  auto stage_fast = [&](int s) {                              // the chunk after the one staged last
+    in_voff += kCK * a.Tx * 4;
+    w_voff += w_len * 4;
+    const unsigned boff = (unsigned)(s * buf_len) * 4;
+    auto items = [&](auto nf) {                               // one statement an item
+      const char* src = it_src;
+      unsigned lds = it_lds + boff;
+      for (int k = 0; k < n_mine; ++k, src += it_step, lds += it_lds_step)
+        glds_item<decltype(nf)::value>(tail_lanes, lds, src, in_voff);
+    };
+    switch (cnt4_full >> 6) {
+      case 0: items(std::integral_constant<int, 0>{}); break;
+      case 1: items(std::integral_constant<int, 1>{}); break;
+      case 2: items(std::integral_constant<int, 2>{}); break;
+      default: items(std::integral_constant<int, 3>{}); break;
+    }
+    glds_lines<4, 0>(w_lds + boff, w_src, w_voff);
+    glds_lines<1, 0>(w_lds + boff + 4096, w_src + 4096, w_voff);
+  };
 
   // Every wave always carries NT column tiles (no branches around the MFMAs); tiles past the end compute on
   // whatever the LDS holds and are not stored.  The first layer is a valid convolution (pad 0): columns
@@ -564,11 +675,11 @@ __global__ __launch_bounds__(256) void conv5_fwd_glds_kernel(ConvArgs a) {
       }
     __builtin_amdgcn_sched_barrier(0);
   };
-  const unsigned smem_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) float*)smem;
   stage(0, 0);
   int ch = 0;
   if constexpr (GT == 2) {
     for (; ch < cin / kCK; ++ch) {                          // the full chunks
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (stage_fast's DMA is not the compiler's to wait for)
       __syncthreads();                                      // drains this wave's DMA of chunk ch; all waves left chunk ch-1
       unsigned a_addr = smem_base + (unsigned)(4 + (ch & 1) * buf_len + in_len + lane) * 4;
       unsigned b_addr[NT];
@@ -579,7 +690,10 @@ __global__ __launch_bounds__(256) void conv5_fwd_glds_kernel(ConvArgs a) {
 #pragma unroll
       for (int cg = 0; cg < kCK / 4; cg += 2) {
         issue(f1, a_addr, b_addr);
-        if (cg == 0 && ch + 1 < n_chunks) stage(ch + 1, (ch + 1) & 1);
+        if (cg == 0 && ch + 1 < n_chunks) {
+          if (fast && ch + 1 < cin / kCK) stage_fast((ch + 1) & 1);
+          else stage(ch + 1, (ch + 1) & 1);
+        }
         take(f0, std::integral_constant<int, kSetReads>{});
         mma_set(f0);
         if (cg + 2 < kCK / 4) {
@@ -2894,6 +3008,30 @@ __global__ __launch_bounds__(256) void conv5_wgrad_wide_kernel(WgradArgs a) {
                   (cw * a.Tin) >> 2, lane);
     }
   };
+  // The same staging as straight-line code (glds_run).  A stage is at most four items, so a wave
+  // stages one: item `wave` of the stage, into its slot of the buffer.  Its two source bases, the piece counts and the
+  // two partial-piece lane masks are worked out here once; a stage moves the bases on by IPS items (scalar adds).
+  // A ragged last stage leaves the waves past its last item idle, a narrow channel group has fewer input pieces: both
+  // stage what `stage` does.  Taken when dOut and the input rows of an item are at most 8 pieces each (glds_run's limit).
+  const unsigned smem_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) float*)smem;
+  const int do_q = do_len >> 2, in_q = (cw * a.Tin) >> 2;
+  const bool fast = a.IPS <= 4 && do_q <= kGldsRunMax4 && in_q <= kGldsRunMax4;
+  const uint64_t do_tail = __builtin_amdgcn_ballot_w64(lane < (do_q & 63));
+  const uint64_t in_tail = __builtin_amdgcn_ballot_w64(lane < (in_q & 63));
+  const char* do_src = (const char*)a.dout + ((i_lo + wave_s) * a.Z + z) * (int64_t)do_len * 4;
+  const char* in_src = (const char*)a.in + ((i_lo + wave_s) * a.Ctot + chan0 + c_base) * (int64_t)a.Tx * 4;
+  const int64_t do_step = (int64_t)a.IPS * a.Z * do_len * 4, in_step = (int64_t)a.IPS * a.Ctot * a.Tx * 4;
+  const unsigned slot_lds = smem_base + (unsigned)(wave_s * item_len) * 4;
+  const unsigned lane16 = lane * 16;
+  auto stage_fast = [&](int n_it, int s) {                              // the stage after the one staged last
+    if (wave_s < n_it) {
+      const unsigned dst = slot_lds + (unsigned)(s * buf_len) * 4;
+      glds_run(do_q >> 6, do_tail, dst, do_src, lane16);
+      glds_run(in_q >> 6, in_tail, dst + (unsigned)do_len * 4, in_src, lane16);
+    }
+    do_src += do_step;
+    in_src += in_step;
+  };
 
   f32x4 acc[GT][kTaps], accb[GT];
 #pragma unroll
@@ -2918,7 +3056,6 @@ __global__ __launch_bounds__(256) void conv5_wgrad_wide_kernel(WgradArgs a) {
     float b4;
   };
   constexpr int kSetReads = GT + 3;
-  const unsigned smem_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) float*)smem;
   const unsigned zero_addr = smem_base + (unsigned)(2 * buf_len) * 4;   // 8 floats behind the buffers: cleared above, never staged
   auto run_packed = [&](auto bias, int sbuf, int n_it) {
     const unsigned buf_addr = smem_base + (unsigned)(sbuf * buf_len) * 4;
@@ -3038,10 +3175,15 @@ __global__ __launch_bounds__(256) void conv5_wgrad_wide_kernel(WgradArgs a) {
   // only stages), so the accumulators stay in one register set and no branch sits between the MFMA groups.
   auto run_stages = [&](auto mode) {
     int s = 0;
-    if (i_lo < i_hi) stage(i_lo, 0);
+    auto stage_any = [&](int64_t is, int sb) {
+      if (fast) stage_fast((int)((i_hi - is) < a.IPS ? (i_hi - is) : a.IPS), sb);
+      else stage(is, sb);
+    };
+    if (i_lo < i_hi) stage_any(i_lo, 0);
     for (int64_t is = i_lo; is < i_hi; is += a.IPS, s ^= 1) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                 // (stage_fast's DMA is not the compiler's to wait for)
       __syncthreads();                                                 // DMA of this stage retired; previous stage consumed
-      if (is + a.IPS < i_hi) stage(is + a.IPS, s ^ 1);
+      if (is + a.IPS < i_hi) stage_any(is + a.IPS, s ^ 1);
       const int n_it = (int)((i_hi - is) < a.IPS ? (i_hi - is) : a.IPS);
       if constexpr (decltype(mode)::value == 0) run_single(s, n_it);
       else if constexpr (decltype(mode)::value != 3) run_packed(std::integral_constant<bool, decltype(mode)::value == 2>{}, s, n_it);
@@ -3794,6 +3936,13 @@ static bool bf16_mfma_ok(const isd_conv4_plan* p, const Geo& g, const void* x) {
          ((uintptr_t)x & 15) == 0;
 }
 
+// What isd_first_layer_last_path() reports: the kernels the calling thread's last first-layer forward and weight
+// gradient launched.  Forward (low four bits): 0 conv5_fwd_kernel, 1..4 conv5_fwd_glds_kernel<2, 2>, <2, 4>, <1, 2>,
+// <1, 4>, 5 conv5_fwd_bf16_kernel.  Weight gradient (the bits above): 0 conv5_wgrad_kernel, 1 conv5_wgrad_wide_kernel,
+// 2 conv5_wgrad_wide_bf16_kernel.
+static thread_local int g_first_fwd_path = 0, g_first_wgrad_path = 0;
+extern "C" int isd_first_layer_last_path(void) { return g_first_fwd_path + 16 * g_first_wgrad_path; }
+
 // cnn1 o cnn2 forward into the A2 buffer; `a` comes back filled with the shared fields for the later layers
 static int first_layer_forward(const isd_conv4_plan* p, const Geo& g, const float* x, int64_t T, float* ws,
                                hipStream_t st, ConvArgs& a, bool tap16 = false, bool in16 = false) {
@@ -3812,6 +3961,7 @@ static int first_layer_forward(const isd_conv4_plan* p, const Geo& g, const floa
     if (NT == 3) { NT = 4; }
     ipw = NT * 4;
     d.IPW = ipw;
+    g_first_fwd_path = 5;
     static void (*const k[2][3])(ConvArgs, const uint4*) = {   // [in16 ? 0 : 1][NT == 4 ? 0 : NT == 2 ? 1 : 2]
         {conv5_fwd_bf16_kernel<2, 4, true>, conv5_fwd_bf16_kernel<2, 2, true>, conv5_fwd_bf16_kernel<2, 1, true>},
         {conv5_fwd_bf16_kernel<2, 4, false>, conv5_fwd_bf16_kernel<2, 2, false>, conv5_fwd_bf16_kernel<2, 1, false>}};
@@ -3841,8 +3991,10 @@ static int first_layer_forward(const isd_conv4_plan* p, const Geo& g, const floa
     else if (GT == 2) k = conv5_fwd_glds_kernel<2, 4>;
     else if (NT == 2) k = conv5_fwd_glds_kernel<1, 2>;
     else k = conv5_fwd_glds_kernel<1, 4>;
+    g_first_fwd_path = (GT == 2 ? 1 : 3) + (NT == 2 ? 0 : 1);
     return launch_lds(k, dim3((unsigned)cdiv(g.items, ipw), p->Z), dim3(256), lds, st, d);
   }
+  g_first_fwd_path = 0;
   return launch_conv(0, p->act_bf16, a, p->Z, st);
 }
 
@@ -3982,12 +4134,15 @@ static int first_layer_backward(const isd_conv4_plan* p, const Geo& g, const flo
     rc = launch_lds(in16 ? conv5_wgrad_wide_bf16_kernel<2, true> : conv5_wgrad_wide_bf16_kernel<2, false>, grid, dim3(256),
                     conv5_wgrad_wide_lds(ips16, conv5_wgrad_wide_bf16_item_floats(F, p->W)), st, w);
     n_slabs0 = R;
+    g_first_wgrad_path = 2;
   } else if (g.lin0 && p->dma_ok && !p->act_bf16 && p->max_cz >= 64 && (F * g.T1) % 4 == 0 && lds <= 64 * 1024 &&
              ((uintptr_t)x & 15) == 0 && ((uintptr_t)g2 & 15) == 0) {
     w.items_per_wg = ipw; w.IPS = ips;
     rc = launch_lds(F == 32 ? conv5_wgrad_wide_kernel<2> : conv5_wgrad_wide_kernel<1>, grid, dim3(256), lds, st, w);
     n_slabs0 = R;
+    g_first_wgrad_path = 1;
   } else {
+    g_first_wgrad_path = 0;
     rc = launch_wgrad(0, p->act_bf16, w, p->Z, p->max_cz + 1, st);
   }
   if (rc) return rc;
