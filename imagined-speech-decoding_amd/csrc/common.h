@@ -37,6 +37,8 @@ static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // ------------------------------------------------------------------ device side
 #if defined(__HIPCC__)
 
+typedef float f32x4 __attribute__((ext_vector_type(4)));   // an MFMA accumulator fragment
+
 // DPP row shift right by N inside each 16-lane row; lanes with no source get 0 (bound_ctrl: no `old` operand to
 // initialise, and the shift can fold into a consuming VOP2).
 template <int N>

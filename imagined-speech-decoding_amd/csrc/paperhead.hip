@@ -21,13 +21,8 @@
 
 namespace isd {
 
-// every launch of this file goes through zone_launch: issued at once, or recorded for a zone-batched launch (zonebatch.h)
-#define ISD_ZLAUNCH(...)                                    \
-  do {                                                      \
-    if (!zone_launch(__VA_ARGS__)) return ISD_ERR_INVALID;  \
-  } while (0)
+// every launch of this file goes through ISD_ZLAUNCH (zonebatch.h): issued at once, or recorded for a zone batch
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int kPhMaxF = 64;      // widest layer supported (feature_dim <= 64)
 constexpr int kPhSlabs = 1024;
 
@@ -74,422 +69,348 @@ __device__ __forceinline__ float ph_block_sum(float v, float* red) {
 // Weff / beff, and the two scalar-load layouts of every layer's weight:
 //   Wf[l][c][k][Fp]  (forward: 16 consecutive output channels per tap)
 //   Wb[l][o][k][Cp]  (data gradient: 16 consecutive input channels per tap)
-__device__ __forceinline__ void ph_prep_kernel_body(const float* __restrict__ params, float* __restrict__ Wf,
-                                                      float* __restrict__ Wb, float* __restrict__ beff, PhGeo g,
-                                                      int l, int64_t wf_off, int64_t wb_off,
-    unsigned zgx, unsigned zgy, unsigned zbz, unsigned zgz) {   // this zone's own gridDim.x/.y, blockIdx.z, gridDim.z
-  const int Fo = g.Fo[l], Ci = g.Ci[l], Fp = g.Fp[l], Cp = g.Cp[l];
-  const int e = blockIdx.x * 256 + threadIdx.x;
-  const int n = (Fp > Fo ? Fp : Fo) * (Cp > Ci ? Cp : Ci) * 3;
-  if (l == 0 && e < Fo) {
-    float s = 0.f;
-    for (int f = 0; f < Fo; ++f) {
-      float ws = 0.f;
-      for (int c = 0; c < Ci; ++c) ws += params[g.ws + (e * Fo + f) * Ci + c];
-      s = fmaf(ws, params[g.bt + f], s);
+struct ph_prep_kernel {
+  static constexpr int kBounds = 256;
+  static __device__ __forceinline__ void run(ZoneGrid zg, const float* __restrict__ params, float* __restrict__ Wf,
+                                             float* __restrict__ Wb, float* __restrict__ beff, PhGeo g, int l,
+                                             int64_t wf_off, int64_t wb_off) {
+    const int Fo = g.Fo[l], Ci = g.Ci[l], Fp = g.Fp[l], Cp = g.Cp[l];
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    const int n = (Fp > Fo ? Fp : Fo) * (Cp > Ci ? Cp : Ci) * 3;
+    if (l == 0 && e < Fo) {
+      float s = 0.f;
+      for (int f = 0; f < Fo; ++f) {
+        float ws = 0.f;
+        for (int c = 0; c < Ci; ++c) ws += params[g.ws + (e * Fo + f) * Ci + c];
+        s = fmaf(ws, params[g.bt + f], s);
+      }
+      beff[e] = s;
     }
-    beff[e] = s;
-  }
-  if (l == 0 && e >= Fo && e < g.Fp[0]) beff[e] = 0.f;
-  if (e >= n) return;
-  const int k = e % 3, c = (e / 3) % (Cp > Ci ? Cp : Ci), o = e / (3 * (Cp > Ci ? Cp : Ci));
-  float w = 0.f;
-  if (o < Fo && c < Ci) {
-    if (l == 0) {
-      for (int f = 0; f < Fo; ++f) w = fmaf(params[g.ws + (o * Fo + f) * Ci + c], params[g.wt + f * 3 + k], w);
-    } else {
-      w = params[g.w[l] + (o * Ci + c) * 3 + k];
+    if (l == 0 && e >= Fo && e < g.Fp[0]) beff[e] = 0.f;
+    if (e >= n) return;
+    const int k = e % 3, c = (e / 3) % (Cp > Ci ? Cp : Ci), o = e / (3 * (Cp > Ci ? Cp : Ci));
+    float w = 0.f;
+    if (o < Fo && c < Ci) {
+      if (l == 0) {
+        for (int f = 0; f < Fo; ++f) w = fmaf(params[g.ws + (o * Fo + f) * Ci + c], params[g.wt + f * 3 + k], w);
+      } else {
+        w = params[g.w[l] + (o * Ci + c) * 3 + k];
+      }
     }
+    if (c < Ci && o < Fp) Wf[wf_off + ((int64_t)c * 3 + k) * Fp + o] = w;
+    if (o < Fo && c < Cp) Wb[wb_off + ((int64_t)o * 3 + k) * Cp + c] = w;
   }
-  if (c < Ci && o < Fp) Wf[wf_off + ((int64_t)c * 3 + k) * Fp + o] = w;
-  if (o < Fo && c < Cp) Wb[wb_off + ((int64_t)o * 3 + k) * Cp + c] = w;
-}
-ISD_ZONE_FN(ph_prep_kernel, 256)
-__global__ __launch_bounds__(256) void ph_prep_kernel(const float* __restrict__ params, float* __restrict__ Wf,
-                                                      float* __restrict__ Wb, float* __restrict__ beff, PhGeo g,
-                                                      int l, int64_t wf_off, int64_t wb_off) {
-  ph_prep_kernel_body(params, Wf, Wb, beff, g, l, wf_off, wb_off,
-      gridDim.x, gridDim.y, blockIdx.z, gridDim.z);
-}
-ISD_ZONE_REGISTER(ph_prep_kernel)
+};
 
 // y[b,o,t] = bias[o] + sum_{c,k} W[o,c,k] in[b,c,t+k];  per-channel sums of y and y^2.
 // Persistent blocks over (b,t); blockIdx.y selects a tile of 16 output channels.
-__device__ __forceinline__ void ph_conv_kernel_body(const float* __restrict__ in, const float* __restrict__ Wf,
-                                                      const float* __restrict__ bias, float* __restrict__ y,
-                                                      ExactAcc* __restrict__ s1, ExactAcc* __restrict__ s2, int64_t B,
-                                                      int Ci, int Ti, int To, int Fo, int Fp, int want_stats,
-    unsigned zgx, unsigned zgy, unsigned zbz, unsigned zgz) {   // this zone's own gridDim.x/.y, blockIdx.z, gridDim.z
-  __shared__ float red[4];
-  __shared__ float tot[32];
-  const int o0 = blockIdx.y * 16;
-  float a1[16], a2[16];
+struct ph_conv_kernel {
+  static constexpr int kBounds = 256;
+  static __device__ __forceinline__ void run(ZoneGrid zg, const float* __restrict__ in, const float* __restrict__ Wf,
+                                             const float* __restrict__ bias, float* __restrict__ y,
+                                             ExactAcc* __restrict__ s1, ExactAcc* __restrict__ s2, int64_t B, int Ci,
+                                             int Ti, int To, int Fo, int Fp, int want_stats) {
+    __shared__ float red[4];
+    __shared__ float tot[32];
+    const int o0 = blockIdx.y * 16;
+    float a1[16], a2[16];
 #pragma unroll
-  for (int i = 0; i < 16; ++i) a1[i] = a2[i] = 0.f;
-  const int64_t n = B * To;
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)zgx * 256) {
-    const int64_t b = e / To;
-    const int t = (int)(e - b * To);
-    float acc[16];
+    for (int i = 0; i < 16; ++i) a1[i] = a2[i] = 0.f;
+    const int64_t n = B * To;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)zg.gx * 256) {
+      const int64_t b = e / To;
+      const int t = (int)(e - b * To);
+      float acc[16];
 #pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = bias ? bias[o0 + i] : 0.f;
-    const float* ip = in + b * Ci * Ti + t;
-    for (int c = 0; c < Ci; ++c) {
-      const float v0 = ip[c * Ti], v1 = ip[c * Ti + 1], v2 = ip[c * Ti + 2];
-      const float* w = Wf + (int64_t)c * 3 * Fp + o0;
+      for (int i = 0; i < 16; ++i) acc[i] = bias ? bias[o0 + i] : 0.f;
+      const float* ip = in + b * Ci * Ti + t;
+      for (int c = 0; c < Ci; ++c) {
+        const float v0 = ip[c * Ti], v1 = ip[c * Ti + 1], v2 = ip[c * Ti + 2];
+        const float* w = Wf + (int64_t)c * 3 * Fp + o0;
 #pragma unroll
-      for (int i = 0; i < 16; ++i) acc[i] = fmaf(w[i], v0, fmaf(w[Fp + i], v1, fmaf(w[2 * Fp + i], v2, acc[i])));
+        for (int i = 0; i < 16; ++i) acc[i] = fmaf(w[i], v0, fmaf(w[Fp + i], v1, fmaf(w[2 * Fp + i], v2, acc[i])));
+      }
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        if (o0 + i < Fo) y[(b * Fo + o0 + i) * To + t] = acc[i];
+        a1[i] += acc[i];
+        a2[i] = fmaf(acc[i], acc[i], a2[i]);
+      }
     }
+    if (want_stats) {
 #pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      if (o0 + i < Fo) y[(b * Fo + o0 + i) * To + t] = acc[i];
-      a1[i] += acc[i];
-      a2[i] = fmaf(acc[i], acc[i], a2[i]);
+      for (int i = 0; i < 16; ++i) {
+        const float r1 = ph_block_sum(a1[i], red);
+        const float r2 = ph_block_sum(a2[i], red);
+        if (threadIdx.x == 0) { tot[i] = r1; tot[16 + i] = r2; }
+      }
+      __syncthreads();
+      const int i = threadIdx.x & 15;
+      if (threadIdx.x < 16 && o0 + i < Fo) exact_add(&s1[o0 + i], tot[i]);
+      else if (threadIdx.x >= 16 && threadIdx.x < 32 && o0 + i < Fo) exact_add(&s2[o0 + i], tot[16 + i]);
     }
   }
-  if (want_stats) {
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const float r1 = ph_block_sum(a1[i], red);
-      const float r2 = ph_block_sum(a2[i], red);
-      if (threadIdx.x == 0) { tot[i] = r1; tot[16 + i] = r2; }
-    }
-    __syncthreads();
-    const int i = threadIdx.x & 15;
-    if (threadIdx.x < 16 && o0 + i < Fo) exact_add(&s1[o0 + i], tot[i]);
-    else if (threadIdx.x >= 16 && threadIdx.x < 32 && o0 + i < Fo) exact_add(&s2[o0 + i], tot[16 + i]);
-  }
-}
-ISD_ZONE_FN(ph_conv_kernel, 256)
-__global__ __launch_bounds__(256) void ph_conv_kernel(const float* __restrict__ in, const float* __restrict__ Wf,
-                                                      const float* __restrict__ bias, float* __restrict__ y,
-                                                      ExactAcc* __restrict__ s1, ExactAcc* __restrict__ s2, int64_t B,
-                                                      int Ci, int Ti, int To, int Fo, int Fp, int want_stats) {
-  ph_conv_kernel_body(in, Wf, bias, y, s1, s2, B, Ci, Ti, To, Fo, Fp, want_stats,
-      gridDim.x, gridDim.y, blockIdx.z, gridDim.z);
-}
-ISD_ZONE_REGISTER(ph_conv_kernel)
+};
 
 // BN coefficients of layer l: bn(y) = A y + Bc.  training: batch statistics (+ running update); eval: running buffers.
-__device__ __forceinline__ void ph_finalize_kernel_body(const float* __restrict__ params, float* __restrict__ bufs,
-                                   const PhStats* __restrict__ st, PhCoef* __restrict__ co, PhGeo g, int l, double N,
-                                   int training, float momentum, float eps,
-    unsigned zgx, unsigned zgy, unsigned zbz, unsigned zgz) {   // this zone's own gridDim.x/.y, blockIdx.z, gridDim.z
-  const int o = threadIdx.x;
-  if (o >= g.Fo[l]) return;
-  double mu, var;
-  if (training) {
-    mu = exact_get(&st->s[l][0][o]) / N;
-    var = exact_get(&st->s[l][1][o]) / N - mu * mu;
-    if (var < 0.0) var = 0.0;
-    bufs[g.rm[l] + o] = (1.f - momentum) * bufs[g.rm[l] + o] + momentum * (float)mu;
-    bufs[g.rv[l] + o] = (1.f - momentum) * bufs[g.rv[l] + o] + momentum * (float)(var * N / (N > 1.0 ? N - 1.0 : 1.0));
-  } else {
-    mu = bufs[g.rm[l] + o];
-    var = bufs[g.rv[l] + o];
+struct ph_finalize_kernel {
+  static constexpr int kBounds = 1024;
+  static __device__ __forceinline__ void run(ZoneGrid zg, const float* __restrict__ params, float* __restrict__ bufs,
+                                             const PhStats* __restrict__ st, PhCoef* __restrict__ co, PhGeo g, int l,
+                                             double N, int training, float momentum, float eps) {
+    const int o = threadIdx.x;
+    if (o >= g.Fo[l]) return;
+    double mu, var;
+    if (training) {
+      mu = exact_get(&st->s[l][0][o]) / N;
+      var = exact_get(&st->s[l][1][o]) / N - mu * mu;
+      if (var < 0.0) var = 0.0;
+      bufs[g.rm[l] + o] = (1.f - momentum) * bufs[g.rm[l] + o] + momentum * (float)mu;
+      bufs[g.rv[l] + o] = (1.f - momentum) * bufs[g.rv[l] + o] + momentum * (float)(var * N / (N > 1.0 ? N - 1.0 : 1.0));
+    } else {
+      mu = bufs[g.rm[l] + o];
+      var = bufs[g.rv[l] + o];
+    }
+    const double isg = 1.0 / sqrt(var + (double)eps);
+    const double gm = params[g.g[l] + o], bt = params[g.b[l] + o];
+    co->A[l][o] = (float)(gm * isg);
+    co->Bc[l][o] = (float)(bt - gm * mu * isg);
+    co->mu[l][o] = (float)mu;
+    co->isg[l][o] = (float)isg;
   }
-  const double isg = 1.0 / sqrt(var + (double)eps);
-  const double gm = params[g.g[l] + o], bt = params[g.b[l] + o];
-  co->A[l][o] = (float)(gm * isg);
-  co->Bc[l][o] = (float)(bt - gm * mu * isg);
-  co->mu[l][o] = (float)mu;
-  co->isg[l][o] = (float)isg;
-}
-ISD_ZONE_FN(ph_finalize_kernel, 1024)
-__global__ void ph_finalize_kernel(const float* __restrict__ params, float* __restrict__ bufs,
-                                   const PhStats* __restrict__ st, PhCoef* __restrict__ co, PhGeo g, int l, double N,
-                                   int training, float momentum, float eps) {
-  ph_finalize_kernel_body(params, bufs, st, co, g, l, N, training, momentum, eps,
-      gridDim.x, gridDim.y, blockIdx.z, gridDim.z);
-}
-ISD_ZONE_REGISTER(ph_finalize_kernel)
+};
 
 // a[b,o,p] = max(GELU(bn(y[2p])), GELU(bn(y[2p+1])))
-__device__ __forceinline__ void ph_pool_kernel_body(const float* __restrict__ y, const PhCoef* __restrict__ co,
-                                                      float* __restrict__ a, int64_t n, int l, int Fo, int To, int Tp,
-    unsigned zgx, unsigned zgy, unsigned zbz, unsigned zgz) {   // this zone's own gridDim.x/.y, blockIdx.z, gridDim.z
-  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= n) return;
-  const int64_t row = e / Tp;
-  const int p = (int)(e - row * Tp), o = (int)(row % Fo);
-  const float A = co->A[l][o], Bc = co->Bc[l][o];
-  const float* yr = y + row * To + 2 * p;
-  a[e] = fmaxf(ph_gelu(fmaf(A, yr[0], Bc)), ph_gelu(fmaf(A, yr[1], Bc)));
-}
-ISD_ZONE_FN(ph_pool_kernel, 256)
-__global__ __launch_bounds__(256) void ph_pool_kernel(const float* __restrict__ y, const PhCoef* __restrict__ co,
-                                                      float* __restrict__ a, int64_t n, int l, int Fo, int To, int Tp) {
-  ph_pool_kernel_body(y, co, a, n, l, Fo, To, Tp,
-      gridDim.x, gridDim.y, blockIdx.z, gridDim.z);
-}
-ISD_ZONE_REGISTER(ph_pool_kernel)
+struct ph_pool_kernel {
+  static constexpr int kBounds = 256;
+  static __device__ __forceinline__ void run(ZoneGrid zg, const float* __restrict__ y, const PhCoef* __restrict__ co,
+                                             float* __restrict__ a, int64_t n, int l, int Fo, int To, int Tp) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n) return;
+    const int64_t row = e / Tp;
+    const int p = (int)(e - row * Tp), o = (int)(row % Fo);
+    const float A = co->A[l][o], Bc = co->Bc[l][o];
+    const float* yr = y + row * To + 2 * p;
+    a[e] = fmaxf(ph_gelu(fmaf(A, yr[0], Bc)), ph_gelu(fmaf(A, yr[1], Bc)));
+  }
+};
 
 // out[b,o] = mean_p a4[b,o,p]
-__device__ __forceinline__ void ph_mean_kernel_body(const float* __restrict__ a, float* __restrict__ out, int64_t rows,
-                                                      int Tp,
-    unsigned zgx, unsigned zgy, unsigned zbz, unsigned zgz) {   // this zone's own gridDim.x/.y, blockIdx.z, gridDim.z
-  const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (r >= rows) return;
-  float s = 0.f;
-  for (int p = 0; p < Tp; ++p) s += a[r * Tp + p];
-  out[r] = s / (float)Tp;
-}
-ISD_ZONE_FN(ph_mean_kernel, 256)
-__global__ __launch_bounds__(256) void ph_mean_kernel(const float* __restrict__ a, float* __restrict__ out, int64_t rows,
-                                                      int Tp) {
-  ph_mean_kernel_body(a, out, rows, Tp,
-      gridDim.x, gridDim.y, blockIdx.z, gridDim.z);
-}
-ISD_ZONE_REGISTER(ph_mean_kernel)
+struct ph_mean_kernel {
+  static constexpr int kBounds = 256;
+  static __device__ __forceinline__ void run(ZoneGrid zg, const float* __restrict__ a, float* __restrict__ out,
+                                             int64_t rows, int Tp) {
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= rows) return;
+    float s = 0.f;
+    for (int p = 0; p < Tp; ++p) s += a[r * Tp + p];
+    out[r] = s / (float)Tp;
+  }
+};
 
 // ------------------------------------------------------------------------------------------------ backward
 // Max-pool routing + GELU':  dyh[b,o,t] (gradient w.r.t. the BN output) from da[b,o,p] (or dout[b,o]/Tp for the
 // last layer), and the BN backward sums.  blockIdx.y = channel; persistent over (b,p).
-__device__ __forceinline__ void ph_bwd_pool_kernel_body(const float* __restrict__ y, const float* __restrict__ da,
-                                                          const float* __restrict__ dout,
-                                                          const PhCoef* __restrict__ co, float* __restrict__ dyh,
-                                                          PhStats* __restrict__ st, int64_t B, int l, int Fo, int To,
-                                                          int Tp,
-    unsigned zgx, unsigned zgy, unsigned zbz, unsigned zgz) {   // this zone's own gridDim.x/.y, blockIdx.z, gridDim.z
-  __shared__ float red[4];
-  const int o = blockIdx.y;
-  const float A = co->A[l][o], Bc = co->Bc[l][o], mu = co->mu[l][o], isg = co->isg[l][o];
-  float s1 = 0.f, s2 = 0.f;
-  const int64_t n = B * Tp;
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)zgx * 256) {
-    const int64_t b = e / Tp;
-    const int p = (int)(e - b * Tp);
-    const int64_t row = b * Fo + o;
-    const float up = dout ? dout[row] / (float)Tp : da[row * Tp + p];
-    const float y0 = y[row * To + 2 * p], y1 = y[row * To + 2 * p + 1];
-    const float v0 = fmaf(A, y0, Bc), v1 = fmaf(A, y1, Bc);
-    const bool second = ph_gelu(v1) > ph_gelu(v0);                  // ties -> first element, like max_pool2d
-    const float d = up * ph_gelu_grad(second ? v1 : v0);
-    dyh[row * To + 2 * p] = second ? 0.f : d;
-    dyh[row * To + 2 * p + 1] = second ? d : 0.f;
-    if ((To & 1) && p == Tp - 1) dyh[row * To + To - 1] = 0.f;      // the sample MaxPool drops
-    s1 += d;
-    s2 = fmaf(d, ((second ? y1 : y0) - mu) * isg, s2);
-  }
-  const float r1 = ph_block_sum(s1, red);
-  const float r2 = ph_block_sum(s2, red);
-  if (threadIdx.x == 0) {
-    exact_add(&st->d[l][0][o], r1);
-    exact_add(&st->d[l][1][o], r2);
-  }
-}
-ISD_ZONE_FN(ph_bwd_pool_kernel, 256)
-__global__ __launch_bounds__(256) void ph_bwd_pool_kernel(const float* __restrict__ y, const float* __restrict__ da,
-                                                          const float* __restrict__ dout,
-                                                          const PhCoef* __restrict__ co, float* __restrict__ dyh,
-                                                          PhStats* __restrict__ st, int64_t B, int l, int Fo, int To,
-                                                          int Tp) {
-  ph_bwd_pool_kernel_body(y, da, dout, co, dyh, st, B, l, Fo, To, Tp,
-      gridDim.x, gridDim.y, blockIdx.z, gridDim.z);
-}
-ISD_ZONE_REGISTER(ph_bwd_pool_kernel)
-
-__device__ __forceinline__ void ph_bwd_coef_kernel_body(const float* __restrict__ params, float* __restrict__ dparams,
-                                   const PhStats* __restrict__ st, PhCoef* __restrict__ co, PhGeo g, int l, double N,
-                                   int bn_train, double gs,
-    unsigned zgx, unsigned zgy, unsigned zbz, unsigned zgz) {   // this zone's own gridDim.x/.y, blockIdx.z, gridDim.z
-  const int o = threadIdx.x;
-  if (o >= g.Fo[l]) return;
-  const double inv = bn_train ? 1.0 / N : 0.0;           // running statistics do not depend on the batch: no mean terms
-  dparams[g.g[l] + o] = (float)(exact_get(&st->d[l][1][o]) * gs);    // global sums on every rank: pre-divided by the world size
-  dparams[g.b[l] + o] = (float)(exact_get(&st->d[l][0][o]) * gs);
-  co->cA[l][o] = params[g.g[l] + o] * co->isg[l][o];
-  co->cB[l][o] = (float)(exact_get(&st->d[l][0][o]) * inv);
-  co->cC[l][o] = (float)(exact_get(&st->d[l][1][o]) * inv);
-}
-ISD_ZONE_FN(ph_bwd_coef_kernel, 1024)
-__global__ void ph_bwd_coef_kernel(const float* __restrict__ params, float* __restrict__ dparams,
-                                   const PhStats* __restrict__ st, PhCoef* __restrict__ co, PhGeo g, int l, double N,
-                                   int bn_train, double gs) {
-  ph_bwd_coef_kernel_body(params, dparams, st, co, g, l, N, bn_train, gs,
-      gridDim.x, gridDim.y, blockIdx.z, gridDim.z);
-}
-ISD_ZONE_REGISTER(ph_bwd_coef_kernel)
-
-// dy = cA (dyh - cB - xhat cC) in place
-__device__ __forceinline__ void ph_bwd_bn_kernel_body(float* __restrict__ dyh, const float* __restrict__ y,
-                                                        const PhCoef* __restrict__ co, int64_t n, int l, int Fo,
-                                                        int To,
-    unsigned zgx, unsigned zgy, unsigned zbz, unsigned zgz) {   // this zone's own gridDim.x/.y, blockIdx.z, gridDim.z
-  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= n) return;
-  const int o = (int)((e / To) % Fo);
-  const float xh = (y[e] - co->mu[l][o]) * co->isg[l][o];
-  dyh[e] = co->cA[l][o] * (dyh[e] - co->cB[l][o] - xh * co->cC[l][o]);
-}
-ISD_ZONE_FN(ph_bwd_bn_kernel, 256)
-__global__ __launch_bounds__(256) void ph_bwd_bn_kernel(float* __restrict__ dyh, const float* __restrict__ y,
-                                                        const PhCoef* __restrict__ co, int64_t n, int l, int Fo,
-                                                        int To) {
-  ph_bwd_bn_kernel_body(dyh, y, co, n, l, Fo, To,
-      gridDim.x, gridDim.y, blockIdx.z, gridDim.z);
-}
-ISD_ZONE_REGISTER(ph_bwd_bn_kernel)
-
-// da[b,c,s] = sum_{o,k} W[o,c,k] dy[b,o,s-k]   (gradient w.r.t. the layer input = the previous pooled activation)
-__device__ __forceinline__ void ph_bwd_dgrad_kernel_body(const float* __restrict__ dy, const float* __restrict__ Wb,
-                                                           float* __restrict__ da, int64_t B, int Ci, int Cp, int Ti,
-                                                           int To, int Fo,
-    unsigned zgx, unsigned zgy, unsigned zbz, unsigned zgz) {   // this zone's own gridDim.x/.y, blockIdx.z, gridDim.z
-  const int c0 = blockIdx.y * 16;
-  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= B * Ti) return;
-  const int64_t b = e / Ti;
-  const int s = (int)(e - b * Ti);
-  float acc[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-  for (int o = 0; o < Fo; ++o) {
-    const float* dr = dy + (b * Fo + o) * To;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const int t = s - k;
-      const float dv = (t >= 0 && t < To) ? dr[t] : 0.f;
-      const float* w = Wb + ((int64_t)o * 3 + k) * Cp + c0;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc[i] = fmaf(w[i], dv, acc[i]);
+struct ph_bwd_pool_kernel {
+  static constexpr int kBounds = 256;
+  static __device__ __forceinline__ void run(ZoneGrid zg, const float* __restrict__ y, const float* __restrict__ da,
+                                             const float* __restrict__ dout, const PhCoef* __restrict__ co,
+                                             float* __restrict__ dyh, PhStats* __restrict__ st, int64_t B, int l,
+                                             int Fo, int To, int Tp) {
+    __shared__ float red[4];
+    const int o = blockIdx.y;
+    const float A = co->A[l][o], Bc = co->Bc[l][o], mu = co->mu[l][o], isg = co->isg[l][o];
+    float s1 = 0.f, s2 = 0.f;
+    const int64_t n = B * Tp;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)zg.gx * 256) {
+      const int64_t b = e / Tp;
+      const int p = (int)(e - b * Tp);
+      const int64_t row = b * Fo + o;
+      const float up = dout ? dout[row] / (float)Tp : da[row * Tp + p];
+      const float y0 = y[row * To + 2 * p], y1 = y[row * To + 2 * p + 1];
+      const float v0 = fmaf(A, y0, Bc), v1 = fmaf(A, y1, Bc);
+      const bool second = ph_gelu(v1) > ph_gelu(v0);                  // ties -> first element, like max_pool2d
+      const float d = up * ph_gelu_grad(second ? v1 : v0);
+      dyh[row * To + 2 * p] = second ? 0.f : d;
+      dyh[row * To + 2 * p + 1] = second ? d : 0.f;
+      if ((To & 1) && p == Tp - 1) dyh[row * To + To - 1] = 0.f;      // the sample MaxPool drops
+      s1 += d;
+      s2 = fmaf(d, ((second ? y1 : y0) - mu) * isg, s2);
+    }
+    const float r1 = ph_block_sum(s1, red);
+    const float r2 = ph_block_sum(s2, red);
+    if (threadIdx.x == 0) {
+      exact_add(&st->d[l][0][o], r1);
+      exact_add(&st->d[l][1][o], r2);
     }
   }
+};
+
+struct ph_bwd_coef_kernel {
+  static constexpr int kBounds = 1024;
+  static __device__ __forceinline__ void run(ZoneGrid zg, const float* __restrict__ params, float* __restrict__ dparams,
+                                             const PhStats* __restrict__ st, PhCoef* __restrict__ co, PhGeo g, int l,
+                                             double N, int bn_train, double gs) {
+    const int o = threadIdx.x;
+    if (o >= g.Fo[l]) return;
+    const double inv = bn_train ? 1.0 / N : 0.0;         // running statistics do not depend on the batch: no mean terms
+    dparams[g.g[l] + o] = (float)(exact_get(&st->d[l][1][o]) * gs);  // global sums on every rank: pre-divided by the world size
+    dparams[g.b[l] + o] = (float)(exact_get(&st->d[l][0][o]) * gs);
+    co->cA[l][o] = params[g.g[l] + o] * co->isg[l][o];
+    co->cB[l][o] = (float)(exact_get(&st->d[l][0][o]) * inv);
+    co->cC[l][o] = (float)(exact_get(&st->d[l][1][o]) * inv);
+  }
+};
+
+// dy = cA (dyh - cB - xhat cC) in place
+struct ph_bwd_bn_kernel {
+  static constexpr int kBounds = 256;
+  static __device__ __forceinline__ void run(ZoneGrid zg, float* __restrict__ dyh, const float* __restrict__ y,
+                                             const PhCoef* __restrict__ co, int64_t n, int l, int Fo, int To) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n) return;
+    const int o = (int)((e / To) % Fo);
+    const float xh = (y[e] - co->mu[l][o]) * co->isg[l][o];
+    dyh[e] = co->cA[l][o] * (dyh[e] - co->cB[l][o] - xh * co->cC[l][o]);
+  }
+};
+
+// da[b,c,s] = sum_{o,k} W[o,c,k] dy[b,o,s-k]   (gradient w.r.t. the layer input = the previous pooled activation)
+struct ph_bwd_dgrad_kernel {
+  static constexpr int kBounds = 256;
+  static __device__ __forceinline__ void run(ZoneGrid zg, const float* __restrict__ dy, const float* __restrict__ Wb,
+                                             float* __restrict__ da, int64_t B, int Ci, int Cp, int Ti, int To,
+                                             int Fo) {
+    const int c0 = blockIdx.y * 16;
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= B * Ti) return;
+    const int64_t b = e / Ti;
+    const int s = (int)(e - b * Ti);
+    float acc[16];
 #pragma unroll
-  for (int i = 0; i < 16; ++i)
-    if (c0 + i < Ci) da[(b * Ci + c0 + i) * Ti + s] = acc[i];
-}
-ISD_ZONE_FN(ph_bwd_dgrad_kernel, 256)
-__global__ __launch_bounds__(256) void ph_bwd_dgrad_kernel(const float* __restrict__ dy, const float* __restrict__ Wb,
-                                                           float* __restrict__ da, int64_t B, int Ci, int Cp, int Ti,
-                                                           int To, int Fo) {
-  ph_bwd_dgrad_kernel_body(dy, Wb, da, B, Ci, Cp, Ti, To, Fo,
-      gridDim.x, gridDim.y, blockIdx.z, gridDim.z);
-}
-ISD_ZONE_REGISTER(ph_bwd_dgrad_kernel)
+    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+    for (int o = 0; o < Fo; ++o) {
+      const float* dr = dy + (b * Fo + o) * To;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const int t = s - k;
+        const float dv = (t >= 0 && t < To) ? dr[t] : 0.f;
+        const float* w = Wb + ((int64_t)o * 3 + k) * Cp + c0;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[i] = fmaf(w[i], dv, acc[i]);
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+      if (c0 + i < Ci) da[(b * Ci + c0 + i) * Ti + s] = acc[i];
+  }
+};
 
 // dW[o,c,k] = sum_{b,t} dy[b,o,t] in[b,c,t+k] on the matrix cores (A = dy tile [16 o][4 t], B = in tile [4 t][16 c],
 // one accumulator per tap) + the bias column sum_{b,t} dy[b,o,t].  blockIdx.y = (o tile, c tile); persistent over b.
 // Partial slabs: part[block][o][c][k] and pbias[block][o].
-__device__ __forceinline__ void ph_bwd_wgrad_kernel_body(const float* __restrict__ dy, const float* __restrict__ in,
-                                                          float* __restrict__ part, float* __restrict__ pbias,
-                                                          int64_t B, int Ci, int Ti, int To, int Fo, int n_ctile,
-    unsigned zgx, unsigned zgy, unsigned zbz, unsigned zgz) {   // this zone's own gridDim.x/.y, blockIdx.z, gridDim.z
-  const int lane = threadIdx.x, q = lane >> 4, jl = lane & 15;
-  const int ot = blockIdx.y / n_ctile, ct = blockIdx.y - ot * n_ctile;
-  const int o = ot * 16 + jl, c = ct * 16 + jl;
-  f32x4 acc[3], accb = (f32x4){0.f, 0.f, 0.f, 0.f};
+struct ph_bwd_wgrad_kernel {
+  static constexpr int kBounds = 64;
+  static __device__ __forceinline__ void run(ZoneGrid zg, const float* __restrict__ dy, const float* __restrict__ in,
+                                             float* __restrict__ part, float* __restrict__ pbias, int64_t B, int Ci,
+                                             int Ti, int To, int Fo, int n_ctile) {
+    const int lane = threadIdx.x, q = lane >> 4, jl = lane & 15;
+    const int ot = blockIdx.y / n_ctile, ct = blockIdx.y - ot * n_ctile;
+    const int o = ot * 16 + jl, c = ct * 16 + jl;
+    f32x4 acc[3], accb = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-  for (int k = 0; k < 3; ++k) acc[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  for (int64_t b = blockIdx.x; b < B; b += zgx) {
-    const float* dr = dy + (b * Fo + (o < Fo ? o : 0)) * To;
-    const float* ir = in + (b * Ci + (c < Ci ? c : 0)) * Ti;
-    for (int t0 = 0; t0 < To; t0 += 4) {
-      const int t = t0 + q;
-      const bool tv = t < To;
-      const float af = (tv && o < Fo) ? dr[t] : 0.f;
+    for (int k = 0; k < 3; ++k) acc[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int64_t b = blockIdx.x; b < B; b += zg.gx) {
+      const float* dr = dy + (b * Fo + (o < Fo ? o : 0)) * To;
+      const float* ir = in + (b * Ci + (c < Ci ? c : 0)) * Ti;
+      for (int t0 = 0; t0 < To; t0 += 4) {
+        const int t = t0 + q;
+        const bool tv = t < To;
+        const float af = (tv && o < Fo) ? dr[t] : 0.f;
 #pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const float bf = (tv && c < Ci) ? ir[t + k] : 0.f;
-        acc[k] = __builtin_amdgcn_mfma_f32_16x16x4f32(af, bf, acc[k], 0, 0, 0);
+        for (int k = 0; k < 3; ++k) {
+          const float bf = (tv && c < Ci) ? ir[t + k] : 0.f;
+          acc[k] = __builtin_amdgcn_mfma_f32_16x16x4f32(af, bf, acc[k], 0, 0, 0);
+        }
+        if (pbias && ct == 0) accb = __builtin_amdgcn_mfma_f32_16x16x4f32(af, tv ? 1.f : 0.f, accb, 0, 0, 0);
       }
-      if (pbias && ct == 0) accb = __builtin_amdgcn_mfma_f32_16x16x4f32(af, tv ? 1.f : 0.f, accb, 0, 0, 0);
+    }
+    float* slab = part + (int64_t)blockIdx.x * Fo * Ci * 3;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int oo = ot * 16 + 4 * q + r;
+      if (oo < Fo && c < Ci) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) slab[((int64_t)oo * Ci + c) * 3 + k] = acc[k][r];
+      }
+      if (pbias && ct == 0 && jl == 0 && oo < Fo) pbias[(int64_t)blockIdx.x * Fo + oo] = accb[r];
     }
   }
-  float* slab = part + (int64_t)blockIdx.x * Fo * Ci * 3;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int oo = ot * 16 + 4 * q + r;
-    if (oo < Fo && c < Ci) {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) slab[((int64_t)oo * Ci + c) * 3 + k] = acc[k][r];
-    }
-    if (pbias && ct == 0 && jl == 0 && oo < Fo) pbias[(int64_t)blockIdx.x * Fo + oo] = accb[r];
-  }
-}
-ISD_ZONE_FN(ph_bwd_wgrad_kernel, 64)
-__global__ __launch_bounds__(64) void ph_bwd_wgrad_kernel(const float* __restrict__ dy, const float* __restrict__ in,
-                                                          float* __restrict__ part, float* __restrict__ pbias,
-                                                          int64_t B, int Ci, int Ti, int To, int Fo, int n_ctile) {
-  ph_bwd_wgrad_kernel_body(dy, in, part, pbias, B, Ci, Ti, To, Fo, n_ctile,
-      gridDim.x, gridDim.y, blockIdx.z, gridDim.z);
-}
-ISD_ZONE_REGISTER(ph_bwd_wgrad_kernel)
+};
 
-__device__ __forceinline__ void ph_reduce_kernel_body(const float* __restrict__ part, int n_slabs, int64_t n,
-                                                        float* __restrict__ dst,
-    unsigned zgx, unsigned zgy, unsigned zbz, unsigned zgz) {   // this zone's own gridDim.x/.y, blockIdx.z, gridDim.z
-  // block = 64 elements x 4 slab groups (contiguous quarters of the slabs, four loads in flight each, combined in LDS in
-  // a fixed order): one thread per element walking all the slabs was a chain of ~160 dependent load pairs, 42 us a launch
-  __shared__ float red[4][64];
-  const int l = threadIdx.x & 63, gq = threadIdx.x >> 6;
-  const int64_t e = (int64_t)blockIdx.x * 64 + l;
-  const int per = (n_slabs + 3) / 4;
-  const int k_lo = gq * per, k_hi = k_lo + per < n_slabs ? k_lo + per : n_slabs;
-  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-  if (e < n) {
-    int k = k_lo;
-    for (; k + 3 < k_hi; k += 4) {
-      s0 += part[(int64_t)k * n + e];
-      s1 += part[(int64_t)(k + 1) * n + e];
-      s2 += part[(int64_t)(k + 2) * n + e];
-      s3 += part[(int64_t)(k + 3) * n + e];
+struct ph_reduce_kernel {
+  static constexpr int kBounds = 256;
+  static __device__ __forceinline__ void run(ZoneGrid zg, const float* __restrict__ part, int n_slabs, int64_t n,
+                                             float* __restrict__ dst) {
+    // block = 64 elements x 4 slab groups (contiguous quarters of the slabs, four loads in flight each, combined in LDS in
+    // a fixed order): one thread per element walking all the slabs was a chain of ~160 dependent load pairs, 42 us a launch
+    __shared__ float red[4][64];
+    const int l = threadIdx.x & 63, gq = threadIdx.x >> 6;
+    const int64_t e = (int64_t)blockIdx.x * 64 + l;
+    const int per = (n_slabs + 3) / 4;
+    const int k_lo = gq * per, k_hi = k_lo + per < n_slabs ? k_lo + per : n_slabs;
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    if (e < n) {
+      int k = k_lo;
+      for (; k + 3 < k_hi; k += 4) {
+        s0 += part[(int64_t)k * n + e];
+        s1 += part[(int64_t)(k + 1) * n + e];
+        s2 += part[(int64_t)(k + 2) * n + e];
+        s3 += part[(int64_t)(k + 3) * n + e];
+      }
+      for (; k < k_hi; ++k) s0 += part[(int64_t)k * n + e];
     }
-    for (; k < k_hi; ++k) s0 += part[(int64_t)k * n + e];
+    red[gq][l] = (s0 + s1) + (s2 + s3);
+    __syncthreads();
+    if (gq == 0 && e < n) dst[e] = (red[0][l] + red[1][l]) + (red[2][l] + red[3][l]);
   }
-  red[gq][l] = (s0 + s1) + (s2 + s3);
-  __syncthreads();
-  if (gq == 0 && e < n) dst[e] = (red[0][l] + red[1][l]) + (red[2][l] + red[3][l]);
-}
-ISD_ZONE_FN(ph_reduce_kernel, 256)
-__global__ __launch_bounds__(256) void ph_reduce_kernel(const float* __restrict__ part, int n_slabs, int64_t n,
-                                                        float* __restrict__ dst) {
-  ph_reduce_kernel_body(part, n_slabs, n, dst,
-      gridDim.x, gridDim.y, blockIdx.z, gridDim.z);
-}
-ISD_ZONE_REGISTER(ph_reduce_kernel)
+};
 
 // dWeff [F1][C][3], dbeff [F1] -> gradients of cnn1_t.weight, cnn1_t.bias, cnn1_s.weight.  One block.
-__device__ __forceinline__ void ph_bwd_l1_kernel_body(const float* __restrict__ params, float* __restrict__ dparams,
-                                                        const float* __restrict__ dWeff, const float* __restrict__ dbeff,
-                                                        PhGeo g,
-    unsigned zgx, unsigned zgy, unsigned zbz, unsigned zgz) {   // this zone's own gridDim.x/.y, blockIdx.z, gridDim.z
-  const int F1 = g.Fo[0], C = g.C;
-  const float* Wt = params + g.wt;
-  const float* bt = params + g.bt;
-  const float* Ws = params + g.ws;
-  for (int e = threadIdx.x; e < F1 * F1 * C; e += 256) {          // dWs[o,f,c]
-    const int c = e % C, f = (e / C) % F1, o = e / (C * F1);
-    float s = dbeff[o] * bt[f];
+struct ph_bwd_l1_kernel {
+  static constexpr int kBounds = 256;
+  static __device__ __forceinline__ void run(ZoneGrid zg, const float* __restrict__ params, float* __restrict__ dparams,
+                                             const float* __restrict__ dWeff, const float* __restrict__ dbeff,
+                                             PhGeo g) {
+    const int F1 = g.Fo[0], C = g.C;
+    const float* Wt = params + g.wt;
+    const float* bt = params + g.bt;
+    const float* Ws = params + g.ws;
+    for (int e = threadIdx.x; e < F1 * F1 * C; e += 256) {          // dWs[o,f,c]
+      const int c = e % C, f = (e / C) % F1, o = e / (C * F1);
+      float s = dbeff[o] * bt[f];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) s = fmaf(dWeff[(o * C + c) * 3 + k], Wt[f * 3 + k], s);
-    dparams[g.ws + e] = s;
-  }
-  for (int e = threadIdx.x; e < F1 * 3; e += 256) {               // dWt[f,k]
-    const int f = e / 3, k = e - f * 3;
-    float s = 0.f;
-    for (int o = 0; o < F1; ++o)
-      for (int c = 0; c < C; ++c) s = fmaf(dWeff[(o * C + c) * 3 + k], Ws[(o * F1 + f) * C + c], s);
-    dparams[g.wt + e] = s;
-  }
-  for (int f = threadIdx.x; f < F1; f += 256) {                   // dbt[f]
-    float s = 0.f;
-    for (int o = 0; o < F1; ++o) {
-      float ws = 0.f;
-      for (int c = 0; c < C; ++c) ws += Ws[(o * F1 + f) * C + c];
-      s = fmaf(dbeff[o], ws, s);
+      for (int k = 0; k < 3; ++k) s = fmaf(dWeff[(o * C + c) * 3 + k], Wt[f * 3 + k], s);
+      dparams[g.ws + e] = s;
     }
-    dparams[g.bt + f] = s;
+    for (int e = threadIdx.x; e < F1 * 3; e += 256) {               // dWt[f,k]
+      const int f = e / 3, k = e - f * 3;
+      float s = 0.f;
+      for (int o = 0; o < F1; ++o)
+        for (int c = 0; c < C; ++c) s = fmaf(dWeff[(o * C + c) * 3 + k], Ws[(o * F1 + f) * C + c], s);
+      dparams[g.wt + e] = s;
+    }
+    for (int f = threadIdx.x; f < F1; f += 256) {                   // dbt[f]
+      float s = 0.f;
+      for (int o = 0; o < F1; ++o) {
+        float ws = 0.f;
+        for (int c = 0; c < C; ++c) ws += Ws[(o * F1 + f) * C + c];
+        s = fmaf(dbeff[o], ws, s);
+      }
+      dparams[g.bt + f] = s;
+    }
   }
-}
-ISD_ZONE_FN(ph_bwd_l1_kernel, 256)
-__global__ __launch_bounds__(256) void ph_bwd_l1_kernel(const float* __restrict__ params, float* __restrict__ dparams,
-                                                        const float* __restrict__ dWeff, const float* __restrict__ dbeff,
-                                                        PhGeo g) {
-  ph_bwd_l1_kernel_body(params, dparams, dWeff, dbeff, g,
-      gridDim.x, gridDim.y, blockIdx.z, gridDim.z);
-}
-ISD_ZONE_REGISTER(ph_bwd_l1_kernel)
+};
 
 }  // namespace isd
 

@@ -35,7 +35,6 @@ __device__ long long tf_times[32];
 #define TF_MARK(k) do { } while (0)
 #endif
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void* tf_lds_ptr_t;
 typedef const __attribute__((address_space(1))) void* tf_gbl_ptr_t;
 

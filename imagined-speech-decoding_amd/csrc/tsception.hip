@@ -20,7 +20,6 @@
 namespace isd {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kMaxF = 16;        // num_T, num_S (one MFMA N tile)
 constexpr int kMaxH = 64;        // hidden

@@ -6,9 +6,12 @@
 // isd_zone_batch_launch() every kernel launch of this thread is RECORDED instead of issued (kernel, grid, block,
 // arguments); isd_zone_batch_next() closes a zone.  The launch then zips the zones' chains: launch i of every zone
 // is the same kernel, so it goes out ONCE with blockIdx.z = zone and the zones' argument tuples side by side in the
-// kernel argument block.  A kernel takes part through ISD_ZONE_FN + ISD_ZONE_REGISTER (its body is a __device__ function that gets
-// its own zone's grid size -- and blockIdx.z / gridDim.z -- as trailing arguments: grid-stride loops must not see the
-// other zones', and blockIdx.z is the zone in the multi-zone launch).
+// kernel argument block.  A zone-batchable kernel is a struct K that is written once: `kBounds` is its launch bound and
+// the static __device__ function `run(ZoneGrid, params...)` its code.  zone_kernel<K, params...> is the plain launch of
+// one zone, zone_multi_kernel<K, params...> the zipped one; run() gets its own zone's grid size -- and blockIdx.z /
+// gridDim.z -- in the ZoneGrid: grid-stride loops must not see the other zones', and blockIdx.z is the zone in the
+// multi-zone launch.  zone_launch<K>(grid, block, lds, stream, args...) issues or records; both kernels are named at
+// that launch site, so a kernel that can be launched can be zone-batched.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -16,7 +19,6 @@
 #include <cstring>
 #include <memory>
 #include <tuple>
-#include <unordered_map>
 #include <utility>
 #include <vector>
 
@@ -33,12 +35,33 @@ struct ZoneArgs {
   std::tuple<P...> a[kMaxBatchZones];
 };
 
+// this zone's own gridDim.x / .y, blockIdx.z and gridDim.z
+struct ZoneGrid {
+  unsigned gx, gy, bz, gz;
+};
+
 #if defined(__HIPCC__)
-template <typename Fn, typename... P>
-__global__ __launch_bounds__(Fn::kBounds) void zone_multi_kernel(ZoneArgs<P...> m) {
+// One zone: the plain launch.  Top-level __restrict__ is not part of run()'s type, so its pointer parameters would
+// reach the entry point without it, and the compiler would then order one zone's loads and stores as if its buffers
+// could overlap.  ZoneParam puts it back.  The rule that makes this right: EVERY pointer parameter of a run() is
+// __restrict__ (a kernel whose buffers may overlap takes them as one pointer and offsets).
+template <typename T>
+struct ZoneParam {
+  using type = T;
+};
+template <typename T>
+struct ZoneParam<T*> {
+  using type = T* __restrict__;
+};
+template <typename K, typename... P>
+__global__ __launch_bounds__(K::kBounds) void zone_kernel(typename ZoneParam<P>::type... a) {
+  K::run(ZoneGrid{gridDim.x, gridDim.y, blockIdx.z, gridDim.z}, a...);
+}
+template <typename K, typename... P>
+__global__ __launch_bounds__(K::kBounds) void zone_multi_kernel(ZoneArgs<P...> m) {
   const int z = blockIdx.z;
   if (blockIdx.x >= m.gx[z] || blockIdx.y >= m.gy[z]) return;      // outside this zone's own grid
-  std::apply([&](const P&... a) { Fn::call(a..., m.gx[z], m.gy[z], 0u, 1u); }, m.a[z]);
+  std::apply([&](const P&... a) { K::run(ZoneGrid{m.gx[z], m.gy[z], 0u, 1u}, a...); }, m.a[z]);
 }
 
 struct ZoneFill {
@@ -58,7 +81,7 @@ __global__ __launch_bounds__(256) inline void zone_fill_kernel(ZoneFill m) {
 struct ZoneOp {
   // kind 0: kernel; 1: clear
   int kind = 0;
-  const void* kernel = nullptr;                                     // the __global__ stub's address: the chain's identity
+  const void* kernel = nullptr;                                     // zone_kernel<K, P...>'s stub: the chain's identity
   // zips `n` recorded argument tuples (type-erased) into one launch
   hipError_t (*zip)(int n, const ZoneOp* const* ops, hipStream_t st) = nullptr;
   dim3 grid, block;
@@ -75,7 +98,7 @@ struct ZoneRecorder {
 ZoneRecorder& zone_recorder();                                      // thread-local (zonebatch.hip)
 
 #if defined(__HIPCC__)
-template <typename Fn, typename... P>
+template <typename K, typename... P>
 hipError_t zone_zip(int n, const ZoneOp* const* ops, hipStream_t st) {
   ZoneArgs<P...> m;
   m.n = n;
@@ -93,47 +116,55 @@ hipError_t zone_zip(int n, const ZoneOp* const* ops, hipStream_t st) {
     m.a[z] = m.a[0];
   }
   if (lds > 64 * 1024) {
-    const hipError_t e = hipFuncSetAttribute((const void*)zone_multi_kernel<Fn, P...>,
+    const hipError_t e = hipFuncSetAttribute((const void*)zone_multi_kernel<K, P...>,
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL((zone_multi_kernel<Fn, P...>), dim3(gx, gy, (unsigned)n), ops[0]->block, lds, st, m);
+  hipLaunchKernelGGL((zone_multi_kernel<K, P...>), dim3(gx, gy, (unsigned)n), ops[0]->block, lds, st, m);
   return hipGetLastError();
 }
 
-// registry: kernel stub -> zip function (filled by the static registrars of ISD_ZONE_REGISTER)
-std::unordered_map<const void*, hipError_t (*)(int, const ZoneOp* const*, hipStream_t)>& zone_registry();
-struct ZoneRegistrar {
-  ZoneRegistrar(const void* k, hipError_t (*zip)(int, const ZoneOp* const*, hipStream_t)) { zone_registry()[k] = zip; }
-};
-
-// Launch now, or record when a zone batch is open on this thread.  Returns false when the kernel cannot be recorded.
-template <typename... P, typename... A>
-bool zone_launch(void (*k)(P...), dim3 grid, dim3 block, unsigned lds, hipStream_t st, A&&... args) {
-  static_assert(sizeof...(P) == sizeof...(A), "argument count");
-  ZoneRecorder& r = zone_recorder();
-  if (!r.active) {
-    hipLaunchKernelGGL(k, grid, block, lds, st, static_cast<P>(args)...);
+// Launch K now, or record it when a zone batch is open on this thread.  Returns false when the launch cannot be
+// recorded.  The parameter types P... are those of K::run after its ZoneGrid.
+template <typename K, typename Run = decltype(&K::run)>
+struct ZoneLaunch;
+template <typename K, typename... P>
+struct ZoneLaunch<K, void (*)(ZoneGrid, P...)> {
+  template <typename... A>
+  static bool launch(dim3 grid, dim3 block, unsigned lds, hipStream_t st, A&&... args) {
+    static_assert(sizeof...(P) == sizeof...(A), "argument count");
+    ZoneRecorder& r = zone_recorder();
+    if (!r.active) {
+      hipLaunchKernelGGL((zone_kernel<K, P...>), grid, block, lds, st, static_cast<P>(args)...);
+      return true;
+    }
+    if (grid.z != 1) {
+      set_error("zone batch: a kernel of this call is not zone-batchable");
+      r.active = false;                                             // poison: isd_zone_batch_launch reports it
+      r.zones.clear();
+      return false;
+    }
+    ZoneOp op;
+    op.kind = 0;
+    op.kernel = reinterpret_cast<const void*>(&zone_kernel<K, P...>);
+    op.zip = &zone_zip<K, P...>;
+    op.grid = grid;
+    op.block = block;
+    op.lds = lds;
+    op.args = std::make_shared<std::tuple<P...>>(static_cast<P>(args)...);
+    r.zones.back().push_back(std::move(op));
     return true;
   }
-  auto it = zone_registry().find(reinterpret_cast<const void*>(k));
-  if (it == zone_registry().end() || grid.z != 1) {
-    set_error("zone batch: a kernel of this call is not zone-batchable");
-    r.active = false;                                               // poison: isd_zone_batch_launch reports it
-    r.zones.clear();
-    return false;
-  }
-  ZoneOp op;
-  op.kind = 0;
-  op.kernel = reinterpret_cast<const void*>(k);
-  op.zip = it->second;
-  op.grid = grid;
-  op.block = block;
-  op.lds = lds;
-  op.args = std::make_shared<std::tuple<P...>>(static_cast<P>(args)...);
-  r.zones.back().push_back(std::move(op));
-  return true;
+};
+template <typename K, typename... A>
+bool zone_launch(dim3 grid, dim3 block, unsigned lds, hipStream_t st, A&&... args) {
+  return ZoneLaunch<K>::launch(grid, block, lds, st, std::forward<A>(args)...);
 }
+// every launch of a zone-batchable kernel goes through zone_launch; a refused record ends the calling function
+#define ISD_ZLAUNCH(K, ...)                                      \
+  do {                                                           \
+    if (!zone_launch<K>(__VA_ARGS__)) return ISD_ERR_INVALID;    \
+  } while (0)
 
 // hipMemsetAsync(ptr, 0, bytes) -- or its record (ptr and bytes must be multiples of 4)
 inline hipError_t zone_clear(void* ptr, size_t bytes, hipStream_t st) {
@@ -147,38 +178,6 @@ inline hipError_t zone_clear(void* ptr, size_t bytes, hipStream_t st) {
   return hipSuccess;
 }
 
-// A zone-batchable kernel NAME: `NAME_body(params..., zgx, zgy, zbz, zgz)` is the __device__ body (zgx / zgy / zgz
-// stand for gridDim.x / .y / .z of the zone's own launch, zbz for its blockIdx.z).  ISD_ZONE_FN defines the functor the
-// multi-zone kernel calls, ISD_ZONE_REGISTER ties it to the plain __global__ entry point (kernel templates:
-// ISD_ZONE_FN_T, then one ISD_ZONE_REGISTER_T per instantiation that is launched; further entry points onto the same
-// body: ISD_ZONE_REGISTER_AS / ISD_ZONE_REGISTER_T_AS).
-#define ISD_ZONE_FN(NAME, BOUNDS)                                                        \
-  struct NAME##_zfn {                                                                    \
-    static constexpr int kBounds = BOUNDS;                                               \
-    template <typename... A>                                                             \
-    __device__ __forceinline__ static void call(A... a) { NAME##_body(a...); }           \
-  };
-template <typename Fn, typename... P>
-auto zone_zip_of(void (*)(P...)) -> hipError_t (*)(int, const ZoneOp* const*, hipStream_t) { return &zone_zip<Fn, P...>; }
-#define ISD_ZONE_REGISTER(NAME) \
-  static ZoneRegistrar NAME##_zreg(reinterpret_cast<const void*>(&NAME), zone_zip_of<NAME##_zfn>(&NAME));
-// kernel templates: functor template via ISD_ZONE_FN_T, one registration per launched instantiation
-#define ISD_ZONE_FN_T(NAME, BOUNDS, TPARAM)                                              \
-  template <TPARAM V>                                                                    \
-  struct NAME##_zfn {                                                                    \
-    static constexpr int kBounds = BOUNDS;                                               \
-    template <typename... A>                                                             \
-    __device__ __forceinline__ static void call(A... a) { NAME##_body<V>(a...); }        \
-  };
-#define ISD_ZONE_REGISTER_T(NAME, V) \
-  static ZoneRegistrar NAME##_zreg_##V(reinterpret_cast<const void*>(&NAME<V>), zone_zip_of<NAME##_zfn<V>>(&NAME<V>));
-// a second entry point KERNEL onto the body of NAME -- e.g. an instance for another input element type, which the
-// body (a function template) deduces from its arguments
-#define ISD_ZONE_REGISTER_AS(KERNEL, NAME) \
-  static ZoneRegistrar KERNEL##_zreg(reinterpret_cast<const void*>(&KERNEL), zone_zip_of<NAME##_zfn>(&KERNEL));
-#define ISD_ZONE_REGISTER_T_AS(KERNEL, NAME, V)                                                      \
-  static ZoneRegistrar KERNEL##_zreg_##V(reinterpret_cast<const void*>(&KERNEL<V>),                  \
-                                         zone_zip_of<NAME##_zfn<V>>(&KERNEL<V>));
 #endif  // __HIPCC__
 
 }  // namespace isd

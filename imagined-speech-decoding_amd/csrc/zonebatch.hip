@@ -1,4 +1,4 @@
-// Recorder, registry and C ABI of the zone-batched launches (zonebatch.h).
+// Recorder and C ABI of the zone-batched launches (zonebatch.h).
 #include "zonebatch.h"
 
 #include "../../include/isd_hip.h"
@@ -10,11 +10,6 @@ ZoneRecorder& zone_recorder() {
   return r;
 }
 bool zone_batch_open() { return zone_recorder().active; }
-
-std::unordered_map<const void*, hipError_t (*)(int, const ZoneOp* const*, hipStream_t)>& zone_registry() {
-  static std::unordered_map<const void*, hipError_t (*)(int, const ZoneOp* const*, hipStream_t)> m;
-  return m;
-}
 
 }  // namespace isd
 

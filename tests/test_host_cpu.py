@@ -217,6 +217,106 @@ def test_zone_batch_recorder_states_without_a_gpu():
     assert lib.isd_zone_batch_launch(None) == 0
 
 
+class _ZoneBatch:
+    """Recording needs no device: one host buffer stands in for every pointer, and nothing recorded is ever issued
+    (every case ends in a refusal or in isd_zone_batch_abort).  Without a device the recorded call's own launch check
+    may report ISD_ERR_HIP after it has recorded, so `rec` accepts both."""
+
+    def __init__(self):
+        import isd_amd._lib as L
+        self.L, self.lib = L, L.lib()
+        self.buf = np.zeros(1 << 19, np.float32)
+        self.p = self.buf.ctypes.data
+
+    def __enter__(self):
+        self.lib.isd_zone_batch_abort()
+        assert self.lib.isd_zone_batch_begin() == 0
+        return self
+
+    def __exit__(self, *exc):
+        assert self.lib.isd_zone_batch_abort() == 0
+
+    def rec(self, rc):
+        assert rc in (self.L.ISD_OK, self.L.ISD_ERR_HIP), (rc, self.lib.isd_last_error())
+
+    def linear_forward(self, M=4, K=8, N=8):
+        p = self.p
+        return self.lib.isd_linear_forward(p, p, p, p, None, M, K, N, 0, None)
+
+    def refused(self, text):
+        assert self.lib.isd_zone_batch_launch(None) == self.L.ISD_ERR_INVALID
+        assert text in self.lib.isd_last_error(), self.lib.isd_last_error()
+
+    def eegnet_plan(self, kernel_length, bf16=False):
+        plan = ctypes.c_void_p()
+        assert self.lib.isd_eegnet_plan_create(ctypes.byref(plan), 8, 16, kernel_length, 128) == 0, \
+            self.lib.isd_last_error()
+        if bf16:
+            assert self.lib.isd_eegnet_plan_set_input_dtype(plan, 1) == 0              # ISD_ACT_BF16
+        assert self.lib.isd_eegnet_workspace_bytes(plan, 4) <= self.buf.nbytes
+        return plan
+
+    def eegnet_stage(self, plan, stage):
+        p = self.p
+        return self.lib.isd_eegnet_forward_stage(plan, stage, p, p, p, p, p, 4, 1, 0.1, 1e-5, 0.0, 0, 1, None)
+
+
+def test_zone_batch_refuses_different_kernels_in_one_slot():
+    with _ZoneBatch() as zb:
+        zb.rec(zb.linear_forward())
+        assert zb.lib.isd_zone_batch_next() == 0
+        zb.rec(zb.lib.isd_softmax_ce(zb.p, None, 8, zb.p, None, None, zb.p, 4, 3, 5, 1.0, None, None))
+        zb.refused(b"differs between zone 0 and zone 1")
+
+
+@pytest.mark.parametrize("what,stage,launch", [("kernel_length", 1, 2), ("element_type", 0, 1)])
+def test_zone_batch_tells_instantiations_of_one_kernel_apart(what, stage, launch):
+    """Two instantiations of one kernel template (the temporal convolution at two filter lengths: launch 2 of stage 1)
+    and two element types of one kernel (the fp32 and the bf16 statistics pass: launch 1 of stage 0) are different
+    kernels to the recorder.  Their recorded argument tuples are type-erased: zipping them would corrupt memory."""
+    with _ZoneBatch() as zb:
+        plans = [zb.eegnet_plan(64), zb.eegnet_plan(32) if what == "kernel_length" else zb.eegnet_plan(64, bf16=True)]
+        try:
+            zb.rec(zb.eegnet_stage(plans[0], stage))
+            assert zb.lib.isd_zone_batch_next() == 0
+            zb.rec(zb.eegnet_stage(plans[1], stage))
+            zb.refused(b"launch %d differs between zone 0 and zone 1" % launch)
+        finally:
+            for plan in plans:
+                zb.lib.isd_eegnet_plan_destroy(plan)
+
+
+def test_zone_batch_refuses_unequal_chain_lengths():
+    with _ZoneBatch() as zb:
+        zb.rec(zb.linear_forward())
+        zb.rec(zb.linear_forward())
+        assert zb.lib.isd_zone_batch_next() == 0
+        zb.rec(zb.linear_forward())
+        zb.refused(b"zone 1 recorded 1 launches, zone 0 2")
+
+
+def test_zone_batch_refuses_grid_z_at_record_time():
+    """isd_linear_backward splits the output features over blockIdx.z in chunks of 64: N = 65 cannot be zone-batched,
+    and the refusal poisons the batch; N = 8 records."""
+    def backward(zb, N):
+        p = zb.p
+        return zb.lib.isd_linear_backward(p, p, p, None, None, p, p, p, 4, 8, N, 0, None)
+    with _ZoneBatch() as zb:
+        assert backward(zb, 65) == zb.L.ISD_ERR_INVALID
+        assert b"not zone-batchable" in zb.lib.isd_last_error()
+        zb.refused(b"no zone batch is open")
+    with _ZoneBatch() as zb:
+        zb.rec(backward(zb, 8))
+
+
+def test_zone_batch_refuses_a_ninth_zone():
+    with _ZoneBatch() as zb:
+        for _ in range(7):
+            assert zb.lib.isd_zone_batch_next() == 0
+        assert zb.lib.isd_zone_batch_next() == zb.L.ISD_ERR_INVALID
+        assert b"more than 8 zones" in zb.lib.isd_last_error()
+
+
 def test_optimizers_reject_what_the_hip_kernels_cannot_take():
     """isd_amd.FusedAdamW / Trainer are HIP-only (no silent torch fallback): host tensors and inconsistent options are
     refused with a message, before any launch."""
