@@ -1037,6 +1037,38 @@ __device__ __forceinline__ void fused_layer_store(const f32x4 (&acc)[16 / NW][2]
   }
 }
 
+// Where the LDS regions of conv4_fused_fwd_kernel<NW> start, in floats from the start of its dynamic allocation, and
+// where the last one ends.  The kernel takes its pointers from here and conv4_fused_fwd_lds its size, so the two cannot
+// disagree; conv4_fused_fwd_layout_ok states the rule (regions in this order, none reaching into the next, t2 / t3 on
+// 16 bytes for their float4 copies, the end inside the allocation) and choose_route checks it for the shape of every call.
+struct FusedFwdLds {
+  int xz, t2, t3, red, we, w3s, w4s, bls, end;
+};
+__host__ __device__ constexpr FusedFwdLds conv4_fused_fwd_layout(int NW, int F, int W, int T1) {
+  FusedFwdLds l = {};
+  const int tile = (F * T1 + 3) & ~3, frag = kTaps * 2 * 64;
+  l.xz = 4;                                          // 4 floats of slack in front: the pad-0 / pad-2 masked reads
+  l.t2 = l.xz + ((16 * W + 3) & ~3);
+  l.t3 = l.t2 + tile;
+  l.red = l.t3 + tile;
+  l.we = l.red + NW * F;
+  l.w3s = l.we + 4 * frag;
+  l.w4s = l.w3s + 8 * frag;
+  l.bls = l.w4s + 8 * frag;
+  l.end = l.bls + 64;
+  return l;
+}
+__host__ __device__ constexpr bool conv4_fused_fwd_layout_ok(int NW, int F, int W, int T1, size_t lds_bytes) {
+  const FusedFwdLds l = conv4_fused_fwd_layout(NW, F, W, T1);
+  const int frag = kTaps * 2 * 64;
+  const int start[9] = {l.xz, l.t2, l.t3, l.red, l.we, l.w3s, l.w4s, l.bls, l.end};
+  const int len[8] = {16 * W, F * T1, F * T1, NW * F, 4 * frag, 8 * frag, 8 * frag, F};
+  if (l.xz < 4 || l.t2 % 4 != 0 || l.t3 % 4 != 0) return false;
+  for (int i = 0; i < 8; ++i)
+    if (len[i] < 0 || start[i] + len[i] > start[i + 1]) return false;
+  return sizeof(float) * (size_t)l.end <= lds_bytes;
+}
+
 template <int NW>
 __global__ __launch_bounds__(NW * 64) void conv4_fused_fwd_kernel(FusedFwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -1046,14 +1078,15 @@ __global__ __launch_bounds__(NW * 64) void conv4_fused_fwd_kernel(FusedFwdArgs a
   const int cz = zd.cin, ncg = (cz + 3) / 4;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane >> 4, jl = lane & 15;
   const int T1 = a.T1, W = a.W, TT = a.TT;
-  float* xz = smem + 4;                              // [16][W]  (4 floats of slack before every tile)
-  float* t2 = smem + ((16 * W + 3) & ~3);            // [32][T1]
-  float* t3 = t2 + ((F * T1 + 3) & ~3);              // [32][T1]
-  float* red = t3 + ((F * T1 + 3) & ~3);             // [8][32]
-  float* we = red + NW * F;                           // [4][5][2][64]   frag-ordered Weff of the zone
-  float* w3s = we + 4 * kTaps * 2 * 64;              // [8][5][2][64]
-  float* w4s = w3s + 8 * kTaps * 2 * 64;
-  float* bls = w4s + 8 * kTaps * 2 * 64;             // [32] beff (in the 64 floats of slack behind the fragments)
+  const FusedFwdLds L = conv4_fused_fwd_layout(NW, F, W, T1);   // the same offsets size the allocation (choose_route checks them)
+  float* xz = smem + L.xz;                           // [16][W]  (4 floats of slack in front: masked reads touch them)
+  float* t2 = smem + L.t2;                           // [32][T1]
+  float* t3 = smem + L.t3;                           // [32][T1]
+  float* red = smem + L.red;                         // [8][32]
+  float* we = smem + L.we;                           // [4][5][2][64]   frag-ordered Weff of the zone
+  float* w3s = smem + L.w3s;                         // [8][5][2][64]
+  float* w4s = smem + L.w4s;
+  float* bls = smem + L.bls;                         // [32] beff (in the 64 floats of slack behind the fragments)
   // ---- weight fragments into LDS once per (persistent) workgroup
   for (int e = threadIdx.x; e < 4 * kTaps * 2 * 64; e += NW * 64) we[e] = (e < ncg * kTaps * 2 * 64) ? a.weff[zd.eff_off + e] : 0.f;
   for (int e = threadIdx.x; e < 8 * kTaps * 2 * 64; e += NW * 64) {
@@ -1213,11 +1246,10 @@ __global__ __launch_bounds__(NW * 64) void conv4_fused_fwd_kernel(FusedFwdArgs a
   }
 }
 
-// dynamic LDS of conv4_fused_fwd_kernel<NW> (xz .. bls at its top): 4 floats of slack, xz [16][W], t2 and t3 [F][T1],
+// dynamic LDS of conv4_fused_fwd_kernel<NW> (conv4_fused_fwd_layout): 4 floats of slack, xz [16][W], t2 and t3 [F][T1],
 // red [NW][F], the Weff / cnn3 / cnn4 fragment sets of 4 + 8 + 8 blocks, 64 floats of slack holding beff
 static size_t conv4_fused_fwd_lds(int NW, int F, int W, int T1) {
-  return sizeof(float) * (size_t)(4 + ((16 * W + 3) & ~3) + 2 * ((F * T1 + 3) & ~3) + NW * F +
-                                  (4 + 8 + 8) * kTaps * 2 * 64 + 64);
+  return sizeof(float) * (size_t)conv4_fused_fwd_layout(NW, F, W, T1).end;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -3730,6 +3762,15 @@ int per_zone_workgroups(const isd_conv4_plan* p, const Geo& g, int per_gpu) {
   return per_zone;
 }
 
+// every window the fused fp32 route admits (4 <= TT <= 16: 53 <= W <= 260) against the 150 KiB the route allows,
+// when this file is compiled; choose_route repeats the check for the shape and allocation of the call
+constexpr bool fused_fwd_layout_ok_for_every_window() {
+  for (int W = 53; W <= 260; ++W)
+    if (!conv4_fused_fwd_layout_ok(kFusedNW, 32, W, W - (kTaps - 1), 150 * 1024)) return false;
+  return true;
+}
+static_assert(fused_fwd_layout_ok_for_every_window(), "conv4_fused_fwd_kernel: LDS regions overlap or exceed 150 KiB");
+
 int choose_route(const isd_conv4_plan* p, Geo& g) {
   const int F = p->F;
   const size_t bwd16 = conv4_fused_bwd_bf16_lds(g.TT);
@@ -3756,6 +3797,10 @@ int choose_route(const isd_conv4_plan* p, Geo& g) {
     g.bwd_lds = conv4_fused_bwd_lds(F, p->W, g.T1);
     ISD_CHECK_ARG(g.fwd_lds <= 150 * 1024 && g.bwd_lds <= 160 * 1024,
                   "conv4: the fused fp32 kernels need %zu / %zu bytes of LDS at window_len=%d", g.fwd_lds, g.bwd_lds, p->W);
+    // the forward's regions follow one another without overlap and end inside the allocation (an overlap of xz and t2
+    // was a race between waves: wrong features from run to run, never a fault)
+    ISD_CHECK_ARG(conv4_fused_fwd_layout_ok(kFusedNW, F, p->W, g.T1, g.fwd_lds),
+                  "conv4: the fused fp32 forward's LDS regions overlap at window_len=%d", p->W);
     g.fwd_per_zone = g.bwd_per_zone = per_zone_workgroups(p, g, 256);
     g.keep_dgelu = true;
   }
@@ -3937,8 +3982,9 @@ static bool bf16_mfma_ok(const isd_conv4_plan* p, const Geo& g, const void* x) {
 
 // What isd_first_layer_last_path() reports: the kernels the calling thread's last first-layer forward and weight
 // gradient launched.  Forward (low four bits): 0 conv5_fwd_kernel, 1..4 conv5_fwd_glds_kernel<2, 2>, <2, 4>, <1, 2>,
-// <1, 4>, 5 conv5_fwd_bf16_kernel.  Weight gradient (the bits above): 0 conv5_wgrad_kernel, 1 conv5_wgrad_wide_kernel,
-// 2 conv5_wgrad_wide_bf16_kernel.
+// <1, 4>, 5 conv5_fwd_bf16_kernel; the fused routes have no separate first layer and report the whole forward:
+// 6 conv4_fused_fwd_kernel, 7 conv4_fused_fwd_bf16_kernel.  Weight gradient (the bits above): 0 conv5_wgrad_kernel,
+// 1 conv5_wgrad_wide_kernel, 2 conv5_wgrad_wide_bf16_kernel (the fused backward kernels leave it as it was).
 static thread_local int g_first_fwd_path = 0, g_first_wgrad_path = 0;
 extern "C" int isd_first_layer_last_path(void) { return g_first_fwd_path + 16 * g_first_wgrad_path; }
 
@@ -4003,6 +4049,7 @@ static int fused_forward(const isd_conv4_plan* p, const Geo& g, const float* x, 
   const FusedFwdArgs fa = make_fused_fwd_args(p, g, x, feat, ws, T);
   void (*k)(FusedFwdArgs) = conv4_fused_fwd_bf16_kernel<kFusedNW>;
   if (g.route == Route::kFusedF32) k = conv4_fused_fwd_kernel<kFusedNW>;
+  g_first_fwd_path = g.route == Route::kFusedF32 ? 6 : 7;
   return launch_lds(k, dim3(g.fwd_per_zone, p->Z), dim3(kFusedNW * 64), g.fwd_lds, st, fa);
 }
 

@@ -465,8 +465,10 @@ int isd_featcnn_supported(const isd_conv4_plan* plan, int64_t B, int64_t T, int 
 /* Which kernels the calling thread's last first-layer forward and weight gradient launched (isd_conv4_forward /
  * _backward on the layerwise route, isd_featcnn_step): forward + 16 * weight gradient.  Forward: 0 the general
  * kernel, 1..4 the LDS-DMA kernel for wide inputs as <filter tiles, column tiles per wave> = <2, 2>, <2, 4>, <1, 2>,
- * <1, 4>, 5 the bf16 matrix-core kernel.  Weight gradient: 0 general, 1 wide fp32, 2 wide bf16.  For tests: a
- * fall-back to another kernel must not pass for the intended one. */
+ * <1, 4>, 5 the bf16 matrix-core kernel.  On the fused routes isd_conv4_forward runs the whole stack in one kernel
+ * and reports that instead: 6 the fused fp32 forward, 7 the fused bf16 forward (the fused backward kernels leave the
+ * weight-gradient code as it was).  Weight gradient: 0 general, 1 wide fp32, 2 wide bf16.  For tests: a fall-back to
+ * another kernel must not pass for the intended one. */
 int isd_first_layer_last_path(void);
 int isd_featcnn_step(const isd_conv4_plan* plan, const float* x, const float* params, const float* fc_w,
                      const float* fc_b, const void* labels, int label_bytes, float* dparams, float* dfc,

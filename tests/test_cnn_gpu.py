@@ -75,12 +75,11 @@ def test_input_gradient_through_windows_and_zones_vs_oracle(inn):
                                                       (128, 17, 16, 4, 7), (100, 20, 32, 2, 33), (320, 9, 32, 4, 1),
                                                       (68, 17, 16, 2, 300), (200, 40, 32, 4, 5),
                                                       # either side of each boundary of the fused fp32 route:
-                                                      # TT = 4 / 3, TT = 16 / 17, 17 channels.  The fused side of the last
-                                                      # two has 15 channels, not 16: with 16 the fused forward has an open
-                                                      # race (the last four samples of x row 15 share LDS with t2[0][0..3];
-                                                      # (16, 260, 32, 4, 2) gives 1.7e-7 or 1e-3 .. 3e-3 from run to run)
+                                                      # TT = 4 / 3, TT = 16 / 17, 17 channels.  16 channels is the widest
+                                                      # zone the fused route takes (tests/test_conv4_fused_gpu.py)
                                                       (8, 53, 32, 4, 3), (8, 52, 32, 4, 3), (15, 260, 32, 4, 2),
-                                                      (16, 261, 32, 4, 2), (17, 100, 32, 4, 3)])
+                                                      (16, 261, 32, 4, 2), (17, 100, 32, 4, 3), (16, 260, 32, 4, 2),
+                                                      (16, 250, 32, 4, 2)])
 def test_conv4layers_vs_oracle_shapes(inn, channels, T, dim, n_layers, B):
     p = ocnn.init_conv4_params(channels, dim, seed=channels + T, n_layers=n_layers)
     m = inn.Conv4Layers(channels, dim, n_layers).cuda()
