@@ -11,8 +11,9 @@ from .features import FeatureExtractor, Filterbank, Stft, band_bins, extract_fea
 from .bandpass import FirFilter, filter_data  # noqa: F401
 from .csp import CSP  # noqa: F401
 from .ica import ICA  # noqa: F401
+from .psd import psd_array_welch  # noqa: F401
 from .filter_design import butter_bandpass_resonators, butter_bandpass_sos, fir_design  # noqa: F401
-from . import csp, data, experiment, explain, ica  # noqa: F401
+from . import csp, data, experiment, explain, ica, psd  # noqa: F401
 from .optim import FusedAdamW  # noqa: F401
 from .classifier import (EEGNetPath, FASTHeadClassifier, FilterbankCNNClassifier,  # noqa: F401
                          FilterbankEEGNetClassifier, GradientBucket, HotPath, NotFittedError, Trainer,
@@ -22,4 +23,5 @@ from . import nn  # noqa: F401
 __all__ = ["TSceptionClassifier", "TSceptionPath", "nn", "FusedAdamW", "FilterbankCNNClassifier", "FilterbankEEGNetClassifier", "FASTHeadClassifier", "EEGNetPath", "NotFittedError", "Trainer", "HotPath", "GradientBucket",
            "cosine_scheduler", "lr_multiplier", "extract_features", "FeatureExtractor", "Filterbank", "Stft", "band_bins", "butter_bandpass_sos",
            "butter_bandpass_resonators", "BANDS_5", "BANDS_9", "BANDS_40", "CLASSES", "ELECTRODES", "ZONES",
-           "zone_index_lists", "data", "experiment", "explain", "FirFilter", "filter_data", "fir_design", "CSP", "csp", "ICA", "ica"]
+           "zone_index_lists", "data", "experiment", "explain", "FirFilter", "filter_data", "fir_design", "CSP", "csp", "ICA", "ica",
+           "psd_array_welch", "psd"]

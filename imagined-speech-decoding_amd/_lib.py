@@ -73,6 +73,13 @@ SIGNATURES = {
     "isd_ica_step_f64": (_i, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i, _i, _i, _p]),
     "isd_spatial_apply_f32": (_i, [_p, _p, _p, _p, _i64, _i, _i, _i, _p]),
     "isd_spatial_apply_f64": (_i, [_p, _p, _p, _p, _i64, _i, _i, _i, _p]),
+    "isd_psd_plan_create": (_i, [C.POINTER(_p), _i, _i, _i, _i, _i, _pd, C.c_double, _i]),
+    "isd_psd_plan_destroy": (_i, [_p]),
+    "isd_psd_plan_bins": (_i, [_p]),
+    "isd_psd_plan_segments": (_i64, [_p, _i64]),
+    "isd_psd_work_bytes": (_i64, [_p, _i64, _i64, _i]),
+    "isd_psd_welch_f32": (_i, [_p, _p, _p, _i64, _i64, _i, _p, _p]),
+    "isd_psd_welch_f64": (_i, [_p, _p, _p, _i64, _i64, _i, _p, _p]),
     "isd_conv4_plan_create": (_i, [C.POINTER(_p), _i, _i, _pi, _pi, _i, _i, _i, _i]),
     "isd_conv4_plan_destroy": (_i, [_p]),
     "isd_conv4_plan_set_activation_dtype": (_i, [_p, _i]),

@@ -245,6 +245,37 @@ int isd_spatial_apply_f64(const double* x, const double* M, const double* bias, 
                           int R, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Welch power spectral density: the data-sized step of
+ *   raw.compute_psd(method='welch') -> mne.time_frequency.psd_array_welch   scripts/artifact_analysis.py:45
+ * as scipy.signal.welch / spectrogram(scaling='density') compute it.  Segment s of a row is samples
+ * s * step .. s * step + n_per_seg - 1 (step = n_per_seg - n_overlap), S = (T - n_per_seg) / step + 1 whole segments,
+ * no boundary extension; samples after the last whole segment are not read.  Each segment has its mean removed (if
+ * remove_dc), is multiplied by `window` [n_per_seg] (host, double), zero-padded to n_fft, and the one-sided power of
+ * bins k_lo .. k_hi is scaled to a density:  |X_k|^2 c_k / (sfreq sum w^2),  c_k = 2 except 1 at k = 0 and at
+ * k = n_fft / 2 for even n_fft.  The transform is a dense product with a windowed cos / sin table the plan owns (one
+ * copy per precision): only the kept bins cost arithmetic.
+ *
+ * x [rows][T] -> out [rows][K] the mean over segments, or with per_segment != 0 out [rows][K][S]; K = k_hi - k_lo + 1.
+ * The _f32 entry multiplies and accumulates in fp32 on the fp32-input matrix cores, the _f64 entry in fp64; the
+ * segment means are taken in fp64 in both.  `work`: isd_psd_work_bytes bytes of scratch.  Sums run in segment order
+ * with no atomics: bitwise repeatable.  x needs element alignment only.  All data pointers are device memory; no call
+ * synchronises with the host.
+ * Envelope: 2 <= n_fft <= 2048, 1 <= n_per_seg <= n_fft, 0 <= n_overlap < n_per_seg, 0 <= k_lo <= k_hi <= n_fft / 2,
+ * T >= n_per_seg, any rows >= 0 (rows = 0 returns at once); outside it ISD_ERR_UNSUPPORTED.
+ * ---------------------------------------------------------------------- */
+typedef struct isd_psd_plan isd_psd_plan;
+int isd_psd_plan_create(isd_psd_plan** out, int n_fft, int n_per_seg, int n_overlap, int k_lo, int k_hi,
+                        const double* window /* host [n_per_seg] */, double sfreq, int remove_dc);
+int isd_psd_plan_destroy(isd_psd_plan* plan);
+int isd_psd_plan_bins(const isd_psd_plan* plan);                    /* K */
+int64_t isd_psd_plan_segments(const isd_psd_plan* plan, int64_t T); /* S, 0 if T < n_per_seg */
+int64_t isd_psd_work_bytes(const isd_psd_plan* plan, int64_t rows, int64_t T, int is_f64);
+int isd_psd_welch_f32(const isd_psd_plan* plan, const float* x, float* out, int64_t rows, int64_t T, int per_segment,
+                      void* work, void* stream);
+int isd_psd_welch_f64(const isd_psd_plan* plan, const double* x, double* out, int64_t rows, int64_t T, int per_segment,
+                      void* work, void* stream);
+
+/* ------------------------------------------------------------------------
  * Zone-wise Conv4Layers stack over sliding windows: the reference's
  *   FAST.forward_head   src/fast/models/fast.py:242-252  (unfold window_len / slide_step)
  *   Head.forward        src/fast/models/fast.py:209-210  (zone gather, one encoder per zone, stack)
