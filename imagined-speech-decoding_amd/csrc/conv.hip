@@ -34,6 +34,28 @@ struct ZoneDesc {
   int64_t wg_off;   // offset of the zone's dWeff block [F][Cz+1][5] in the wgrad result
 };
 
+// Dynamic LDS.  Every kernel of this file that takes a dynamic allocation has ONE constexpr `*_layout` function: the
+// kernel takes its pointers and LDS addresses from the struct it returns, the host takes the allocation's size from the
+// same struct's `end`, and static_asserts (in front of choose_route) check it for every shape the kernel's route admits.
+// LdsCarver hands out the regions front to back: a region starts where the one before it ended (rounded up to `align`,
+// a power of two: the mask is the `(x + 3) & ~3` the kernels always used), so two regions cannot overlap, and slack is
+// a `take` of its own.
+struct LdsCarver {
+  int end = 0;
+  __host__ __device__ constexpr int take(int n, int align = 1) {
+    const int at = (end + align - 1) & ~(align - 1);
+    end = at + n;
+    return at;
+  }
+};
+constexpr int kLdsWorkgroup = 160 * 1024;   // what the CU has, and the most one workgroup can take
+constexpr int kLdsRoute = 150 * 1024;       // what the large-tile routes allow themselves of it
+constexpr int kLdsTwoPerCu = 80 * 1024;     // half of the CU: two workgroups fit side by side
+constexpr int kLdsStage96K = 96 * 1024;     // staging: conv5_wgrad_kernel's stage of several items
+constexpr int kLdsStage64K = 64 * 1024;     // staging: the forward's tile of IPW items, the wide weight gradient's two buffers
+constexpr int kLdsStage48K = 48 * 1024;     // staging: the wide weight gradient's items per stage (three workgroups per CU)
+constexpr int kLdsStage32K = 32 * 1024;     // staging: conv5_wgrad_kernel when several workgroups are to share a CU
+
 // Activation storage type: float, or bf16 (config 3: bf16 activations / activation gradients, fp32
 // accumulate).  Values are rounded to bf16 (RNE) where they are stored and where operands are staged, so
 // the products equal those of a bf16 MFMA with fp32 accumulation; the MFMA itself stays the fp32 one.
@@ -323,6 +345,29 @@ struct ConvArgs {
 // LDS rows are unpadded copies of the source rows (stride RS >= Tin); zero padding, the ragged last
 // time tile and the channel round-up are handled by masking the B fragment, so staging moves only
 // real data (float4 when the block is contiguous and aligned).
+//
+// LDS of conv5_fwd_kernel (one buffer), conv5_fwd_glds_kernel and conv5_fwd_bf16_kernel (two buffers), in floats:
+// 4 floats of slack (masked reads may address up to `pad` elements before row 0), then per buffer in_tile [IPW][CK][RS],
+// w_tile of `w_len` floats on 16 bytes and 32 floats of slack (junk columns and dead lanes read past the last row).
+// Buffer s has its in_tile at in + s * buf_len and its w_tile at w + s * buf_len.
+struct Conv5FwdLds {
+  int in, w, buf_len, end;
+};
+__host__ __device__ constexpr Conv5FwdLds conv5_fwd_layout(int n_buf, int IPW, int CK, int RS, int w_len) {
+  LdsCarver c;
+  Conv5FwdLds l = {};
+  c.take(4);
+  l.in = c.take(IPW * CK * RS);
+  l.w = c.take(w_len, 4);
+  c.take(32);
+  l.buf_len = c.end - l.in;                                // a multiple of 4 floats: the second buffer's w_tile is aligned, too
+  c.take((n_buf - 1) * l.buf_len);
+  l.end = c.end;
+  return l;
+}
+__host__ __device__ constexpr int conv5_fwd_w_len(int CK, int GT) { return (CK / 4) * kTaps * GT * 64; }   // [CK/4][5][GT][64]
+constexpr int kConv5FwdBf16WLen = (kCK / 4) * 2 * 64 * 4;   // conv5_fwd_bf16_kernel<2, ...>: [kCK/4][GT = 2][64] fragments of 16 bytes
+
 template <int MODE, typename AT, int GT, int NT>
 __global__ __launch_bounds__(256) void conv5_fwd_kernel(ConvArgs a) {
   using IT = typename std::conditional<MODE == 0, float, AT>::type;   // storage type of the input
@@ -335,9 +380,9 @@ __global__ __launch_bounds__(256) void conv5_fwd_kernel(ConvArgs a) {
   const int64_t item0 = (int64_t)blockIdx.x * a.IPW;
   const int n_items = (int)((a.items - item0) < a.IPW ? (a.items - item0) : a.IPW);
   const int n_ct = n_items * a.TT;
-  float* in_tile = smem + 4;                               // [IPW][CK][RS]; 4 floats of slack: masked reads may
-                                                           // address up to `pad` elements before row 0
-  float* w_tile = smem + 4 + ((a.IPW * CK * a.RS + 3) & ~3);  // [CK/4][5][GT][64], 16-byte aligned
+  const Conv5FwdLds L = conv5_fwd_layout(1, a.IPW, CK, a.RS, conv5_fwd_w_len(CK, GT));
+  float* in_tile = smem + L.in;                            // [IPW][CK][RS]
+  float* w_tile = smem + L.w;                              // [CK/4][5][GT][64], 16-byte aligned
   const float* wbase = a.wfrag + ((MODE == 0) ? zd.eff_off : (int64_t)z * a.wz_stride);
   const int n_chunks = (cin + CK - 1) / CK;
   const int q = lane >> 4, jl = lane & 15;
@@ -487,10 +532,8 @@ __global__ __launch_bounds__(256) void conv5_fwd_kernel(ConvArgs a) {
   }
 }
 
-// dynamic LDS of conv5_fwd_kernel (the in_tile / w_tile lines at its top): 4 floats of slack, in_tile [IPW][CK][RS]
-// rounded up to 16 bytes, w_tile [CK/4][5][GT][64], 32 floats of slack behind it
 static size_t conv5_fwd_lds(int IPW, int CK, int RS, int GT) {
-  return sizeof(float) * (4 + (((size_t)IPW * CK * RS + 3) & ~(size_t)3) + (size_t)(CK / 4) * kTaps * GT * 64 + 32);
+  return sizeof(float) * (size_t)conv5_fwd_layout(1, IPW, CK, RS, conv5_fwd_w_len(CK, GT)).end;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -516,17 +559,16 @@ __global__ __launch_bounds__(256) void conv5_fwd_glds_kernel(ConvArgs a) {
   const int64_t item0 = (int64_t)blockIdx.x * a.IPW;
   const int n_items = (int)((a.items - item0) < a.IPW ? (a.items - item0) : a.IPW);
   const int n_ct = n_items * a.TT;
-  const int in_len = (a.IPW * kCK * a.RS + 3) & ~3;
-  constexpr int w_len = (kCK / 4) * kTaps * GT * 64;
-  const int buf_len = in_len + w_len + 32;                  // 32 floats of slack: junk columns read past the last row
+  constexpr int w_len = conv5_fwd_w_len(kCK, GT);
+  const Conv5FwdLds L = conv5_fwd_layout(2, a.IPW, kCK, a.RS, w_len);
   const float* wbase = a.wfrag + zd.eff_off;
   const int n_chunks = (cin + kCK - 1) / kCK;
   const int q = lane >> 4, jl = lane & 15;
   const int chan0 = a.chan_idx[zd.idx_off];
 
   auto stage = [&](int ch, int s) {
-    float* in_tile = smem + 4 + s * buf_len;
-    float* w_tile = in_tile + in_len;
+    float* in_tile = smem + L.in + s * L.buf_len;
+    float* w_tile = smem + L.w + s * L.buf_len;
     const int c_lo = ch * kCK;
     const int ckc = (cin - c_lo) < kCK ? (cin - c_lo) : kCK;
     const int cnt4 = (ckc * a.Tin) >> 2;
@@ -555,17 +597,17 @@ __global__ __launch_bounds__(256) void conv5_fwd_glds_kernel(ConvArgs a) {
   const int n_mine = n_items > wave_s ? (n_items - wave_s + 3) >> 2 : 0;
   const uint64_t tail_lanes = __builtin_amdgcn_ballot_w64(lane < (cnt4_full & 63));
   const char* const it_src = (const char*)a.in + ((item0 + wave_s) * a.Ctot + chan0) * (int64_t)a.Tx * 4;
-  const unsigned it_lds = smem_base + (unsigned)(4 + wave_s * kCK * a.RS) * 4;
+  const unsigned it_lds = smem_base + (unsigned)(L.in + wave_s * kCK * a.RS) * 4;
   const int64_t it_step = (int64_t)4 * a.Ctot * a.Tx * 4;
   const unsigned it_lds_step = (unsigned)(4 * kCK * a.RS) * 4;
   static_assert(GT != 2 || w_len == 4 * 5 * 256, "a full 32-filter weight chunk is 20 pieces of 1 KiB");
   const char* const w_src = (const char*)wbase + wave_s * (w_len / 4) * 4;
-  const unsigned w_lds = smem_base + (unsigned)(4 + in_len + wave_s * (w_len / 4)) * 4;
+  const unsigned w_lds = smem_base + (unsigned)(L.w + wave_s * (w_len / 4)) * 4;
   unsigned in_voff = lane * 16, w_voff = lane * 16;           // chunk 0 (they stay below one item's / one zone's bytes)
   auto stage_fast = [&](int s) {                              // the chunk after the one staged last
     in_voff += kCK * a.Tx * 4;
     w_voff += w_len * 4;
-    const unsigned boff = (unsigned)(s * buf_len) * 4;
+    const unsigned boff = (unsigned)(s * L.buf_len) * 4;
     auto items = [&](auto nf) {                               // one statement an item
       const char* src = it_src;
       unsigned lds = it_lds + boff;
@@ -680,10 +722,10 @@ __global__ __launch_bounds__(256) void conv5_fwd_glds_kernel(ConvArgs a) {
     for (; ch < cin / kCK; ++ch) {                          // the full chunks
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (stage_fast's DMA is not the compiler's to wait for)
       __syncthreads();                                      // drains this wave's DMA of chunk ch; all waves left chunk ch-1
-      unsigned a_addr = smem_base + (unsigned)(4 + (ch & 1) * buf_len + in_len + lane) * 4;
+      unsigned a_addr = smem_base + (unsigned)(L.w + (ch & 1) * L.buf_len + lane) * 4;
       unsigned b_addr[NT];
 #pragma unroll
-      for (int jj = 0; jj < NT; ++jj) b_addr[jj] = smem_base + (unsigned)(4 + (ch & 1) * buf_len + boff[jj]) * 4;
+      for (int jj = 0; jj < NT; ++jj) b_addr[jj] = smem_base + (unsigned)(L.in + (ch & 1) * L.buf_len + boff[jj]) * 4;
       FragSet f0, f1;
       issue(f0, a_addr, b_addr);                            // the one read per chunk that no MFMA covers: the DMA issue does
 #pragma unroll
@@ -711,8 +753,8 @@ __global__ __launch_bounds__(256) void conv5_fwd_glds_kernel(ConvArgs a) {
     const int ncg = ((cin - c_lo) < kCK ? (cin - c_lo) : kCK) / 4;
     // a ragged last chunk, and 16 filters: fragments of group cg + 1 are loaded in plain C++ around the MFMAs of group cg
     if (ch + 1 < n_chunks) stage(ch + 1, (ch + 1) & 1);
-    const float* in_tile = smem + 4 + (ch & 1) * buf_len;
-    const float* w_tile = in_tile + in_len + lane;
+    const float* in_tile = smem + L.in + (ch & 1) * L.buf_len;
+    const float* w_tile = smem + L.w + (ch & 1) * L.buf_len + lane;
     auto load = [&](int cg, Frag& f) {
       const float* rowp = in_tile + cg * 4 * a.RS;
 #pragma unroll
@@ -762,11 +804,8 @@ __global__ __launch_bounds__(256) void conv5_fwd_glds_kernel(ConvArgs a) {
   }
 }
 
-// dynamic LDS of conv5_fwd_glds_kernel (in_len / w_len / buf_len at its top): 4 floats of slack, then two buffers of
-// in_tile [ipw][kCK][W], w_tile [kCK/4][5][GT][64] and 32 floats of slack
 static size_t conv5_fwd_glds_lds(int ipw, int W, int GT) {
-  const size_t buf = (size_t)(((ipw * kCK * W + 3) & ~3) + (kCK / 4) * kTaps * GT * 64 + 32);
-  return sizeof(float) * (4 + 2 * buf);
+  return sizeof(float) * (size_t)conv5_fwd_layout(2, ipw, kCK, W, conv5_fwd_w_len(kCK, GT)).end;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -798,17 +837,16 @@ __global__ __launch_bounds__(256) void conv5_fwd_bf16_kernel(ConvArgs a, const u
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t item0 = (int64_t)blockIdx.x * a.IPW;
   const int n_items = (int)((a.items - item0) < a.IPW ? (a.items - item0) : a.IPW);
-  const int in_len = (a.IPW * kCK * a.RS + 3) & ~3;
-  constexpr int w_len = (kCK / 4) * GT * 64 * 4;            // floats: 16 bytes per lane and fragment
-  const int buf_len = in_len + w_len + 32;                  // 32 floats of slack: dead lanes read past the last row
+  static_assert(GT == 2, "kConv5FwdBf16WLen");
+  const Conv5FwdLds L = conv5_fwd_layout(2, a.IPW, kCK, a.RS, kConv5FwdBf16WLen);
   const uint4* wbase = wfrag16 + zd.eff_off / kTaps;
   const int n_chunks = (cin + kCK - 1) / kCK;
   const int q = lane >> 4, jl = lane & 15;
   const int chan0 = a.chan_idx[zd.idx_off];
 
   auto stage = [&](int ch, int s) {
-    float* in_tile = smem + 4 + s * buf_len;
-    float* w_tile = in_tile + in_len;
+    float* in_tile = smem + L.in + s * L.buf_len;
+    float* w_tile = smem + L.w + s * L.buf_len;
     const int c_lo = ch * kCK;
     const int ckc = (cin - c_lo) < kCK ? (cin - c_lo) : kCK;
     const int cnt4 = IN16 ? (ckc * a.Tin) >> 3 : (ckc * a.Tin) >> 2;
@@ -846,8 +884,8 @@ __global__ __launch_bounds__(256) void conv5_fwd_bf16_kernel(ConvArgs a, const u
   for (int ch = 0; ch < n_chunks; ++ch) {
     __syncthreads();                                        // drains this wave's DMA of chunk ch; all waves left chunk ch-1
     if (ch + 1 < n_chunks) stage(ch + 1, (ch + 1) & 1);
-    const float* in_tile = smem + 4 + (ch & 1) * buf_len;
-    const uint4* w_tile = reinterpret_cast<const uint4*>(in_tile + in_len) + lane;
+    const float* in_tile = smem + L.in + (ch & 1) * L.buf_len;
+    const uint4* w_tile = reinterpret_cast<const uint4*>(smem + L.w + (ch & 1) * L.buf_len) + lane;
     const int c_lo = ch * kCK;
     const int ncg = ((cin - c_lo) < kCK ? (cin - c_lo) : kCK) / 4;
     // the LDS reads of channel group cg + 1 are issued before group cg is packed and multiplied (the chain LDS read ->
@@ -937,11 +975,8 @@ __global__ __launch_bounds__(256) void conv5_fwd_bf16_kernel(ConvArgs a, const u
   }
 }
 
-// dynamic LDS of conv5_fwd_bf16_kernel<2, ...> (in_len / w_len / buf_len at its top): as the LDS-DMA kernel above with
-// w_tile [kCK/4][GT = 2][64] fragments of 16 bytes
 static size_t conv5_fwd_bf16_lds(int ipw, int W) {
-  const size_t buf = (size_t)(((ipw * kCK * W + 3) & ~3) + (kCK / 4) * 2 * 64 * 4 + 32);
-  return sizeof(float) * (4 + 2 * buf);
+  return sizeof(float) * (size_t)conv5_fwd_layout(2, ipw, kCK, W, kConv5FwdBf16WLen).end;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1037,36 +1072,31 @@ __device__ __forceinline__ void fused_layer_store(const f32x4 (&acc)[16 / NW][2]
   }
 }
 
-// Where the LDS regions of conv4_fused_fwd_kernel<NW> start, in floats from the start of its dynamic allocation, and
-// where the last one ends.  The kernel takes its pointers from here and conv4_fused_fwd_lds its size, so the two cannot
-// disagree; conv4_fused_fwd_layout_ok states the rule (regions in this order, none reaching into the next, t2 / t3 on
-// 16 bytes for their float4 copies, the end inside the allocation) and choose_route checks it for the shape of every call.
+// LDS of conv4_fused_fwd_kernel<NW>, in floats.  choose_route checks conv4_fused_fwd_layout_ok (t2 / t3 on 16 bytes for
+// their float4 copies, the end inside the allocation) for the shape of every call.
+constexpr int kFusedFrag = kTaps * 2 * 64;           // one fp32 fragment block: [5][2][64]
 struct FusedFwdLds {
   int xz, t2, t3, red, we, w3s, w4s, bls, end;
 };
 __host__ __device__ constexpr FusedFwdLds conv4_fused_fwd_layout(int NW, int F, int W, int T1) {
+  LdsCarver c;
   FusedFwdLds l = {};
-  const int tile = (F * T1 + 3) & ~3, frag = kTaps * 2 * 64;
-  l.xz = 4;                                          // 4 floats of slack in front: the pad-0 / pad-2 masked reads
-  l.t2 = l.xz + ((16 * W + 3) & ~3);
-  l.t3 = l.t2 + tile;
-  l.red = l.t3 + tile;
-  l.we = l.red + NW * F;
-  l.w3s = l.we + 4 * frag;
-  l.w4s = l.w3s + 8 * frag;
-  l.bls = l.w4s + 8 * frag;
-  l.end = l.bls + 64;
+  c.take(4);                                         // slack: the pad-0 / pad-2 masked reads reach in front of row 0
+  l.xz = c.take(16 * W);                             // [16][W]
+  l.t2 = c.take(F * T1, 4);                          // [F][T1]
+  l.t3 = c.take(F * T1, 4);                          // [F][T1]
+  l.red = c.take(NW * F, 4);                         // [NW][F]
+  l.we = c.take(4 * kFusedFrag);                     // [4][5][2][64]   frag-ordered Weff of the zone
+  l.w3s = c.take(8 * kFusedFrag);                    // [8][5][2][64]
+  l.w4s = c.take(8 * kFusedFrag);
+  l.bls = c.take(F);                                 // [F] beff
+  c.take(64 - F);                                    // slack behind the fragments
+  l.end = c.end;
   return l;
 }
 __host__ __device__ constexpr bool conv4_fused_fwd_layout_ok(int NW, int F, int W, int T1, size_t lds_bytes) {
   const FusedFwdLds l = conv4_fused_fwd_layout(NW, F, W, T1);
-  const int frag = kTaps * 2 * 64;
-  const int start[9] = {l.xz, l.t2, l.t3, l.red, l.we, l.w3s, l.w4s, l.bls, l.end};
-  const int len[8] = {16 * W, F * T1, F * T1, NW * F, 4 * frag, 8 * frag, 8 * frag, F};
-  if (l.xz < 4 || l.t2 % 4 != 0 || l.t3 % 4 != 0) return false;
-  for (int i = 0; i < 8; ++i)
-    if (len[i] < 0 || start[i] + len[i] > start[i + 1]) return false;
-  return sizeof(float) * (size_t)l.end <= lds_bytes;
+  return l.xz >= 4 && l.t2 % 4 == 0 && l.t3 % 4 == 0 && sizeof(float) * (size_t)l.end <= lds_bytes;
 }
 
 template <int NW>
@@ -1078,15 +1108,9 @@ __global__ __launch_bounds__(NW * 64) void conv4_fused_fwd_kernel(FusedFwdArgs a
   const int cz = zd.cin, ncg = (cz + 3) / 4;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane >> 4, jl = lane & 15;
   const int T1 = a.T1, W = a.W, TT = a.TT;
-  const FusedFwdLds L = conv4_fused_fwd_layout(NW, F, W, T1);   // the same offsets size the allocation (choose_route checks them)
-  float* xz = smem + L.xz;                           // [16][W]  (4 floats of slack in front: masked reads touch them)
-  float* t2 = smem + L.t2;                           // [32][T1]
-  float* t3 = smem + L.t3;                           // [32][T1]
-  float* red = smem + L.red;                         // [8][32]
-  float* we = smem + L.we;                           // [4][5][2][64]   frag-ordered Weff of the zone
-  float* w3s = smem + L.w3s;                         // [8][5][2][64]
-  float* w4s = smem + L.w4s;
-  float* bls = smem + L.bls;                         // [32] beff (in the 64 floats of slack behind the fragments)
+  const FusedFwdLds L = conv4_fused_fwd_layout(NW, F, W, T1);
+  float *xz = smem + L.xz, *t2 = smem + L.t2, *t3 = smem + L.t3, *red = smem + L.red;
+  float *we = smem + L.we, *w3s = smem + L.w3s, *w4s = smem + L.w4s, *bls = smem + L.bls;
   // ---- weight fragments into LDS once per (persistent) workgroup
   for (int e = threadIdx.x; e < 4 * kTaps * 2 * 64; e += NW * 64) we[e] = (e < ncg * kTaps * 2 * 64) ? a.weff[zd.eff_off + e] : 0.f;
   for (int e = threadIdx.x; e < 8 * kTaps * 2 * 64; e += NW * 64) {
@@ -1246,8 +1270,6 @@ __global__ __launch_bounds__(NW * 64) void conv4_fused_fwd_kernel(FusedFwdArgs a
   }
 }
 
-// dynamic LDS of conv4_fused_fwd_kernel<NW> (conv4_fused_fwd_layout): 4 floats of slack, xz [16][W], t2 and t3 [F][T1],
-// red [NW][F], the Weff / cnn3 / cnn4 fragment sets of 4 + 8 + 8 blocks, 64 floats of slack holding beff
 static size_t conv4_fused_fwd_lds(int NW, int F, int W, int T1) {
   return sizeof(float) * (size_t)conv4_fused_fwd_layout(NW, F, W, T1).end;
 }
@@ -1343,6 +1365,31 @@ __device__ __forceinline__ void fused_wgrad_mma(const float* __restrict__ G, con
   }
 }
 
+// LDS of conv4_fused_bwd_kernel<8>, in floats.  The pad-2 reads of a tile reach two floats in front of its first row:
+// four floats of slack stand in front of xz and of each tile, and behind the last one.
+struct FusedBwdLds {
+  int xz, ga, gb, at, w4s, w3s, dfs, end;
+};
+__host__ __device__ constexpr FusedBwdLds conv4_fused_bwd_layout(int F, int W, int T1) {
+  LdsCarver c;
+  FusedBwdLds l = {};
+  c.take(4);
+  l.xz = c.take(16 * W);                             // [16][W]
+  c.take(4, 4);
+  l.ga = c.take(F * T1);                             // [F][T1]  GELU'(A4) -> G4 -> G2
+  c.take(4, 4);
+  l.gb = c.take(F * T1);                             // [F][T1]  G3
+  c.take(4, 4);
+  l.at = c.take(F * T1);                             // [F][T1]  staged activation (A3, then A2)
+  c.take(4, 4);
+  l.w4s = c.take(8 * kFusedFrag);                    // [8][5][2][64] transposed + flipped cnn4 fragments
+  l.w3s = c.take(8 * kFusedFrag);
+  l.dfs = c.take(F);                                 // [F] dfeat of the item / T1
+  c.take(16);                                        // slack
+  l.end = c.end;
+  return l;
+}
+
 template <int NW>
 __global__ __launch_bounds__(NW * 64) void conv4_fused_bwd_kernel(FusedBwdArgs a) {
   static_assert(NW == 8, "wave roles below assume 8 waves");
@@ -1353,14 +1400,9 @@ __global__ __launch_bounds__(NW * 64) void conv4_fused_bwd_kernel(FusedBwdArgs a
   const int cz = zd.cin, cin1 = cz + 1;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane >> 4, jl = lane & 15;
   const int T1 = a.T1, W = a.W, TT = a.TT;
-  const int tile = (F * T1 + 3) & ~3;
-  float* xz = smem + 4;                              // [16][W]
-  float* ga = smem + ((4 + 16 * W + 3) & ~3) + 4;    // [32][T1]  (4 floats of slack before each tile: pad-2 reads)
-  float* gb = ga + tile + 4;                         // [32][T1]
-  float* at = gb + tile + 4;                         // [32][T1]  staged activation (A3, then A2)
-  float* w4s = at + tile + 4;                        // [8][5][2][64] transposed + flipped cnn4 fragments
-  float* w3s = w4s + 8 * kTaps * 2 * 64;
-  float* dfs = w3s + 8 * kTaps * 2 * 64;             // [32] dfeat of the item / T1
+  const FusedBwdLds L = conv4_fused_bwd_layout(F, W, T1);
+  float *xz = smem + L.xz, *ga = smem + L.ga, *gb = smem + L.gb, *at = smem + L.at;
+  float *w4s = smem + L.w4s, *w3s = smem + L.w3s, *dfs = smem + L.dfs;
   for (int e = threadIdx.x; e < 8 * kTaps * 2 * 64; e += NW * 64) {
     w4s[e] = a.w4t[(int64_t)z * a.wz_stride + e];
     w3s[e] = a.w3t[(int64_t)z * a.wz_stride + e];
@@ -1473,11 +1515,8 @@ __global__ __launch_bounds__(NW * 64) void conv4_fused_bwd_kernel(FusedBwdArgs a
   }
 }
 
-// dynamic LDS of conv4_fused_bwd_kernel<8> (xz .. dfs at its top): xz [16][W], three tiles [F][T1] with 4 floats of
-// slack before each, the two transposed fragment sets, dfs [32] and 16 floats of slack
 static size_t conv4_fused_bwd_lds(int F, int W, int T1) {
-  const int tile = ((F * T1 + 3) & ~3) + 4;
-  return sizeof(float) * (size_t)(((4 + 16 * W + 3) & ~3) + 4 + 3 * tile + 2 * 8 * kTaps * 2 * 64 + 32 + 16);
+  return sizeof(float) * (size_t)conv4_fused_bwd_layout(F, W, T1).end;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1506,7 +1545,51 @@ __device__ long long cf_times[32];
 #else
 #define CF_MARK(k) do { } while (0)
 #endif
-__host__ __device__ __forceinline__ int fused16_rows(int TT) { return 32 * ((TT + 1) / 2) + 8; }   // tile rows incl. guards
+__host__ __device__ constexpr int fused16_rows(int TT) { return 32 * ((TT + 1) / 2) + 8; }   // tile rows incl. guards
+constexpr int kFused16Frag = kTaps * 2 * 64 * 16;   // bytes of one K = 32 bf16 fragment set: [5][2][64] of 16 bytes
+
+// LDS of conv4_fused_fwd_bf16_kernel<NW>, in bytes.  xt, the bf16 x tile [TT * 16 + 8][16 channels], lies over the front
+// of t3 (idle between cnn4's reads and cnn3's stores): xt_len against `tile` is part of the static_assert below.
+struct Fused16FwdLds {
+  int t2, t3, xt, xt_len, tile, red, bls, w1s, w3s, w4s, end;
+};
+__host__ __device__ constexpr Fused16FwdLds conv4_fused_fwd_bf16_layout(int NW, int F, int TT) {
+  LdsCarver c;
+  Fused16FwdLds l = {};
+  l.tile = fused16_rows(TT) * 64;                    // rows of 64 bytes
+  l.t2 = c.take(l.tile, 16);
+  l.t3 = c.take(l.tile, 16);
+  l.xt = l.t3;
+  l.xt_len = (TT * 16 + 8) * 32;                     // rows of 32 bytes
+  l.red = c.take(NW * F * 4);                        // [NW][F] floats
+  l.bls = c.take(F * 4);                             // [F] beff
+  l.w1s = c.take(3 * 2 * 64 * 16, 16);               // [3][2][64] bf16 K = 32 fragments of Weff
+  l.w3s = c.take(kFused16Frag, 16);                  // [5][2][64]
+  l.w4s = c.take(kFused16Frag, 16);
+  c.take(64);                                        // slack
+  l.end = c.end;
+  return l;
+}
+// LDS of conv4_fused_bwd_bf16_kernel<8>, in bytes: set 0 {tA, tB, tC}, set 1 {tA, tB, tC}, gb, xt, w4s, w3s.
+// tA: GELU'(A4) -> G4 -> G2;  tB: A3;  tC: A2.  Set s has its tA at sets + s * set_len, tB and tC one and two `tile` on.
+struct Fused16BwdLds {
+  int sets, set_len, tile, gb, xt, w4s, w3s, end;
+};
+__host__ __device__ constexpr Fused16BwdLds conv4_fused_bwd_bf16_layout(int TT) {
+  LdsCarver c;
+  Fused16BwdLds l = {};
+  l.tile = fused16_rows(TT) * 64;
+  l.set_len = 3 * l.tile;
+  l.sets = c.take(2 * l.set_len, 16);
+  l.gb = c.take(l.tile, 16);                         // G3
+  l.xt = c.take((32 * ((TT + 1) / 2) + 16) * 32);    // bf16 x tile, rows of 32 bytes (rows past W: zeros): the last
+                                                     // 32-step block's 12-step window stays inside
+  l.w4s = c.take(kFused16Frag, 16);                  // transposed + flipped cnn4 / cnn3 fragments
+  l.w3s = c.take(kFused16Frag, 16);
+  c.take(64);                                        // slack
+  l.end = c.end;
+  return l;
+}
 
 // acc[j][gt] = sum_k W_k[gt] x in(rows tt[j]*16 + . + k): `wfr` = LDS fragments [5][2][64] uint4, `in` = tile bytes
 template <int NJ>
@@ -1592,17 +1675,16 @@ __global__ __launch_bounds__(NW * 64, 4) void conv4_fused_fwd_bf16_kernel(FusedF
   const int cz = zd.cin, ncg = (cz + 3) / 4;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane >> 4, jl = lane & 15;
   const int T1 = a.T1, W = a.W, TT = a.TT;
-  const int R = fused16_rows(TT), tile_f = R * 16;            // tile = R rows x 64 bytes
-  char* t2 = reinterpret_cast<char*>(smem);
-  char* t3 = t2 + tile_f * 4;
-  char* xt = t3;                                              // [TT * 16 + 8][16] bf16
-  float* red = reinterpret_cast<float*>(t3 + tile_f * 4);     // [NW][32]
-  float* bls = red + NW * F;                                  // [32] beff: read per item from LDS -- as registers
-                                                              // loaded before the loop the compiler waited for ALL
-                                                              // vector memory (the x fetch included) at their use
-  uint4* w1s = reinterpret_cast<uint4*>(bls + F);             // [3][2][64] bf16 K = 32 fragments of Weff
-  uint4* w3s = w1s + 3 * 2 * 64;                              // [5][2][64]
-  uint4* w4s = w3s + kTaps * 2 * 64;
+  const Fused16FwdLds L = conv4_fused_fwd_bf16_layout(NW, F, TT);
+  char* const lds = reinterpret_cast<char*>(smem);
+  char *t2 = lds + L.t2, *t3 = lds + L.t3, *xt = lds + L.xt;
+  float* red = reinterpret_cast<float*>(lds + L.red);
+  float* bls = reinterpret_cast<float*>(lds + L.bls);         // beff: read per item from LDS -- as registers loaded
+                                                              // before the loop the compiler waited for ALL vector
+                                                              // memory (the x fetch included) at their use
+  uint4* w1s = reinterpret_cast<uint4*>(lds + L.w1s);
+  uint4* w3s = reinterpret_cast<uint4*>(lds + L.w3s);
+  uint4* w4s = reinterpret_cast<uint4*>(lds + L.w4s);
   for (int e = threadIdx.x; e < 3 * 2 * 64; e += NW * 64) {
     const int l = e & 63, gt = (e >> 6) & 1, p = e >> 7, tap = 2 * p + (l >> 5);
     float v[8];
@@ -1618,7 +1700,7 @@ __global__ __launch_bounds__(NW * 64, 4) void conv4_fused_fwd_bf16_kernel(FusedF
     w3s[e] = reinterpret_cast<const uint4*>(a.w3 + (int64_t)z * a.wz_stride)[e];
     w4s[e] = reinterpret_cast<const uint4*>(a.w4 + (int64_t)z * a.wz_stride)[e];
   }
-  for (int e = threadIdx.x; e < 2 * tile_f; e += NW * 64) reinterpret_cast<float*>(t2)[e] = 0.f;   // guards, rows >= T1
+  for (int e = threadIdx.x; e < 2 * L.tile / 4; e += NW * 64) reinterpret_cast<float*>(t2)[e] = 0.f;   // guards, rows >= T1
   if (threadIdx.x < F) bls[threadIdx.x] = a.beff[z * F + threadIdx.x];
   constexpr int NJ = 16 / NW;
   int ttj[NJ];
@@ -1784,12 +1866,7 @@ __global__ __launch_bounds__(NW * 64, 4) void conv4_fused_fwd_bf16_kernel(FusedF
   }
 }
 
-// dynamic LDS of conv4_fused_fwd_bf16_kernel<8> (t2 .. w4s at its top): t2, t3 (its front doubles as the bf16 x tile),
-// row sums [8][32], bias, three Weff fragment sets and the cnn3 / cnn4 sets of 16 bytes per lane
-static size_t conv4_fused_fwd_bf16_lds(int TT) {
-  const size_t tile_f = (size_t)fused16_rows(TT) * 16, w16 = (size_t)kTaps * 2 * 64 * 4;
-  return sizeof(float) * (2 * tile_f + 8 * 32 + 32 + 3 * 2 * 64 * 4 + 2 * w16 + 16);
-}
+static size_t conv4_fused_fwd_bf16_lds(int TT) { return (size_t)conv4_fused_fwd_bf16_layout(8, 32, TT).end; }
 
 // transposed 4-row x 16-column block read of a [row][32] bf16 tile: the lane of column c receives rows r0 .. r0 + 3 of
 // that column, packed (lane 4 r + p of the 16-lane group supplies the address of row r, columns 4 p .. 4 p + 3)
@@ -1890,19 +1967,17 @@ __global__ __launch_bounds__(NW * 64) void conv4_fused_bwd_bf16_kernel(FusedBwdA
   const int cz = zd.cin, cin1 = cz + 1;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane >> 4, jl = lane & 15;
   const int T1 = a.T1, W = a.W, TT = a.TT;
-  const int R = fused16_rows(TT), tile_f = R * 16, tile_b = tile_f * 4;
-  // LDS: set 0 {tA, tB, tC}, set 1 {tA, tB, tC}, gb, xt, w4s, w3s.   tA: GELU'(A4) -> G4 -> G2;  tB: A3;  tC: A2
-  char* sets = reinterpret_cast<char*>(smem);
-  char* gb = sets + 6 * tile_b;
-  const int xt_rows = 32 * ((TT + 1) / 2) + 16;               // the last 32-step block's 12-step window stays inside
-  char* xt = gb + tile_b;                                     // [xt_rows][16] bf16 (rows past W: zeros)
-  uint4* w4s = reinterpret_cast<uint4*>(xt + xt_rows * 32);   // transposed + flipped cnn4 / cnn3 fragments
-  uint4* w3s = w4s + kTaps * 2 * 64;
+  const Fused16BwdLds L = conv4_fused_bwd_bf16_layout(TT);
+  const int tile_b = L.tile;
+  char* const lds = reinterpret_cast<char*>(smem);
+  char *sets = lds + L.sets, *gb = lds + L.gb, *xt = lds + L.xt;
+  uint4* w4s = reinterpret_cast<uint4*>(lds + L.w4s);
+  uint4* w3s = reinterpret_cast<uint4*>(lds + L.w3s);
   for (int e = threadIdx.x; e < kTaps * 2 * 64; e += NW * 64) {
     w4s[e] = reinterpret_cast<const uint4*>(a.w4t + (int64_t)z * a.wz_stride)[e];
     w3s[e] = reinterpret_cast<const uint4*>(a.w3t + (int64_t)z * a.wz_stride)[e];
   }
-  for (int e = threadIdx.x; e < 7 * tile_f + xt_rows * 8; e += NW * 64) smem[e] = 0.f;   // guards, rows >= T1
+  for (int e = threadIdx.x; e < L.w4s / 4; e += NW * 64) smem[e] = 0.f;   // everything in front of the fragments: guards, rows >= T1
   constexpr int NJ = 16 / NW;
   int ttj[NJ];
 #pragma unroll
@@ -1910,8 +1985,7 @@ __global__ __launch_bounds__(NW * 64) void conv4_fused_bwd_bf16_kernel(FusedBwdA
   const int ct = wave & 1, ks = wave >> 1;
   const int nkb = (T1 + 31) >> 5;                             // 32-step blocks of the weight gradients
   const unsigned smem_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) float*)smem;
-  const unsigned gb_base = smem_base + 6 * tile_b;
-  const unsigned xt_base = gb_base + tile_b;
+  const unsigned gb_base = smem_base + L.gb, xt_base = smem_base + L.xt;
   f32x4 acc4[2][kTaps], acc3[2][kTaps], acc0[2][kTaps], accb[2];
 #pragma unroll
   for (int g = 0; g < 2; ++g) {
@@ -1943,7 +2017,7 @@ __global__ __launch_bounds__(NW * 64) void conv4_fused_bwd_bf16_kernel(FusedBwdA
   }
   auto prefetch = [&](int item, int set) {
     const int64_t abase = ((int64_t)item * a.Z + z) * (int64_t)T1 * 64;
-    const unsigned tA = smem_base + (unsigned)(set * 3 * tile_b) + 128;          // past the two guard rows
+    const unsigned tA = smem_base + (unsigned)(L.sets + set * L.set_len) + 128;  // past the two guard rows
 #pragma unroll 1
     for (int e0 = wave * 64; e0 < n16; e0 += NW * 64)
       if (e0 + lane < n16) {
@@ -1974,9 +2048,9 @@ __global__ __launch_bounds__(NW * 64) void conv4_fused_bwd_bf16_kernel(FusedBwdA
 
   int set = 0;
   for (int item = blockIdx.x; item < nitems; item += gridDim.x, set ^= 1) {
-    char* tA = sets + set * 3 * tile_b;
+    char* tA = sets + set * L.set_len;
     char* tB = tA + tile_b;
-    const unsigned tA_base = smem_base + (unsigned)(set * 3 * tile_b), tC_base = tA_base + 2 * tile_b;
+    const unsigned tA_base = smem_base + (unsigned)(L.sets + set * L.set_len), tC_base = tA_base + 2 * tile_b;
     CF_MARK(17);
     __builtin_amdgcn_s_waitcnt(0x0F70);                // vmcnt(0): this wave's share of the item's fetch has landed
     __syncthreads();                                   // ... everyone's; the previous item's tiles are no longer read
@@ -2061,12 +2135,7 @@ __global__ __launch_bounds__(NW * 64) void conv4_fused_bwd_bf16_kernel(FusedBwdA
   }
 }
 
-// dynamic LDS of conv4_fused_bwd_bf16_kernel<8> (sets .. w3s at its top): two sets of {GELU'(A4) / G4 / G2, A3, A2},
-// G3, the bf16 x tile of xt_rows rows and the two transposed fragment sets
-static size_t conv4_fused_bwd_bf16_lds(int TT) {
-  const size_t tile_f = (size_t)fused16_rows(TT) * 16, w16 = (size_t)kTaps * 2 * 64 * 4;
-  return sizeof(float) * (7 * tile_f + (size_t)(32 * ((TT + 1) / 2) + 16) * 8 + 2 * w16 + 16);
-}
+static size_t conv4_fused_bwd_bf16_lds(int TT) { return (size_t)conv4_fused_bwd_bf16_layout(TT).end; }
 
 // ---------------------------------------------------------------------------------------
 // Tail of the feature classifier (spec-S features: a handful of time steps, one zone) in ONE launch:
@@ -2294,6 +2363,50 @@ __device__ __forceinline__ void tail_combine_store_split(float* __restrict__ sme
   }
 }
 
+// LDS of featcnn_tail_kernel<NW>, in floats: the four fragment sets and the FC weights are shared by the workgroup, wave
+// w has its scratch at scr + w * kTailScr and its four tiles (A2, A3, G4, G3) at tiles + w * kTailSlot.  The epilogue
+// (tail_combine_store_split) lays two accumulator copies over the whole allocation, from its start.
+constexpr int kTailScr = 80;                               // per wave: [32] pooled features, [16] logits, [16] dlogits, the loss term
+constexpr int kTailSlot = 4 * kTailTile;
+struct TailLds {
+  int w3s, w4s, w3ts, w4ts, fcs, scr, tiles, end;
+};
+__host__ __device__ constexpr TailLds featcnn_tail_layout(int NW, int F) {
+  LdsCarver c;
+  TailLds l = {};
+  l.w3s = c.take(8 * kFusedFrag, 4);                       // 5120 floats per fragment set
+  l.w4s = c.take(8 * kFusedFrag, 4);
+  l.w3ts = c.take(8 * kFusedFrag, 4);
+  l.w4ts = c.take(8 * kFusedFrag, 4);
+  l.fcs = c.take(kTailMaxCls * (F + 1));                   // [n_cls][F] then [n_cls]
+  l.scr = c.take(NW * kTailScr);
+  c.take(4);                                               // four zero floats in front of the first tile
+  l.tiles = c.take(NW * kTailSlot, 4);
+  l.end = c.end > 2 * kTailCombCopy ? c.end : 2 * kTailCombCopy;
+  return l;
+}
+// LDS of featcnn_tail_bf16_kernel<NW>, in bytes: wave w has, at priv + w * kTail16Priv, its tiles A2, A3, G4 / G2 and G3
+// of kTail16Tile each and 256 bytes of scratch ([32] pooled features, [16] logits, [16] dlogits).  The epilogue
+// (tail_combine_store<NW, 3>) lays three accumulator copies over the whole allocation.
+constexpr int kTail16Tile = fused16_rows(1) * 64;          // 40 rows of 64 bytes
+constexpr int kTail16Priv = 4 * kTail16Tile + 256;
+struct Tail16Lds {
+  int w3s, w4s, w3ts, w4ts, fcs, priv, end;
+};
+__host__ __device__ constexpr Tail16Lds featcnn_tail_bf16_layout(int NW, int F) {
+  LdsCarver c;
+  Tail16Lds l = {};
+  l.w3s = c.take(kFused16Frag, 16);                        // K = 32 fragment sets of 10 KiB
+  l.w4s = c.take(kFused16Frag, 16);
+  l.w3ts = c.take(kFused16Frag, 16);
+  l.w4ts = c.take(kFused16Frag, 16);
+  l.fcs = c.take(kTailMaxCls * (F + 1) * 4);               // floats: [n_cls][F] then [n_cls]
+  l.priv = c.take(NW * kTail16Priv, 16);
+  c.take(64);                                              // slack
+  l.end = c.end > 3 * kTailCombCopy * 4 ? c.end : 3 * kTailCombCopy * 4;
+  return l;
+}
+
 // Eight waves, two per SIMD (a lone wave issues a vector instruction every four cycles and cannot put its LDS and index
 // work under its own MFMAs).  Every wave runs the chain of one item per round; for the weight gradients the partners
 // 2p / 2p + 1 read each other's tiles: wave 2p + h accumulates filter tile h of dW3 and dW4 (20 accumulators instead
@@ -2306,20 +2419,16 @@ __device__ __forceinline__ void tail_combine_store_split(float* __restrict__ sme
 template <int NW>
 __global__ __launch_bounds__(NW * 64) void featcnn_tail_kernel(TailArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  constexpr int F = 32, WF = 8 * kTaps * 2 * 64;              // 5120 floats per fragment set
+  constexpr int F = 32, WF = 8 * kFusedFrag;                  // 5120 floats per fragment set
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), q = lane >> 4, jl = lane & 15;
   const int T1 = a.T1, n_cls = a.n_cls, half = wave & 1, pair = wave >> 1;
   const int tile = F * T1;
-  constexpr int SCR = 80;                                     // floats of per-wave scratch
-  float* w3s = smem;                                          // fragment sets, shared by the workgroup
-  float* w4s = w3s + WF;
-  float* w3ts = w4s + WF;
-  float* w4ts = w3ts + WF;
-  float* fcs = w4ts + WF;                                     // [n_cls][F] then [n_cls]
-  float* featL = fcs + kTailMaxCls * (F + 1) + wave * SCR;    // per wave: [32] pooled features, [16] logits, [16] dlogits,
+  constexpr TailLds L = featcnn_tail_layout(NW, F);
+  float *w3s = smem + L.w3s, *w4s = smem + L.w4s, *w3ts = smem + L.w3ts, *w4ts = smem + L.w4ts, *fcs = smem + L.fcs;
+  float* featL = smem + L.scr + wave * kTailScr;              // [32] pooled features, [16] logits, [16] dlogits,
   float* logL = featL + 32;                                   // [1] the item's loss term (featL[64])
-  float* tiles = fcs + kTailMaxCls * (F + 1) + NW * SCR + 4;  // four zero floats in front; per wave A2, A3, G4, G3
-  constexpr int tA2 = 0, tA3 = kTailTile, tG4 = 2 * kTailTile, tG3 = 3 * kTailTile, slot = 4 * kTailTile;
+  float* tiles = smem + L.tiles;
+  constexpr int tA2 = 0, tA3 = kTailTile, tG4 = 2 * kTailTile, tG3 = 3 * kTailTile, slot = kTailSlot;
   float* pairT = tiles + (wave & ~1) * slot;                  // the partners' tiles: wave 2p + s at s * slot
   float* own = pairT + half * slot;
   for (int e = threadIdx.x; e < WF / 4; e += NW * 64) {      // float4: the sets are 16-byte aligned workspace blocks
@@ -2434,7 +2543,7 @@ __global__ __launch_bounds__(NW * 64) void featcnn_tail_kernel(TailArgs a) {
     auto add_loss = [&]() {
       if (half == 0 && lane == 0) {
         if (live) loss_acc += featL[64] * a.grad_scale;
-        if (live_odd) loss_acc += featL[SCR + 64] * a.grad_scale;
+        if (live_odd) loss_acc += featL[kTailScr + 64] * a.grad_scale;
       }
     };
     if (!a.train) {
@@ -2466,7 +2575,7 @@ __global__ __launch_bounds__(NW * 64) void featcnn_tail_kernel(TailArgs a) {
       // FC gradients of both items: flat element e = lane + 64 j of [n_cls][F]
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
-        const float* fL = featL + s * SCR;
+        const float* fL = featL + s * kTailScr;
 #pragma unroll
         for (int j = 0; j < kTailMaxCls * F / 64; ++j) {
           const int e = lane + 64 * j;
@@ -2496,12 +2605,7 @@ __global__ __launch_bounds__(NW * 64) void featcnn_tail_kernel(TailArgs a) {
                                accfc, accb, loss_acc, a.part + (int64_t)blockIdx.x * a.slab, a.slab, n_cls);
 }
 
-// dynamic LDS of featcnn_tail_kernel<NW> (w3s .. tiles at its top): four fragment sets, the FC weights and bias, 80
-// floats per wave, four zero floats and four tiles per wave; the epilogue's two accumulator copies fit inside
-static size_t featcnn_tail_lds(int NW, int F) {
-  const size_t lds = sizeof(float) * (size_t)(4 * 8 * kTaps * 2 * 64 + kTailMaxCls * (F + 1) + NW * 80 + 4 + NW * 4 * kTailTile);
-  return lds < sizeof(float) * 2 * kTailCombCopy ? sizeof(float) * 2 * kTailCombCopy : lds;
-}
+static size_t featcnn_tail_lds(int NW, int F) { return sizeof(float) * (size_t)featcnn_tail_layout(NW, F).end; }
 
 // BASELINE config 3, round 3: the same launch on the bf16 matrix cores (v_mfma_f32_16x16x32_bf16).  The fp32-MFMA
 // instance above (featcnn_tail_kernel<., true>: bf16 I/O and bf16-rounded intermediates, 480 v_mfma_f32_16x16x4_f32
@@ -2514,17 +2618,18 @@ static size_t featcnn_tail_lds(int NW, int F) {
 template <int NW>
 __global__ __launch_bounds__(NW * 64) void featcnn_tail_bf16_kernel(TailArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  constexpr int F = 32, FR = kTaps * 2 * 64;                   // uint4 per K = 32 fragment set (10 KiB)
-  constexpr int R = 40, tile_b = R * 64;                       // fused16_rows(1) rows of 64 bytes
-  constexpr int priv_b = 4 * tile_b + 256;
+  constexpr int F = 32, FR = kFused16Frag / 16;                // uint4 per K = 32 fragment set (10 KiB)
+  constexpr int tile_b = kTail16Tile, priv_b = kTail16Priv;
+  constexpr Tail16Lds L = featcnn_tail_bf16_layout(NW, F);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane >> 4, jl = lane & 15;
   const int T1 = a.T1, n_cls = a.n_cls;
-  uint4* w3s = reinterpret_cast<uint4*>(smem);
-  uint4* w4s = w3s + FR;
-  uint4* w3ts = w4s + FR;
-  uint4* w4ts = w3ts + FR;
-  float* fcs = reinterpret_cast<float*>(w4ts + FR);            // [n_cls][F] then [n_cls]
-  char* priv = reinterpret_cast<char*>(fcs + kTailMaxCls * (F + 1)) + wave * priv_b;
+  char* const lds = reinterpret_cast<char*>(smem);
+  uint4* w3s = reinterpret_cast<uint4*>(lds + L.w3s);
+  uint4* w4s = reinterpret_cast<uint4*>(lds + L.w4s);
+  uint4* w3ts = reinterpret_cast<uint4*>(lds + L.w3ts);
+  uint4* w4ts = reinterpret_cast<uint4*>(lds + L.w4ts);
+  float* fcs = reinterpret_cast<float*>(lds + L.fcs);
+  char* priv = lds + L.priv + wave * priv_b;
   char* tA2 = priv;
   char* tA3 = priv + tile_b;
   char* tG = priv + 2 * tile_b;                                // G4, later G2
@@ -2532,7 +2637,7 @@ __global__ __launch_bounds__(NW * 64) void featcnn_tail_bf16_kernel(TailArgs a) 
   float* featL = reinterpret_cast<float*>(priv + 4 * tile_b);  // [32] pooled features
   float* logL = featL + 32;                                    // [16] logits, [16] dlogits
   const unsigned smem_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) float*)smem;
-  const unsigned priv_base = smem_base + (unsigned)(4 * FR * 16 + kTailMaxCls * (F + 1) * 4 + wave * priv_b);
+  const unsigned priv_base = smem_base + (unsigned)(L.priv + wave * priv_b);
   for (int e = threadIdx.x; e < FR; e += NW * 64) {
     w3s[e] = reinterpret_cast<const uint4*>(a.w3)[e];
     w4s[e] = reinterpret_cast<const uint4*>(a.w4)[e];
@@ -2676,12 +2781,7 @@ __global__ __launch_bounds__(NW * 64) void featcnn_tail_bf16_kernel(TailArgs a) 
                             accfc, accb, loss_acc, a.part + (int64_t)blockIdx.x * a.slab, a.slab, n_cls);
 }
 
-// dynamic LDS of featcnn_tail_bf16_kernel<NW> (w3s .. logL at its top): four K = 32 fragment sets, the FC weights and
-// bias, per wave priv_b = four tiles of 40 rows x 64 bytes + 256; at least the epilogue's three accumulator copies
-static size_t featcnn_tail_bf16_lds(int NW, int F) {
-  const size_t lds = (size_t)4 * kTaps * 2 * 64 * 16 + sizeof(float) * kTailMaxCls * (F + 1) + (size_t)NW * (4 * 40 * 64 + 256) + 64;
-  return lds < sizeof(float) * 3 * kTailCombCopy ? sizeof(float) * 3 * kTailCombCopy : lds;
-}
+static size_t featcnn_tail_bf16_lds(int NW, int F) { return (size_t)featcnn_tail_bf16_layout(NW, F).end; }
 
 // ---------------------------------------------------------------------------------------
 // GELU + mean over time (fast.py:117-118) and its backward (in place on the activation).
@@ -2721,17 +2821,29 @@ __global__ __launch_bounds__(256) void gelu_mean_bwd_kernel(void* __restrict__ a
 // correlation of the first, fused layer; zones own disjoint channels, overlapping windows add).  One workgroup per
 // (window, zone) item with the G2 tile in LDS; not a hot path (saliency / SHAP-style attributions), plain VALU.
 // With at most two windows covering a sample (slide_step >= window_len / 2) the float atomics commute exactly.
+// LDS of conv5_dx_kernel, in floats: the G2 tile
+struct Conv5DxLds {
+  int g2, end;
+};
+__host__ __device__ constexpr Conv5DxLds conv5_dx_layout(int F, int T1) {
+  LdsCarver c;
+  Conv5DxLds l = {};
+  l.g2 = c.take(F * T1);                             // [F][T1]
+  l.end = c.end;
+  return l;
+}
 __global__ __launch_bounds__(256) void conv5_dx_kernel(const float* __restrict__ g2, const float* __restrict__ wfrag,
                                                        const ZoneDesc* __restrict__ zones,
                                                        const int* __restrict__ chan_idx, float* __restrict__ dx,
                                                        int Z, int F, int T1, int W, int Ctot, int Tx, int N, int S) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];          // [F][T1]
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  float* tile = smem + conv5_dx_layout(F, T1).g2;
   const int64_t item = blockIdx.x;
   const int z = blockIdx.y;
   const ZoneDesc zd = zones[z];
   const int GT = F / 16;
   const float* src = g2 + (item * Z + z) * (int64_t)(F * T1);
-  for (int e = threadIdx.x; e < F * T1; e += 256) smem[e] = src[e];
+  for (int e = threadIdx.x; e < F * T1; e += 256) tile[e] = src[e];
   __syncthreads();
   const int64_t b = item / N;
   const int n = (int)(item - b * N);
@@ -2741,7 +2853,7 @@ __global__ __launch_bounds__(256) void conv5_dx_kernel(const float* __restrict__
     const int cg = c >> 2, cl = (c & 3) * 16;
     float acc = 0.f;
     for (int g = 0; g < F; ++g) {
-      const float* gr = smem + g * T1;
+      const float* gr = tile + g * T1;
       const int gt = g >> 4, gl = g & 15;
 #pragma unroll
       for (int k = 0; k < kTaps; ++k) {
@@ -2753,8 +2865,7 @@ __global__ __launch_bounds__(256) void conv5_dx_kernel(const float* __restrict__
   }
 }
 
-// dynamic LDS of conv5_dx_kernel: the G2 tile [F][T1]
-static size_t conv5_dx_lds(int F, int T1) { return sizeof(float) * (size_t)F * T1; }
+static size_t conv5_dx_lds(int F, int T1) { return sizeof(float) * (size_t)conv5_dx_layout(F, T1).end; }
 
 // ---------------------------------------------------------------------------------------
 // Weight gradient: dW[g][c][k] = sum_{item,t} dOut[item][g][t] * In[item][c][t + k - pad].
@@ -2782,6 +2893,21 @@ struct WgradArgs {
 // shared by both); the 4/n_ct wave groups split the time range of each item and write separate slabs
 // (summed by reduce_slabs_kernel).
 // LDS rows are unpadded copies (RSo >= Tout, RSi >= Tin); range / padding handled by masks.
+//
+// LDS of conv5_wgrad_kernel, in floats: one stage of IPS items.  The allocation is the two tiles and four floats; what
+// the round-up of in_tile to 16 bytes does not use of the four stays behind it as slack.
+struct Conv5WgradLds {
+  int dout, in, end;
+};
+__host__ __device__ constexpr Conv5WgradLds conv5_wgrad_layout(int IPS, int F, int RSo, int CW, int RSi) {
+  LdsCarver c;
+  Conv5WgradLds l = {};
+  l.dout = c.take(IPS * F * RSo);                    // [IPS][F][RSo]
+  l.in = c.take(IPS * CW * RSi, 4);                  // [IPS][CW][RSi]
+  c.take(4 - (l.in - IPS * F * RSo));
+  l.end = c.end;
+  return l;
+}
 template <int MODE, typename AT, bool BOTH>
 __global__ __launch_bounds__(256) void conv5_wgrad_kernel(WgradArgs a) {
   using IT = typename std::conditional<MODE == 0, float, AT>::type;
@@ -2803,9 +2929,8 @@ __global__ __launch_bounds__(256) void conv5_wgrad_kernel(WgradArgs a) {
   const int c_tile = c_base + ct * 16;
   const bool wave_live = c_tile < cin && grp < n_grp;
   const int n_real = (MODE == 0) ? cin - 1 : cin;           // channels that exist in memory
-  const int do_sz = (a.IPS * a.F * a.RSo + 3) & ~3;
-  float* do_tile = smem;                                    // [IPS][F][RSo]
-  float* in_tile = smem + do_sz;                            // [IPS][CW][RSi]
+  const Conv5WgradLds L = conv5_wgrad_layout(a.IPS, a.F, a.RSo, a.CW, a.RSi);
+  float *do_tile = smem + L.dout, *in_tile = smem + L.in;
   const int64_t i_lo = (int64_t)blockIdx.x * a.items_per_wg;
   const int64_t i_hi = (i_lo + a.items_per_wg) < a.items ? (i_lo + a.items_per_wg) : a.items;
   const int c_mine = c_tile + jl;                           // channel of this lane's B column
@@ -2991,10 +3116,11 @@ __global__ __launch_bounds__(256) void conv5_wgrad_kernel(WgradArgs a) {
   }
 }
 
-// dynamic LDS of conv5_wgrad_kernel (do_tile / in_tile at its top): per staged item F rows of RSo gradient samples and
-// CW rows of RSi input samples, IPS items, 4 floats for the rounding of do_sz
+// what launch_wgrad fits into its budgets: per staged item F rows of RSo gradient samples and CW rows of RSi input samples
 static int64_t conv5_wgrad_item_floats(int F, int RSo, int CW, int RSi) { return (int64_t)F * RSo + (int64_t)CW * RSi; }
-static size_t conv5_wgrad_lds(int ips, int64_t per_item) { return sizeof(float) * ((size_t)ips * per_item + 4); }
+static size_t conv5_wgrad_lds(const WgradArgs& a) {
+  return sizeof(float) * (size_t)conv5_wgrad_layout(a.IPS, a.F, a.RSo, a.CW, a.RSi).end;
+}
 
 // First-layer weight gradient for wide inputs (companion of conv5_fwd_glds_kernel; same preconditions).
 // A workgroup owns 64 input channels (one 16-channel tile per wave, all GT filter tiles) and a range of items;
@@ -3004,6 +3130,29 @@ static size_t conv5_wgrad_lds(int ips, int64_t per_item) { return sizeof(float) 
 // the odd last step is peeled, and lanes past the stage's last (item, step) pair read zero words the DMA never
 // writes instead of being masked after the load.  The dbias column (virtual all-ones channel `cin`, B fragment 1.0f)
 // rides along in wave 0 of channel group 0, which runs its own copy of the loop.
+//
+// LDS of conv5_wgrad_wide_kernel and conv5_wgrad_wide_bf16_kernel, in floats.  An item is its gradient image of `do_len`
+// floats and, at `in`, 64 input rows (`in_len` floats), rounded up to 16 bytes; buffer s starts at s * buf_len and holds
+// IPS items and 32 floats of slack (the last rows' junk columns read them); the 8 floats at `zero` are cleared once and
+// never staged.
+struct Conv5WgradWideLds {
+  int in, item_len, buf_len, zero, end;
+};
+__host__ __device__ constexpr Conv5WgradWideLds conv5_wgrad_wide_layout(int IPS, int do_len, int in_len) {
+  Conv5WgradWideLds l = {};
+  LdsCarver item;
+  item.take(do_len);
+  l.in = item.take(in_len);
+  l.item_len = item.take(0, 4);
+  LdsCarver c;
+  c.take(IPS * l.item_len);
+  c.take(32);
+  l.buf_len = c.end;
+  c.take(l.buf_len);
+  l.zero = c.take(8);
+  l.end = c.end;
+  return l;
+}
 template <int GT>
 __global__ __launch_bounds__(256) void conv5_wgrad_wide_kernel(WgradArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -3019,14 +3168,14 @@ __global__ __launch_bounds__(256) void conv5_wgrad_wide_kernel(WgradArgs a) {
   const int wave_s = __builtin_amdgcn_readfirstlane(wave);           // (scalar: the wave's role is a branch, not a mask)
   const bool wave_live = c_base + wave_s * 16 < cin;
   const bool with_bias = blockIdx.z == 0 && wave_s == 0;
-  const int do_len = a.F * a.Tout, in_len = 64 * a.Tin;             // per item (in_len: stride; cw*Tin are filled)
-  const int item_len = (do_len + in_len + 3) & ~3;
-  const int buf_len = a.IPS * item_len + 32;
+  const int do_len = a.F * a.Tout;                                  // per item; of the 64 * Tin input floats cw * Tin are filled
+  const Conv5WgradWideLds L = conv5_wgrad_wide_layout(a.IPS, do_len, 64 * a.Tin);
+  const int item_len = L.item_len, buf_len = L.buf_len;
   const int64_t i_lo = (int64_t)blockIdx.x * a.items_per_wg;
   const int64_t i_hi = (i_lo + a.items_per_wg) < a.items ? (i_lo + a.items_per_wg) : a.items;
   const int chan0 = a.chan_idx[zd.idx_off];
   // the tail of both buffers is read (masked) by the last rows' junk columns: keep it finite
-  for (int e = threadIdx.x; e < 2 * buf_len + 8; e += 256) smem[e] = 0.f;
+  for (int e = threadIdx.x; e < L.end; e += 256) smem[e] = 0.f;
   __syncthreads();
 
   auto stage = [&](int64_t is, int s) {
@@ -3035,7 +3184,7 @@ __global__ __launch_bounds__(256) void conv5_wgrad_wide_kernel(WgradArgs a) {
     for (int ii = wave; ii < n_it; ii += 4) {
       float* dst = buf + ii * item_len;
       glds_copy16((const float*)a.dout + ((is + ii) * a.Z + z) * (int64_t)do_len, dst, do_len >> 2, lane);
-      glds_copy16((const float*)a.in + ((is + ii) * a.Ctot + chan0 + c_base) * (int64_t)a.Tx, dst + do_len,
+      glds_copy16((const float*)a.in + ((is + ii) * a.Ctot + chan0 + c_base) * (int64_t)a.Tx, dst + L.in,
                   (cw * a.Tin) >> 2, lane);
     }
   };
@@ -3058,7 +3207,7 @@ __global__ __launch_bounds__(256) void conv5_wgrad_wide_kernel(WgradArgs a) {
     if (wave_s < n_it) {
       const unsigned dst = slot_lds + (unsigned)(s * buf_len) * 4;
       glds_run(do_q >> 6, do_tail, dst, do_src, lane16);
-      glds_run(in_q >> 6, in_tail, dst + (unsigned)do_len * 4, in_src, lane16);
+      glds_run(in_q >> 6, in_tail, dst + (unsigned)L.in * 4, in_src, lane16);
     }
     do_src += do_step;
     in_src += in_step;
@@ -3077,7 +3226,7 @@ __global__ __launch_bounds__(256) void conv5_wgrad_wide_kernel(WgradArgs a) {
     float one;
   };
   const int a_off = jl * a.Tout + q;                                   // dOut[g = jl (+16 gt)][t0 + q]
-  const int b_off = do_len + (wave * 16 + jl) * a.Tin + q;             // In[c][t0 + q + k]
+  const int b_off = L.in + (wave * 16 + jl) * a.Tin + q;               // In[c][t0 + q + k]
   // The packed loop (Tout >= 4): K index 4 st + q of a stage is step f % Tout of item f / Tout, f = 4 st + q, kept per
   // lane as three byte addresses that advance by four steps per issue.  A set is GT ds_read (dOut) + two ds_read2 and
   // one ds_read (the five tap samples).
@@ -3087,7 +3236,7 @@ __global__ __launch_bounds__(256) void conv5_wgrad_wide_kernel(WgradArgs a) {
     float b4;
   };
   constexpr int kSetReads = GT + 3;
-  const unsigned zero_addr = smem_base + (unsigned)(2 * buf_len) * 4;   // 8 floats behind the buffers: cleared above, never staged
+  const unsigned zero_addr = smem_base + (unsigned)L.zero * 4;
   auto run_packed = [&](auto bias, int sbuf, int n_it) {
     const unsigned buf_addr = smem_base + (unsigned)(sbuf * buf_len) * 4;
     unsigned a0 = buf_addr + (unsigned)a_off * 4, a1 = a0 + (unsigned)(16 * a.Tout) * 4, b = buf_addr + (unsigned)b_off * 4;
@@ -3239,10 +3388,9 @@ __global__ __launch_bounds__(256) void conv5_wgrad_wide_kernel(WgradArgs a) {
     }
 }
 
-// dynamic LDS of conv5_wgrad_wide_kernel and its bf16 twin (item_len / buf_len at their tops): two buffers of IPS items
-// + 32 floats, 8 floats behind them; an item is the gradient tile [F][T1] and 64 input rows of W samples
-static int conv5_wgrad_wide_item_floats(int F, int T1, int W) { return (F * T1 + 64 * W + 3) & ~3; }
-static size_t conv5_wgrad_wide_lds(int ips, int item_len) { return sizeof(float) * (size_t)(2 * (ips * item_len + 32) + 8); }
+static size_t conv5_wgrad_wide_lds(int ips, int do_len, int in_len) {
+  return sizeof(float) * (size_t)conv5_wgrad_wide_layout(ips, do_len, in_len).end;
+}
 
 // ---------------------------------------------------------------------------------------
 // BASELINE config 3: first-layer weight gradient on the bf16 matrix cores (companion of conv5_fwd_bf16_kernel).
@@ -3273,15 +3421,14 @@ __global__ __launch_bounds__(256) void conv5_wgrad_wide_bf16_kernel(WgradArgs a)
   const bool with_bias = blockIdx.z == 0 && wave == 0;
   const int do_len = 16 * a.F / 2;                                  // floats: 16 rows x F bf16 (rows >= Tout stay zero)
   const int do_real4 = (a.Tout * a.F * 2) >> 4;                     // 16-byte pieces actually copied
-  const int in_len = 64 * a.Tin;                                    // per item (stride; cw * Tin are filled)
-  const int item_len = (do_len + in_len + 3) & ~3;
-  const int buf_len = a.IPS * item_len + 32;
+  const Conv5WgradWideLds L = conv5_wgrad_wide_layout(a.IPS, do_len, 64 * a.Tin);   // of the 64 * Tin input floats cw * Tin are filled
+  const int item_len = L.item_len, buf_len = L.buf_len;
   const int64_t i_lo = (int64_t)blockIdx.x * a.items_per_wg;
   const int64_t i_hi = (i_lo + a.items_per_wg) < a.items ? (i_lo + a.items_per_wg) : a.items;
   const int chan0 = a.chan_idx[zd.idx_off];
   // zero everything once: the pad rows of the gradient images are never written by the DMA, and the tail of both
   // buffers is read by the last rows' junk columns
-  for (int e = threadIdx.x; e < 2 * buf_len + 8; e += 256) smem[e] = 0.f;
+  for (int e = threadIdx.x; e < L.end; e += 256) smem[e] = 0.f;
   __syncthreads();
 
   auto stage = [&](int64_t is, int s) {
@@ -3296,9 +3443,9 @@ __global__ __launch_bounds__(256) void conv5_wgrad_wide_bf16_kernel(WgradArgs a)
         if (IN16)      // bf16 input rows (2 Tin bytes each): cw is a multiple of 8 (host check), whole 16-byte pieces
           glds_copy16(reinterpret_cast<const float*>((const unsigned short*)a.in +
                                                      ((is + ii) * a.Ctot + chan0 + c_base) * (int64_t)a.Tx),
-                      dst + do_len, (cw * a.Tin) >> 3, lane);
+                      dst + L.in, (cw * a.Tin) >> 3, lane);
         else
-          glds_copy16((const float*)a.in + ((is + ii) * a.Ctot + chan0 + c_base) * (int64_t)a.Tx, dst + do_len,
+          glds_copy16((const float*)a.in + ((is + ii) * a.Ctot + chan0 + c_base) * (int64_t)a.Tx, dst + L.in,
                       (cw * a.Tin) >> 2, lane);
       } else {
         // a missing second item of the last pair: its gradient image must read as zero (the x rows may be stale)
@@ -3317,7 +3464,7 @@ __global__ __launch_bounds__(256) void conv5_wgrad_wide_bf16_kernel(WgradArgs a)
   const int ih = q >> 1, t0 = 8 * (q & 1);                            // this lane group's item of the pair, first step
   // transposed read: lane 4 r + p of a 16-lane group supplies row r, columns 4 p .. 4 p + 3 of a 4 x 16 block
   const unsigned a_byte = (unsigned)((t0 + (jl >> 2)) * a.F + 4 * (jl & 3)) * 2u;
-  const int b_off = do_len + (wave * 16 + jl) * a.Tin + t0;          // x[c][t0 ...]
+  const int b_off = L.in + (wave * 16 + jl) * a.Tin + t0;            // x[c][t0 ...]
   const unsigned smem_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) float*)smem;
   const bf16x8 ones = {0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80};
   int s = 0;
@@ -3344,7 +3491,7 @@ __global__ __launch_bounds__(256) void conv5_wgrad_wide_bf16_kernel(WgradArgs a)
       // B: 12 samples of this lane's channel, packed as even pairs (e0e1, e2e3, ...) and odd pairs (e1e2, e3e4, ...)
       unsigned int pe[6], po[5];
       if constexpr (IN16) {
-        const unsigned short* xr = reinterpret_cast<const unsigned short*>(smem + item_off + do_len) +
+        const unsigned short* xr = reinterpret_cast<const unsigned short*>(smem + item_off + L.in) +
                                    (wave * 16 + jl) * a.Tin + t0;
         unsigned int e[12];
 #pragma unroll
@@ -3393,9 +3540,6 @@ __global__ __launch_bounds__(256) void conv5_wgrad_wide_bf16_kernel(WgradArgs a)
     }
 }
 
-// an item of conv5_wgrad_wide_bf16_kernel (do_len / in_len at its top): a gradient image of 16 x F bf16 and 64 input
-// rows of W samples
-static int conv5_wgrad_wide_bf16_item_floats(int F, int W) { return (16 * F / 2 + 64 * W + 3) & ~3; }
 
 // sum the per-workgroup slabs: out[e] = sum_s part[s][e].  Block = 64 elements x 4 slab groups
 // (coalesced 256-B rows, 4 independent load streams per element, LDS combine).  blockIdx.y selects a run of
@@ -3762,45 +3906,146 @@ int per_zone_workgroups(const isd_conv4_plan* p, const Geo& g, int per_gpu) {
   return per_zone;
 }
 
-// every window the fused fp32 route admits (4 <= TT <= 16: 53 <= W <= 260) against the 150 KiB the route allows,
-// when this file is compiled; choose_route repeats the check for the shape and allocation of the call
-constexpr bool fused_fwd_layout_ok_for_every_window() {
-  for (int W = 53; W <= 260; ++W)
-    if (!conv4_fused_fwd_layout_ok(kFusedNW, 32, W, W - (kTaps - 1), 150 * 1024)) return false;
+// The LDS layouts, checked when this file is compiled: for every shape a kernel's route admits the allocation is inside
+// the route's budget and the regions read or written 16 bytes at a time (float4, LDS-DMA, b128 fragments) are aligned;
+// the sizes at the ends of each range are pinned.  The launch sites repeat the budget checks for the shape of the call.
+constexpr bool aligned4(int a, int b = 0, int c = 0, int d = 0) { return (a | b | c | d) % 4 == 0; }
+constexpr bool aligned16(int a, int b = 0, int c = 0, int d = 0) { return (a | b | c | d) % 16 == 0; }
+
+// the fused fp32 pair: 4 <= TT <= 16, that is 53 <= W <= 260
+constexpr bool fused_f32_layouts_ok() {
+  for (int W = 53; W <= 260; ++W) {
+    const int T1 = W - (kTaps - 1);
+    if (!conv4_fused_fwd_layout_ok(kFusedNW, 32, W, T1, kLdsRoute)) return false;
+    const FusedBwdLds b = conv4_fused_bwd_layout(32, W, T1);
+    if (!aligned4(b.ga, b.gb, b.at) || !aligned4(b.w4s, b.w3s) || b.end * 4 > kLdsWorkgroup) return false;
+  }
   return true;
 }
-static_assert(fused_fwd_layout_ok_for_every_window(), "conv4_fused_fwd_kernel: LDS regions overlap or exceed 150 KiB");
+static_assert(fused_f32_layouts_ok(), "conv4_fused_fwd_kernel / conv4_fused_bwd_kernel: LDS regions misaligned or over budget");
+static_assert(conv4_fused_fwd_layout(kFusedNW, 32, 53, 49).end * 4 == 68432 &&
+              conv4_fused_fwd_layout(kFusedNW, 32, 250, 246).end * 4 == 131472 &&
+              conv4_fused_fwd_layout(kFusedNW, 32, 260, 256).end * 4 == 134672, "conv4_fused_fwd_kernel: LDS size");
+static_assert(conv4_fused_bwd_layout(32, 53, 49).end * 4 == 63440 && conv4_fused_bwd_layout(32, 260, 256).end * 4 == 156176,
+              "conv4_fused_bwd_kernel: LDS size");
+
+// the fused bf16 pair: 4 <= TT <= 16; the forward runs two workgroups per CU at every one of them
+constexpr bool fused_bf16_layouts_ok() {
+  for (int TT = 4; TT <= 16; ++TT) {
+    const Fused16FwdLds f = conv4_fused_fwd_bf16_layout(kFusedNW, 32, TT);
+    if (!aligned16(f.t2, f.t3, f.red, f.bls) || !aligned16(f.w1s, f.w3s, f.w4s) || f.end > kLdsTwoPerCu) return false;
+    if (f.xt != f.t3 || f.xt_len > f.tile) return false;          // the x tile stays inside t3
+    const Fused16BwdLds b = conv4_fused_bwd_bf16_layout(TT);
+    if (!aligned16(b.sets, b.set_len, b.tile, b.gb) || !aligned16(b.xt, b.w4s, b.w3s) || b.end > kLdsWorkgroup) return false;
+  }
+  return true;
+}
+static_assert(fused_bf16_layouts_ok(), "conv4_fused_fwd_bf16_kernel / conv4_fused_bwd_bf16_kernel: LDS regions misaligned or over budget");
+static_assert(conv4_fused_fwd_bf16_layout(kFusedNW, 32, 4).end == 37056 && conv4_fused_fwd_bf16_layout(kFusedNW, 32, 16).end == 61632,
+              "conv4_fused_fwd_bf16_kernel: LDS size");
+static_assert(conv4_fused_bwd_bf16_layout(4).end == 55360 && conv4_fused_bwd_bf16_layout(16).end == 147520,
+              "conv4_fused_bwd_bf16_kernel: LDS size");
+
+// the classifier tails: eight waves, 32 filters
+constexpr TailLds kTailLds8 = featcnn_tail_layout(8, 32);
+static_assert(aligned4(kTailLds8.w3s, kTailLds8.w4s, kTailLds8.w3ts, kTailLds8.w4ts) && aligned4(kTailLds8.tiles, kTailSlot) &&
+              kTailLds8.end * 4 == 160336 && kTailLds8.end * 4 <= kLdsWorkgroup, "featcnn_tail_kernel: LDS layout");
+constexpr Tail16Lds kTail16Lds8 = featcnn_tail_bf16_layout(8, 32);
+static_assert(aligned16(kTail16Lds8.w3s, kTail16Lds8.w4s, kTail16Lds8.w3ts, kTail16Lds8.w4ts) &&
+              aligned16(kTail16Lds8.priv, kTail16Priv, kTail16Tile) && kTail16Lds8.end == 132096 && kTail16Lds8.end <= kLdsWorkgroup,
+              "featcnn_tail_bf16_kernel: LDS layout");
+
+// the layer-wise forward kernels.  make_geo fits IPW * CK * RS + w_len + 64 floats into its budget: the 64 cover the
+// layout's slack and rounding.  (The allocation is checked against kLdsRoute at every launch.)
+constexpr bool conv5_fwd_layouts_ok() {
+  for (int IPW = 1; IPW <= 16; ++IPW)
+    for (int CK = 4; CK <= kCK; CK += 4)
+      for (int RS = 5; RS <= 36; ++RS)
+        for (int GT = 1; GT <= 2; ++GT) {
+          const int w_len = conv5_fwd_w_len(CK, GT);
+          const Conv5FwdLds one = conv5_fwd_layout(1, IPW, CK, RS, w_len), two = conv5_fwd_layout(2, IPW, CK, RS, w_len);
+          if (!aligned4(one.in, one.w, two.in, two.w) || !aligned4(two.buf_len)) return false;
+          if (one.end > IPW * CK * RS + w_len + 64 || two.end != 4 + 2 * two.buf_len) return false;
+        }
+  return true;
+}
+static_assert(conv5_fwd_layouts_ok(), "conv5_fwd_kernel / conv5_fwd_glds_kernel / conv5_fwd_bf16_kernel: LDS layout");
+static_assert(conv5_fwd_layout(1, 1, 4, 5, conv5_fwd_w_len(4, 1)).end * 4 == 1504 &&
+              conv5_fwd_layout(1, 1, 4, 9431, conv5_fwd_w_len(4, 2)).end * 4 == kLdsRoute, "conv5_fwd_kernel: LDS size");
+static_assert(conv5_fwd_layout(2, 1, kCK, 5, conv5_fwd_w_len(kCK, 1)).end * 4 == 22032 &&
+              conv5_fwd_layout(2, 1, kCK, 438, conv5_fwd_w_len(kCK, 2)).end * 4 == 153360, "conv5_fwd_glds_kernel: LDS size");
+// conv5_fwd_bf16_kernel (bf16_mfma_ok, first_layer_forward): 4, 8 or 16 items, 5 <= W <= 17
+static_assert(conv5_fwd_layout(2, 4, kCK, 5, kConv5FwdBf16WLen).end * 4 == 38160 &&
+              conv5_fwd_layout(2, 16, kCK, 17, kConv5FwdBf16WLen).end * 4 == 102672 && 102672 <= kLdsRoute, "conv5_fwd_bf16_kernel: LDS size");
+
+// conv5_dx_kernel: one tile, checked against kLdsRoute at the launch
+static_assert(conv5_dx_layout(16, 1).end * 4 == 64 && conv5_dx_layout(32, 1200).end * 4 == kLdsRoute, "conv5_dx_kernel: LDS size");
+
+// conv5_wgrad_kernel: launch_wgrad fits IPS * per_item + 4 floats into its budgets, and that is the allocation
+constexpr bool conv5_wgrad_layouts_ok() {
+  for (int IPS = 1; IPS <= 16; ++IPS)
+    for (int F = 16; F <= 32; F += 16)
+      for (int CW = 16; CW <= 64; CW += 16)
+        for (int RSo = 1; RSo <= 13; ++RSo)
+          for (int RSi = RSo; RSi <= RSo + 5; ++RSi) {
+            const Conv5WgradLds l = conv5_wgrad_layout(IPS, F, RSo, CW, RSi);
+            if (!aligned4(l.dout, l.in) || l.in + IPS * CW * RSi > l.end || l.end != IPS * (F * RSo + CW * RSi) + 4) return false;
+          }
+  return true;
+}
+static_assert(conv5_wgrad_layouts_ok(), "conv5_wgrad_kernel: LDS layout");
+static_assert(conv5_wgrad_layout(1, 16, 1, 16, 5).end * 4 == 400 && conv5_wgrad_layout(1, 32, 396, 64, 400).end * 4 == 153104 &&
+              153104 <= kLdsRoute, "conv5_wgrad_kernel: LDS size");
+
+// the wide weight gradients: up to four items a stage; fp32 inside kLdsStage64K (first_layer_backward tests it), the
+// bf16 kernel (four items, 32 filters, 5 <= W <= 17) inside kLdsStage48K
+constexpr bool conv5_wgrad_wide_layouts_ok() {
+  for (int IPS = 1; IPS <= 4; ++IPS)
+    for (int W = 5; W <= 90; ++W) {
+      const Conv5WgradWideLds l = conv5_wgrad_wide_layout(IPS, 32 * (W - 4), 64 * W), h = conv5_wgrad_wide_layout(IPS, 16 * (W - 4), 64 * W);
+      if (!aligned4(l.item_len, l.buf_len, l.zero) || !aligned4(h.item_len, h.buf_len, h.zero)) return false;
+      if (l.end != l.zero + 8 || l.zero != 2 * l.buf_len || l.buf_len != IPS * l.item_len + 32) return false;
+    }
+  for (int W = 5; W <= 17; ++W) {
+    const Conv5WgradWideLds l = conv5_wgrad_wide_layout(4, 16 * 32 / 2, 64 * W);
+    if (!aligned4(l.in, l.item_len, l.buf_len) || l.end * 4 > kLdsStage48K) return false;
+  }
+  return true;
+}
+static_assert(conv5_wgrad_wide_layouts_ok(), "conv5_wgrad_wide_kernel / conv5_wgrad_wide_bf16_kernel: LDS layout");
+static_assert(conv5_wgrad_wide_layout(1, 16 * 1, 64 * 5).end * 4 == 2976 && conv5_wgrad_wide_layout(1, 32 * 82, 64 * 86).end * 4 == 65312 &&
+              65312 <= kLdsStage64K, "conv5_wgrad_wide_kernel: LDS size");
+static_assert(conv5_wgrad_wide_layout(4, 16 * 32 / 2, 64 * 5).end * 4 == 18720 && conv5_wgrad_wide_layout(4, 16 * 32 / 2, 64 * 17).end * 4 == 43296,
+              "conv5_wgrad_wide_bf16_kernel: LDS size");
 
 int choose_route(const isd_conv4_plan* p, Geo& g) {
   const int F = p->F;
   const size_t bwd16 = conv4_fused_bwd_bf16_lds(g.TT);
-  if (p->n_layers == 4 && F == 32 && p->act_bf16 && p->max_cz <= 16 && g.TT <= 16 && g.TT >= 4 && bwd16 <= 160 * 1024) {
+  if (p->n_layers == 4 && F == 32 && p->act_bf16 && p->max_cz <= 16 && g.TT <= 16 && g.TT >= 4 && bwd16 <= kLdsWorkgroup) {
     // reference-native shape, bf16 activations: the fused pair on the bf16 matrix cores; the LDS test is a condition of
     // the route, not an invariant
     g.route = Route::kFusedBf16;
     g.fwd_lds = conv4_fused_fwd_bf16_lds(g.TT);
     g.bwd_lds = bwd16;
-    g.fwd_per_zone = per_zone_workgroups(p, g, g.fwd_lds <= 80 * 1024 ? 512 : 256);   // two workgroups per CU when the tiles allow
+    g.fwd_per_zone = per_zone_workgroups(p, g, g.fwd_lds <= kLdsTwoPerCu ? 512 : 256);   // two workgroups per CU when the tiles allow
     g.bwd_per_zone = per_zone_workgroups(p, g, 256);
     g.keep_dgelu = g.prep16 = true;
   } else if (p->n_layers == 4 && F == 32 && !p->act_bf16 && p->max_cz <= 16 && g.TT <= 16 && (F * g.T1) % 4 == 0 &&
              g.TT >= 4) {
     // reference-native shape: one persistent fused kernel each way (register-resident weights, activations and
-    // gradient tiles through LDS).  The forward always keeps GELU'(A4) on this route:
-    //   TT <= 16  =>  T1 <= 256  =>  W = T1 + 4 <= 260, and both sizes grow monotonically with W.  At W = 260, T1 = 256:
-    //   forward   4 + 4160 + 2 * 8192 + 8 * 32 + 20 * 640 + 64      = 33668 floats = 134672 bytes <= 150 KiB (153600)
-    //   backward  4164 + 4 + 3 * (8192 + 4) + 16 * 640 + 32 + 16   = 39044 floats = 156176 bytes <= 160 KiB (163840)
-    // so both kernels fit for every shape the predicate admits, and neither a forward that keeps plain A4 (store == 1)
-    // nor a fall-through to the layer-wise chain can happen.  The check below fails loudly if a tile size changes that.
+    // gradient tiles through LDS).  The forward always keeps GELU'(A4) on this route: TT <= 16 is W <= 260, and both
+    // kernels fit for every such window (fused_f32_layouts_ok above), so neither a forward that keeps plain A4
+    // (store == 1) nor a fall-through to the layer-wise chain can happen.  The check below fails loudly if a tile size
+    // changes that.
     g.route = Route::kFusedF32;
     g.fwd_lds = conv4_fused_fwd_lds(kFusedNW, F, p->W, g.T1);
     g.bwd_lds = conv4_fused_bwd_lds(F, p->W, g.T1);
-    ISD_CHECK_ARG(g.fwd_lds <= 150 * 1024 && g.bwd_lds <= 160 * 1024,
+    ISD_CHECK_ARG(g.fwd_lds <= kLdsRoute && g.bwd_lds <= kLdsWorkgroup,
                   "conv4: the fused fp32 kernels need %zu / %zu bytes of LDS at window_len=%d", g.fwd_lds, g.bwd_lds, p->W);
-    // the forward's regions follow one another without overlap and end inside the allocation (an overlap of xz and t2
-    // was a race between waves: wrong features from run to run, never a fault)
+    // the forward's tiles are aligned and end inside the allocation (an overlap of xz and t2 was a race between waves:
+    // wrong features from run to run, never a fault; the carver rules it out)
     ISD_CHECK_ARG(conv4_fused_fwd_layout_ok(kFusedNW, F, p->W, g.T1, g.fwd_lds),
-                  "conv4: the fused fp32 forward's LDS regions overlap at window_len=%d", p->W);
+                  "conv4: the fused fp32 forward's LDS layout at window_len=%d", p->W);
     g.fwd_per_zone = g.bwd_per_zone = per_zone_workgroups(p, g, 256);
     g.keep_dgelu = true;
   }
@@ -3825,10 +4070,10 @@ int make_geo(const isd_conv4_plan* p, int64_t B, int64_t T, Geo& g) {
     const int GTf = p->F / 16;
     const int64_t row = g.RS_a > g.RS_b ? g.RS_a : g.RS_b;
     g.CK = kCK;
-    int64_t fit = (64 * 1024 / 4 - (int64_t)(g.CK / 4) * kTaps * GTf * 64) / (g.CK * row);
+    int64_t fit = (kLdsStage64K / 4 - (int64_t)(g.CK / 4) * kTaps * GTf * 64) / (g.CK * row);
     if (fit < 1) {
-      while (g.CK > 4 && (150 * 1024 / 4 - 64 - (int64_t)(g.CK / 4) * kTaps * GTf * 64) / (g.CK * row) < 1) g.CK -= 4;
-      fit = (150 * 1024 / 4 - 64 - (int64_t)(g.CK / 4) * kTaps * GTf * 64) / (g.CK * row);
+      while (g.CK > 4 && (kLdsRoute / 4 - 64 - (int64_t)(g.CK / 4) * kTaps * GTf * 64) / (g.CK * row) < 1) g.CK -= 4;
+      fit = (kLdsRoute / 4 - 64 - (int64_t)(g.CK / 4) * kTaps * GTf * 64) / (g.CK * row);
     }
     ISD_CHECK_ARG(fit >= 1, "conv4: window_len=%d is too long for the LDS tile (about 9000 samples)", p->W);
     if (g.IPW > fit) g.IPW = (int)fit;
@@ -3953,7 +4198,7 @@ static int launch_conv(int mode, int bf16, const ConvArgs& a, int n_zones, hipSt
   ISD_CHECK_ARG(blocks <= 0x7fffffffLL, "conv4: too many items");
   const int GT = a.F / 16;
   const size_t lds = conv5_fwd_lds(a.IPW, a.CK, a.RS, GT);
-  ISD_CHECK_ARG(lds <= 150 * 1024, "conv4: LDS tile of %zu bytes exceeds 150 KiB (window too long)", lds);
+  ISD_CHECK_ARG(lds <= kLdsRoute, "conv4: LDS tile of %zu bytes exceeds 150 KiB (window too long)", lds);
   const int tiles = a.IPW * a.TT;                     // column tiles per workgroup -> tiles per wave (1, 2 or 4)
   const int NT = tiles > 8 ? 4 : tiles > 4 ? 2 : 1;
   return launch_lds(conv5_fwd_instance(mode, bf16, GT, NT), dim3((unsigned)blocks, n_zones), dim3(256), lds, st, a);
@@ -4028,7 +4273,7 @@ static int first_layer_forward(const isd_conv4_plan* p, const Geo& g, const floa
     if (ipw > per_cu) ipw = (int)per_cu;
   }
   const size_t lds = conv5_fwd_glds_lds(ipw, p->W, GT);
-  if (g.lin0 && p->dma_ok && !p->act_bf16 && p->max_cz > kCK && g.TT <= 4 * NT && ipw >= 1 && lds <= 150 * 1024 &&
+  if (g.lin0 && p->dma_ok && !p->act_bf16 && p->max_cz > kCK && g.TT <= 4 * NT && ipw >= 1 && lds <= kLdsRoute &&
       ((uintptr_t)x & 15) == 0) {
     d.IPW = ipw;
     void (*k)(ConvArgs);
@@ -4099,12 +4344,12 @@ static void (*conv5_wgrad_instance(int F))(WgradArgs) {
 
 static int launch_wgrad(int mode, int bf16, WgradArgs a, int n_zones, int cin_max, hipStream_t st) {   // `a` by value: the stage geometry chosen here must not leak into the caller's next launch
   int64_t per_item = conv5_wgrad_item_floats(a.F, a.RSo, a.CW, a.RSi);
-  int ips = (int)((96 * 1024 / 4 - 4) / per_item);
-  if (ips < 1) ips = (int)((150 * 1024 / 4 - 4) / per_item);   // long windows: one item in the large LDS allocation
+  int ips = (int)((kLdsStage96K / 4 - 4) / per_item);
+  if (ips < 1) ips = (int)((kLdsRoute / 4 - 4) / per_item);   // long windows: one item in the large LDS allocation
   a.seg_len = 0;
   if (ips < 1) {
     // longer still: time segments (the reduction dimension of the weight gradient), one item per stage
-    int seg = (int)((150 * 1024 / 4 - 64 - (int64_t)a.CW * (kTaps - 1)) / (a.F + a.CW)) & ~3;
+    int seg = (int)((kLdsRoute / 4 - 64 - (int64_t)a.CW * (kTaps - 1)) / (a.F + a.CW)) & ~3;
     ISD_CHECK_ARG(seg >= 16, "conv4 wgrad: no LDS segment fits");
     a.seg_len = seg;
     a.RSo = seg;
@@ -4113,8 +4358,8 @@ static int launch_wgrad(int mode, int bf16, WgradArgs a, int n_zones, int cin_ma
     per_item = conv5_wgrad_item_floats(a.F, a.RSo, a.CW, a.RSi);
     ips = 1;
   }
-  if (ips > 1 && per_item * 4 > 32 * 1024) ips = 1;           // big items: one per stage, 2-3 workgroups per CU
-  const int ips_occ = (int)((32 * 1024 / 4) / per_item);      // prefer <= 32 KiB so several workgroups share a CU
+  if (ips > 1 && per_item * 4 > kLdsStage32K) ips = 1;           // big items: one per stage, 2-3 workgroups per CU
+  const int ips_occ = (int)((kLdsStage32K / 4) / per_item);      // prefer <= 32 KiB so several workgroups share a CU
   if (ips_occ >= 1 && ips > ips_occ) ips = ips_occ;
   if (ips > 16) ips = 16;
   if (ips > a.items_per_wg) ips = a.items_per_wg;
@@ -4126,7 +4371,7 @@ static int launch_wgrad(int mode, int bf16, WgradArgs a, int n_zones, int cin_ma
   void (*k)(WgradArgs);
   if (mode == 0) k = bf16 ? conv5_wgrad_instance<0, bf16_t>(a.F) : conv5_wgrad_instance<0, float>(a.F);
   else k = bf16 ? conv5_wgrad_instance<1, bf16_t>(a.F) : conv5_wgrad_instance<1, float>(a.F);
-  return launch_lds(k, dim3((unsigned)wgs, n_zones, zgroups), dim3(256), conv5_wgrad_lds(ips, per_item), st, a);
+  return launch_lds(k, dim3((unsigned)wgs, n_zones, zgroups), dim3(256), conv5_wgrad_lds(a), st, a);
 }
 
 // cnn3 / cnn4 gradient in natural [F][F][5] layout -> flat gradient block
@@ -4169,19 +4414,19 @@ static int first_layer_backward(const isd_conv4_plan* p, const Geo& g, const flo
   const int ipw = (int)cdiv(g.items, r_target);
   const int R = (int)cdiv(g.items, ipw);
   const dim3 grid((unsigned)R, p->Z, zg);
-  const int item_len = conv5_wgrad_wide_item_floats(F, g.T1, p->W);
+  const int in_len = 64 * p->W;                       // an item: its gradient tile [F][T1] and 64 input rows of W samples
   int ips = 4;
-  while (ips > 1 && conv5_wgrad_wide_lds(ips, item_len) > 48 * 1024) --ips;
-  const size_t lds = conv5_wgrad_wide_lds(ips, item_len);
+  while (ips > 1 && conv5_wgrad_wide_lds(ips, F * g.T1, in_len) > kLdsStage48K) --ips;
+  const size_t lds = conv5_wgrad_wide_lds(ips, F * g.T1, in_len);
   if (tap16) {
     // bf16 matrix cores: item pairs per K step
     const int ips16 = 4;
     w.items_per_wg = ipw; w.IPS = ips16;
     rc = launch_lds(in16 ? conv5_wgrad_wide_bf16_kernel<2, true> : conv5_wgrad_wide_bf16_kernel<2, false>, grid, dim3(256),
-                    conv5_wgrad_wide_lds(ips16, conv5_wgrad_wide_bf16_item_floats(F, p->W)), st, w);
+                    conv5_wgrad_wide_lds(ips16, 16 * F / 2, in_len), st, w);   // gradient image: 16 rows x F bf16
     n_slabs0 = R;
     g_first_wgrad_path = 2;
-  } else if (g.lin0 && p->dma_ok && !p->act_bf16 && p->max_cz >= 64 && (F * g.T1) % 4 == 0 && lds <= 64 * 1024 &&
+  } else if (g.lin0 && p->dma_ok && !p->act_bf16 && p->max_cz >= 64 && (F * g.T1) % 4 == 0 && lds <= kLdsStage64K &&
              ((uintptr_t)x & 15) == 0 && ((uintptr_t)g2 & 15) == 0) {
     w.items_per_wg = ipw; w.IPS = ips;
     rc = launch_lds(F == 32 ? conv5_wgrad_wide_kernel<2> : conv5_wgrad_wide_kernel<1>, grid, dim3(256), lds, st, w);
@@ -4260,11 +4505,11 @@ static int featcnn_step_impl(const isd_conv4_plan* p, const float* x, const floa
   constexpr int BNW = 8;                                          // bf16 matrix cores: eight waves, an item per wave and round
   int blocks = tail_blocks(TNW);                                  // one round of eight items until every CU has a workgroup
   size_t lds = featcnn_tail_lds(TNW, F);
-  ISD_CHECK_ARG(lds <= 160 * 1024 && (int64_t)blocks * t.slab <= g.total - g.o_part, "isd_featcnn_step: workspace");
+  ISD_CHECK_ARG(lds <= kLdsWorkgroup && (int64_t)blocks * t.slab <= g.total - g.o_part, "isd_featcnn_step: workspace");
   if (tap16) {
     blocks = tail_blocks(BNW * 2);
     lds = featcnn_tail_bf16_lds(BNW, F);
-    ISD_CHECK_ARG(lds <= 160 * 1024 && (int64_t)blocks * t.slab <= g.total - g.o_part, "isd_featcnn_step: workspace");
+    ISD_CHECK_ARG(lds <= kLdsWorkgroup && (int64_t)blocks * t.slab <= g.total - g.o_part, "isd_featcnn_step: workspace");
     rc = launch_lds(featcnn_tail_bf16_kernel<BNW>, dim3(blocks), dim3(BNW * 64), lds, st, t);
   } else {
     rc = launch_lds(featcnn_tail_kernel<TNW>, dim3(blocks), dim3(TNW * 64), lds, st, t);
@@ -4387,7 +4632,7 @@ static int conv4_backward_impl(const isd_conv4_plan* p, const float* x, const fl
   rc = first_layer_backward(p, g, x, T, params, g2, dparams, ws, st);
   if (rc || !dx) return rc;
   const size_t lds = conv5_dx_lds(F, g.T1);
-  ISD_CHECK_ARG(lds <= 150 * 1024, "isd_conv4_backward_x: window_len=%d is too long for the gradient tile", p->W);
+  ISD_CHECK_ARG(lds <= kLdsRoute, "isd_conv4_backward_x: window_len=%d is too long for the gradient tile", p->W);
   ISD_CHECK_ARG(g.items <= 0x7fffffffLL, "isd_conv4_backward_x: too many items");
   ISD_HIP_TRY(hipMemsetAsync(dx, 0, sizeof(float) * (size_t)B * p->Ctot * T, st));
   return launch_lds(conv5_dx_kernel, dim3((unsigned)g.items, p->Z), dim3(256), lds, st, g2, ws + g.o_eff, p->d_zones,
