@@ -68,6 +68,8 @@ SIGNATURES = {
     "isd_cov_group_mean": (_i, [_p, _i, _p, _p, _i, _p, _i64, _i, _i, _p]),
     "isd_csp_power_f32": (_i, [_p, _p, _p, _i64, _i, _i, _i, _i, _p]),
     "isd_csp_power_f64": (_i, [_p, _p, _p, _i64, _i, _i, _i, _i, _p]),
+    "isd_fb_trial_cov": (_i, [_p, _p, _p, _i64, _i, _i, _p]),
+    "isd_fb_csp_power": (_i, [_p, _p, _p, _p, _i64, _i, _i, _i, _i, _p]),
     "isd_ica_step_work_bytes": (_i64, [_i64, _i, _i, _i, _i]),
     "isd_ica_step_f32": (_i, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i, _i, _i, _p]),
     "isd_ica_step_f64": (_i, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i, _i, _i, _p]),

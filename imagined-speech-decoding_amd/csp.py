@@ -8,7 +8,8 @@ the fused projection + average power (+ log) of ``transform``.  The decompositio
 is host work in float64 (``decompose``): a generalised eigen-decomposition for two classes, Pham's approximate joint
 diagonalisation with mutual-information ordering (Grosse-Wentrup & Buss 2008) for more, restated from the published
 method.  MNE is not vendored in the reference and is not installed here: parity is pinned against a NumPy restatement
-(tests/test_csp_*.py), not against MNE.  There is no CPU fallback.
+(tests/test_csp_*.py), not against MNE.  There is no CPU fallback.  One CSP per band of a filterbank, on the raw
+trials: ``isd_amd.FBCSP`` (fbcsp.py).
 """
 import ctypes as C
 

@@ -2532,3 +2532,379 @@ static constexpr decltype(&features_grad_kernel<float>) kern[2] = {features_grad
   }
   return ISD_OK;
 }
+
+// ------------------------------------------------------------------------------------------------ filter-bank CSP
+// The two data-sized steps of isd_amd.FBCSP (Ang et al. 2008: one CSP per band of a filterbank), without the
+// [n][n_bands][C][T] filtered map in memory.  Both run a band's gain and cascade with grad_cascade: one row per lane,
+// a 32-sample chunk at a time, the section states carried in LDS and cleared at the start of every workgroup, so a
+// trial's result does not depend on the batch or on earlier launches.
+//
+//   fb_cov_kernel   cov[i][b] = Y Y^T / T, Y = band b of trial i.  A workgroup has one trial and BW bands; a band has
+//                   NW waves (1 for C <= 64, 2 above), lane = channel.  Per chunk the workgroup stages the trial's x
+//                   rows in LDS once (coalesced along T, fetched into registers one chunk ahead), every wave filters
+//                   its rows and writes them, samples past T zeroed, into its band's [64 NW][32 + 4] LDS tile, and the
+//                   band's waves feed the UPPER 16x16 tiles to v_mfma_f32_16x16x4_f32 as trial_cov_kernel does
+//                   (csp.hip): 10 tiles in one wave at C = 64, 36 over two waves at C = 128.  Elements on or above the
+//                   diagonal are stored twice, at [a][c] and [c][a].
+//   fb_pow_kernel   out[i][b][j] = mean_t y^2, y = band b of the projected row z = sum_c w[b][j][c] x_i[c][.]: the
+//                   projection commutes with the filter and leaves m rows to filter instead of C.  A workgroup has G
+//                   trials and up to four bands, one wave per band, lane = (trial, component).  Per chunk the workgroup
+//                   stages its trials' x rows in LDS (fetched one chunk ahead), every wave forms z = W_b x of each trial
+//                   on the matrix cores (two 16x16 tiles, W_b's fragments in registers for the whole kernel) into its
+//                   own LDS tile, every lane reads its row, filters it and adds y^2 sample by sample, chunk by chunk:
+//                   a fixed order.
+namespace isd {
+
+constexpr int kFcLD = kL + 4;                         // LDS row stride of a chunk tile (floats): 16-byte rows, skewed banks
+constexpr int kFcStateDoubles = 2 * 64;               // carried state of one section of one wave
+constexpr size_t kFcMaxLds = 160 * 1024;
+
+template <typename VT, int NW, int BW>
+__global__ __launch_bounds__(64 * NW * BW) void fb_cov_kernel(
+    const FbSec* __restrict__ secs, const SerSec* __restrict__ sers, const FbBand* __restrict__ bands,
+    const int* __restrict__ map, int nb, int ns, int nb_out, const float* __restrict__ x, float* __restrict__ cov,
+    int C, int T) {
+  constexpr int NT = 64 * NW * BW, ROWS = 64 * NW, LD = kFcLD, MAXQ = NW == 1 ? 10 : 18;
+  constexpr int NPRE = (ROWS * kL + NT - 1) / NT;      // staged elements per thread and chunk
+  extern __shared__ __attribute__((aligned(16))) unsigned char fc_smem[];
+  double* st_all = reinterpret_cast<double*>(fc_smem);                   // [BW * NW][ns][2][64]
+  float* xs = reinterpret_cast<float*>(st_all + BW * NW * ns * kFcStateDoubles);   // [ROWS][LD]
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), wb = wave / NW, wc = wave % NW;
+  const int groups = (nb + BW - 1) / BW;
+  const int trial = blockIdx.x / groups, bi = (blockIdx.x % groups) * BW + wb;
+  const bool active = bi < nb;                                           // wave-uniform
+  float* ys = xs + ROWS * LD + wb * ROWS * LD;                           // the band's filtered chunk, [ROWS][LD]
+  double* st = st_all + wave * ns * kFcStateDoubles;
+  const int nt = (C + 15) >> 4, Cp = nt * 16, U = nt * (nt + 1) / 2;
+  const float* xi = x + (int64_t)trial * C * T;
+  const int ch = wc * 64 + lane;                                         // the lane's channel
+
+  for (int e = 0; e < 2 * ns; ++e) st[e * 64 + lane] = 0.0;
+  int ti[MAXQ], tj[MAXQ];
+  f32x4 acc[MAXQ];
+#pragma unroll
+  for (int q = 0; q < MAXQ; ++q) {
+    int u = q * NW + wc, a = 0;                                          // u-th upper tile, row-major over (ti <= tj)
+    while (a < nt && u >= nt - a) { u -= nt - a; ++a; }
+    ti[q] = a;
+    tj[q] = a + u;
+    acc[q] = (f32x4)(0.f);
+  }
+  const FbSec* bsec = secs + (active ? bi : 0) * ns;
+  const SerSec* bser = std::is_same<VT, float>::value ? sers + (active ? bi : 0) * ns : nullptr;
+  const FbBand band = bands[active ? bi : 0];
+
+  float pre[NPRE];
+#pragma unroll
+  for (int i = 0; i < NPRE; ++i) {
+    const int e = i * NT + tid, c = e >> 5, k = e & 31;
+    // never past a row, never past C rows; branch-free (loads behind a branch are waited for one by one) and not
+    // looked at before the store below (a select here would wait for the load)
+    pre[i] = xi[(c < C && k < T) ? (int64_t)c * T + k : 0];
+  }
+  for (int t0 = 0; t0 < T; t0 += kL) {
+    __syncthreads();                                                     // the previous chunk has been consumed
+#pragma unroll
+    for (int i = 0; i < NPRE; ++i) {
+      const int e = i * NT + tid, c = e >> 5, k = e & 31;
+      if (e < Cp * kL) xs[c * LD + k] = (c < C && t0 + k < T) ? pre[i] : 0.f;   // rows C .. Cp - 1 are zeros
+    }
+    __syncthreads();
+    if (t0 + kL < T) {
+#pragma unroll
+      for (int i = 0; i < NPRE; ++i) {
+        const int e = i * NT + tid, c = e >> 5, t = t0 + kL + (e & 31);
+        pre[i] = xi[(c < C && t < T) ? (int64_t)c * T + t : 0];
+      }
+    }
+    if (active) {
+      float io[kL];
+      float4 xv[kL / 4];                                                 // rows >= Cp of xs are never written:
+#pragma unroll
+      for (int q = 0; q < kL / 4; ++q) xv[q] = *reinterpret_cast<const float4*>(xs + ch * LD + 4 * q);
+#pragma unroll
+      for (int q = 0; q < kL / 4; ++q) {                                 // their lanes filter zeros
+        io[4 * q] = ch < Cp ? xv[q].x : 0.f; io[4 * q + 1] = ch < Cp ? xv[q].y : 0.f;
+        io[4 * q + 2] = ch < Cp ? xv[q].z : 0.f; io[4 * q + 3] = ch < Cp ? xv[q].w : 0.f;
+      }
+      grad_cascade<VT>(io, bsec, bser, band, ns, st, lane);
+#pragma unroll
+      for (int j = 0; j < kL; ++j) io[j] = t0 + j < T ? io[j] : 0.f;     // the filter rings on past T: not part of Y
+#pragma unroll
+      for (int q = 0; q < kL / 4; ++q)
+        *reinterpret_cast<float4*>(ys + ch * LD + 4 * q) = make_float4(io[4 * q], io[4 * q + 1], io[4 * q + 2], io[4 * q + 3]);
+    }
+    if constexpr (NW == 1) wave_lds_sync(); else __syncthreads();        // the band's tile is complete
+    if (NW == 1 && nt == 4) {
+      if (active) {                                                      // all ten tiles: four row blocks feed them
+        float a[4][kL / 4];
+#pragma unroll
+        for (int rb = 0; rb < 4; ++rb)
+#pragma unroll
+          for (int k = 0; k < kL / 4; ++k) a[rb][k] = ys[(rb * 16 + (lane & 15)) * LD + (lane >> 4) + 4 * k];
+        __builtin_amdgcn_sched_barrier(0);                               // every fragment is requested before the first MFMA
+#pragma unroll
+        for (int k = 0; k < kL / 4; ++k) {
+          int u = 0;
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = i; j < 4; ++j, ++u)
+              if (u < MAXQ) acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i][k], a[j][k], acc[u], 0, 0, 0);
+        }
+      }
+    } else if (active) {
+#pragma unroll
+      for (int q = 0; q < MAXQ; ++q) {
+        if (q * NW + wc < U) {                                           // wave-uniform
+          const float* pa = ys + (ti[q] * 16 + (lane & 15)) * LD + (lane >> 4);
+          const float* pb = ys + (tj[q] * 16 + (lane & 15)) * LD + (lane >> 4);
+#pragma unroll
+          for (int k = 0; k < kL; k += 4) acc[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(pa[k], pb[k], acc[q], 0, 0, 0);
+        }
+      }
+    }
+  }
+  if (!active) return;
+  float* ci = cov + ((int64_t)trial * nb_out + map[bi]) * C * C;
+  const float den = (float)T;
+#pragma unroll
+  for (int q = 0; q < MAXQ; ++q) {
+    if (q * NW + wc < U) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int a = ti[q] * 16 + 4 * (lane >> 4) + r, b = tj[q] * 16 + (lane & 15);
+        if (a <= b && b < C) {                                           // a <= b < C; the lower triangle is the mirror
+          const float v = acc[q][r] / den;
+          ci[a * C + b] = v;
+          ci[b * C + a] = v;
+        }
+      }
+    }
+  }
+}
+
+constexpr int kFpWaves = 4, kFpNT = 64 * kFpWaves;    // fb_pow_kernel: four waves stage, up to four own a band
+constexpr int kFpRows = 512;                          // staged rows (trials x channels padded to 16) per workgroup
+constexpr int kFpPre = kFpRows * kL / kFpNT;          // staged elements per thread and chunk
+
+// G trials per workgroup (G m <= 64, G CP <= kFpRows with CP = C rounded up to 16), BW <= 4 bands
+template <typename VT>
+__global__ __launch_bounds__(kFpNT) void fb_pow_kernel(
+    const FbSec* __restrict__ secs, const SerSec* __restrict__ sers, const FbBand* __restrict__ bands,
+    const int* __restrict__ map, int nb, int ns, int nb_out, const float* __restrict__ x, const float* __restrict__ w,
+    float* __restrict__ out, int64_t n, int C, int T, int m, int G, int BW, int take_log) {
+  constexpr int LD = kFcLD;
+  extern __shared__ __attribute__((aligned(16))) unsigned char fp_smem[];
+  double* st_all = reinterpret_cast<double*>(fp_smem);                   // [kFpWaves][ns][2][64]
+  float* zt_all = reinterpret_cast<float*>(st_all + kFpWaves * ns * kFcStateDoubles);   // [kFpWaves][64][LD]
+  float* xs = zt_all + kFpWaves * 64 * LD;                               // [G][CP][LD], rows C .. CP - 1 zeros
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int CP = (C + 15) & ~15, GR = G * CP, nkg = CP >> 4;
+  const int groups = (nb + BW - 1) / BW;
+  const int64_t trial0 = (int64_t)(blockIdx.x / groups) * G;
+  const int bi = (blockIdx.x % groups) * BW + wave;
+  const bool active = wave < BW && bi < nb;                              // wave-uniform
+  double* st = st_all + wave * ns * kFcStateDoubles;
+  float* zt = zt_all + wave * 64 * LD;                                   // the wave's projected rows, row = lane
+  const int g_l = lane / m, j_l = lane - g_l * m;
+  const bool lane_ok = g_l < G && trial0 + g_l < n;                      // the last lanes and the last group have no trial
+  const int64_t left = n - trial0;
+  const int Gn = left < G ? (int)left : G;                               // trials of this workgroup that exist
+  const float* xg = x + trial0 * C * T;
+  const int aj = lane & 15, ac = lane >> 4;                              // MFMA operand position
+
+  for (int e = 0; e < 2 * ns; ++e) st[e * 64 + lane] = 0.0;
+  const int band_out = map[active ? bi : 0];
+  const FbSec* bsec = secs + (active ? bi : 0) * ns;
+  const SerSec* bser = std::is_same<VT, float>::value ? sers + (active ? bi : 0) * ns : nullptr;
+  const FbBand band = bands[active ? bi : 0];
+  float wa[32];                                                          // A fragments: wa[ks] = w[band][aj][4 ks + ac]
+  {
+    const float* wb = w + (int64_t)band_out * m * C;
+#pragma unroll
+    for (int ks = 0; ks < 32; ++ks) {
+      const int c = 4 * ks + ac;
+      wa[ks] = (active && aj < m && c < C) ? wb[aj * C + c] : 0.f;
+    }
+  }
+
+  // staging: thread (rsub, k) owns sample k of the rows i * 8 + rsub; CP is a multiple of 8, so the trial of row
+  // block i is wave-uniform
+  const int rsub = tid >> 5, kk = tid & 31;
+  float pre[kFpPre];
+  auto fetch = [&](int t0) {
+    int g = 0, cb = 0;
+#pragma unroll
+    for (int i = 0; i < kFpPre; ++i) {
+      const int c = cb + rsub, t = t0 + kk;
+      // never past x; branch-free (loads behind a branch are waited for one by one) and not looked at before the
+      // store (a select here would wait for the load)
+      pre[i] = xg[(i * 8 < GR && g < Gn && c < C && t < T) ? ((int64_t)g * C + c) * T + t : 0];
+      const bool wrap = cb + 8 >= CP;
+      cb = wrap ? 0 : cb + 8;
+      g += wrap ? 1 : 0;
+    }
+  };
+  fetch(0);
+  float sq = 0.f;
+  for (int t0 = 0; t0 < T; t0 += kL) {
+    __syncthreads();                                                     // the previous chunk has been consumed
+    {
+      int g = 0, cb = 0;
+#pragma unroll
+      for (int i = 0; i < kFpPre; ++i) {
+        if (i * 8 < GR) xs[(i * 8 + rsub) * LD + kk] = (g < Gn && cb + rsub < C && t0 + kk < T) ? pre[i] : 0.f;
+        const bool wrap = cb + 8 >= CP;
+        cb = wrap ? 0 : cb + 8;
+        g += wrap ? 1 : 0;
+      }
+    }
+    __syncthreads();
+    if (t0 + kL < T) fetch(t0 + kL);
+    if (active) {
+      for (int g = 0; g < G; ++g) {                                      // z = W x of trial g: [16][32] in two tiles
+        const float* xb = xs + (g * CP + ac) * LD + aj;
+        f32x4 z0 = (f32x4)(0.f), z1 = (f32x4)(0.f);
+        float b0[32], b1[32];                                            // the trial's B fragments, all requested
+#pragma unroll
+        for (int kg = 0; kg < 8; ++kg) {                                 // before the first MFMA
+          if (kg < nkg) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+              const int ks = kg * 4 + u;
+              b0[ks] = xb[4 * ks * LD];
+              b1[ks] = xb[4 * ks * LD + 16];
+            }
+          }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int kg = 0; kg < 8; ++kg) {
+          if (kg < nkg) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+              const int ks = kg * 4 + u;
+              z0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[ks], b0[ks], z0, 0, 0, 0);
+              z1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[ks], b1[ks], z1, 0, 0, 0);
+            }
+          }
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int j = 4 * ac + r;
+          if (j < m) {
+            zt[(g * m + j) * LD + aj] = z0[r];
+            zt[(g * m + j) * LD + 16 + aj] = z1[r];
+          }
+        }
+      }
+      wave_lds_sync();
+      float io[kL];
+      float4 zv[kL / 4];                                                 // rows >= G m of zt are never written:
+#pragma unroll
+      for (int q = 0; q < kL / 4; ++q) zv[q] = *reinterpret_cast<const float4*>(zt + lane * LD + 4 * q);
+#pragma unroll
+      for (int q = 0; q < kL / 4; ++q) {                                 // their lanes filter zeros
+        io[4 * q] = g_l < G ? zv[q].x : 0.f; io[4 * q + 1] = g_l < G ? zv[q].y : 0.f;
+        io[4 * q + 2] = g_l < G ? zv[q].z : 0.f; io[4 * q + 3] = g_l < G ? zv[q].w : 0.f;
+      }
+      grad_cascade<VT>(io, bsec, bser, band, ns, st, lane);
+      float s = 0.f;
+#pragma unroll
+      for (int i = 0; i < kL; ++i) s = t0 + i < T ? fmaf(io[i], io[i], s) : s;     // the ringing past T is not summed
+      sq += s;
+      wave_lds_sync();                                                   // the rows are read before the next chunk's
+    }
+  }
+  if (active && lane_ok) {
+    const float v = sq / (float)T;
+    out[((trial0 + g_l) * nb_out + band_out) * m + j_l] = take_log ? logf(v) : v;
+  }
+}
+
+// bands of one workgroup: the split of nb bands into groups of 3 or 4 that leaves fewer idle waves
+static int fc_band_waves(int nb) {
+  if (nb <= 2) return 1;
+  const int w3 = (int)cdiv(nb, 3) * 3 - nb, w4 = (int)cdiv(nb, 4) * 4 - nb;
+  return w3 < w4 ? 3 : 4;
+}
+
+template <typename VT>
+static int fb_cov_launch(const FbSet& fs, int ns, int nb_out, const float* x, float* cov, int64_t n, int C, int T,
+                         hipStream_t st) {
+  const int NW = C > 64 ? 2 : 1, BW = NW == 2 ? 1 : fc_band_waves(fs.nb);
+  const int64_t blocks = n * cdiv(fs.nb, BW);
+  ISD_CHECK_ARG(blocks <= 0x7fffffffLL, "isd_fb_trial_cov: n=%lld trials of %d bands are too many for one launch",
+                (long long)n, fs.nb);
+  const size_t lds = sizeof(double) * BW * NW * ns * kFcStateDoubles + sizeof(float) * (1 + BW) * 64 * NW * kFcLD;
+  const dim3 grid((unsigned)blocks), block(64 * NW * BW);
+#define ISD_FC_COV(NW_, BW_)                                                                                        \
+  return launch_lds(fb_cov_kernel<VT, NW_, BW_>, grid, block, lds, st, fs.d_sec, fs.d_ser, fs.d_band, fs.d_map,     \
+                    fs.nb, ns, nb_out, x, cov, C, T)
+  if (NW == 2) ISD_FC_COV(2, 1);
+  if (BW == 1) ISD_FC_COV(1, 1);
+  if (BW == 3) ISD_FC_COV(1, 3);
+  ISD_FC_COV(1, 4);
+#undef ISD_FC_COV
+}
+
+template <typename VT>
+static int fb_pow_launch(const FbSet& fs, int ns, int nb_out, const float* x, const float* w, float* out, int64_t n,
+                         int C, int T, int m, int take_log, hipStream_t st) {
+  const int BW = fs.nb <= kFpWaves ? fs.nb : fc_band_waves(fs.nb);
+  const int CP = (C + 15) / 16 * 16;
+  int G = 64 / m;                                       // lanes of a wave
+  if (G > kFpRows / CP) G = kFpRows / CP;               // 72 KiB of staged rows at the most
+  const int64_t blocks = cdiv(n, G) * cdiv(fs.nb, BW);
+  ISD_CHECK_ARG(blocks <= 0x7fffffffLL, "isd_fb_csp_power: n=%lld trials of %d bands are too many for one launch",
+                (long long)n, fs.nb);
+  const size_t lds = sizeof(double) * kFpWaves * ns * kFcStateDoubles +
+                     sizeof(float) * ((size_t)kFpWaves * 64 + (size_t)G * CP) * kFcLD;
+  ISD_CHECK_ARG(lds <= kFcMaxLds, "isd_fb_csp_power: %zu bytes of LDS", lds);
+  return launch_lds(fb_pow_kernel<VT>, dim3((unsigned)blocks), dim3(kFpNT), lds, st, fs.d_sec, fs.d_ser, fs.d_band,
+                    fs.d_map, fs.nb, ns, nb_out, x, w, out, n, C, T, m, G, BW, take_log);
+}
+
+}  // namespace isd
+
+// The shape is checked before the pointers, so a bad shape is refused whatever else is passed.
+extern "C" int isd_fb_trial_cov(const isd_fb_plan* plan, const float* x, float* cov, int64_t n, int C, int T,
+                                void* stream) {
+  ISD_CHECK_ARG(n >= 0 && n <= 2147483647LL, "isd_fb_trial_cov: n=%lld", (long long)n);
+  ISD_CHECK_ARG(C >= 1 && C <= 128 && T >= 1 && T <= 0x7fffffff - kL,
+                "isd_fb_trial_cov: C=%d T=%d (need 1 <= C <= 128, T >= 1)", C, T);
+  ISD_CHECK_ARG(plan, "isd_fb_trial_cov: null plan");
+  ISD_CHECK_ARG(x && cov, "isd_fb_trial_cov: null argument");
+  if (n == 0) return ISD_OK;
+  for (int k = 0; k < 2; ++k) {
+    const FbSet& fs = plan->set[k];
+    if (!fs.nb) continue;
+    const int rc = k == 0 ? fb_cov_launch<float>(fs, plan->n_sections, plan->n_bands, x, cov, n, C, T, (hipStream_t)stream)
+                          : fb_cov_launch<double>(fs, plan->n_sections, plan->n_bands, x, cov, n, C, T, (hipStream_t)stream);
+    if (rc) return rc;
+  }
+  return ISD_OK;
+}
+
+extern "C" int isd_fb_csp_power(const isd_fb_plan* plan, const float* x, const float* w, float* out, int64_t n, int C,
+                                int T, int m, int take_log, void* stream) {
+  ISD_CHECK_ARG(n >= 0 && n <= 2147483647LL, "isd_fb_csp_power: n=%lld", (long long)n);
+  ISD_CHECK_ARG(C >= 1 && C <= 128 && T >= 1 && T <= 0x7fffffff - kL && m >= 1 && m <= 16,
+                "isd_fb_csp_power: C=%d T=%d m=%d (need 1 <= C <= 128, T >= 1, 1 <= m <= 16)", C, T, m);
+  ISD_CHECK_ARG(plan, "isd_fb_csp_power: null plan");
+  ISD_CHECK_ARG(x && w && out, "isd_fb_csp_power: null argument");
+  if (n == 0) return ISD_OK;
+  for (int k = 0; k < 2; ++k) {
+    const FbSet& fs = plan->set[k];
+    if (!fs.nb) continue;
+    const int rc = k == 0 ? fb_pow_launch<float>(fs, plan->n_sections, plan->n_bands, x, w, out, n, C, T, m, take_log,
+                                                 (hipStream_t)stream)
+                          : fb_pow_launch<double>(fs, plan->n_sections, plan->n_bands, x, w, out, n, C, T, m, take_log,
+                                                  (hipStream_t)stream);
+    if (rc) return rc;
+  }
+  return ISD_OK;
+}

@@ -218,6 +218,24 @@ int isd_csp_power_f64(const double* x, const double* w, double* out, int64_t n, 
                       void* stream);
 
 /* ------------------------------------------------------------------------
+ * Filter-bank CSP (Ang et al. 2008; isd_amd.FBCSP): the two steps above for every band of a filterbank plan, without
+ * the filtered [n][n_bands][C][T] map in memory.  Any plan of isd_fb_plan_create is taken (<= 8 sections, F32 / F64 /
+ * AUTO, mixed sets); bands come out in the caller's order.  All pointers are device memory; no call synchronises with
+ * the host; n == 0 returns 0 without a launch; 1 <= C <= 128, T >= 1.  A trial's result depends on the plan, C, T and
+ * m only, never on n or on its position in the batch, and is the same bits on every call.
+ *
+ * fb_trial_cov: x [n][C][T] f32 -> cov [n][n_bands][C][C] f32,
+ *               cov[i][b] = Y Y^T / T with Y = gain_b * cascade_b(x_i): causal, zero initial state, samples 0 .. T-1
+ *               only.  No mean removal.  [a][c] and [c][a] are the same bits.
+ * fb_csp_power: w [n_bands][m][C] f32 (1 <= m <= 16) -> out [n][n_bands][m] f32,
+ *               out[i][b][j] = mean_{t<T} (gain_b * cascade_b(sum_c w[b][j][c] x_i[c][.]))[t]^2, its natural log when
+ *               take_log != 0.  The projection is formed first, then filtered; the sum over T has a fixed order.
+ * ---------------------------------------------------------------------- */
+int isd_fb_trial_cov(const isd_fb_plan* plan, const float* x, float* cov, int64_t n, int C, int T, void* stream);
+int isd_fb_csp_power(const isd_fb_plan* plan, const float* x, const float* w, float* out, int64_t n, int C, int T,
+                     int m, int take_log, void* stream);
+
+/* ------------------------------------------------------------------------
  * Independent component analysis: the data-sized steps of parallel FastICA with the logcosh contrast (alpha = 1), the
  * default method of the reference's artifact removal
  *   ICA(n_components, method='fastica').fit(epochs); ica.apply(epochs)   scripts/artifact_analysis.py:61
