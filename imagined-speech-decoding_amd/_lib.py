@@ -75,6 +75,8 @@ SIGNATURES = {
     "isd_ica_step_f64": (_i, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i, _i, _i, _p]),
     "isd_spatial_apply_f32": (_i, [_p, _p, _p, _p, _i64, _i, _i, _i, _p]),
     "isd_spatial_apply_f64": (_i, [_p, _p, _p, _p, _i64, _i, _i, _i, _p]),
+    "isd_spd_congruence": (_i, [_p, _i, _p, _p, _p, _i64, _i, _i, _p]),
+    "isd_spd_eigfun": (_i, [_p, _p, _p, _p, _i64, _i, _i, _i, _p]),
     "isd_psd_plan_create": (_i, [C.POINTER(_p), _i, _i, _i, _i, _i, _pd, C.c_double, _i]),
     "isd_psd_plan_destroy": (_i, [_p]),
     "isd_psd_plan_bins": (_i, [_p]),

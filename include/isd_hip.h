@@ -263,6 +263,44 @@ int isd_spatial_apply_f64(const double* x, const double* M, const double* bias, 
                           int R, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Riemannian geometry of covariance matrices (isd_amd.riemann: Covariances -> TangentSpace -> a linear classifier, and
+ * MDM, Barachant et al. 2012; pyriemann is not vendored in the reference, the published method is restated): matrix
+ * functions of n small symmetric positive-definite matrices behind isd_trial_cov_*.  All arithmetic is fp64.  The
+ * square roots, exp and step control of the [K][C][C] class means are host work: isd_amd.riemann.mean_riemann.
+ * All pointers are device memory; no call synchronises with the host, takes a workspace or uses atomics; n == 0 returns
+ * 0 without a launch; 1 <= C <= 128, beyond that ISD_ERR_UNSUPPORTED.  A matrix's result depends on that matrix (and
+ * its W) alone, never on n, its position or an earlier launch, and is the same bits on every call.
+ *
+ * spd_congruence: cov [n][C][C] (fp64 when cov_f64 != 0, else fp32: what isd_trial_cov_* leave), W [K][C][C] double,
+ *                 widx [n] int32 in [0, K) or NULL (then W[0] for all) -> out [n][C][C] double,
+ *                 out_i = W_k cov_i W_k^T with k = widx[i].  Only the upper triangle of the second product is formed
+ *                 (as if cov_i were symmetric); out[i][a][b] and out[i][b][a] are the same bits.  A matrix whose
+ *                 widx lies outside [0, K) comes out NaN.  out must not be cov or W.
+ * spd_eigfun:     a [n][C][C] double, symmetric positive (semi-)definite -> with A = V L V^T:  f(A) = V f(L) V^T,
+ *                 f = log, sqrt, 1/sqrt, 1/x or x for fn = ISD_SPD_LOG .. ISD_SPD_NONE.
+ *                 out_kind ISD_SPD_FULL:    out [n][C][C], [a][b] and [b][a] the same bits;
+ *                          ISD_SPD_TANGENT: out [n][C(C+1)/2], the upper triangle row by row (np.triu_indices(C)
+ *                                           order) with the off-diagonal entries times sqrt 2, whose Euclidean norm
+ *                                           is the Frobenius norm of f(A);
+ *                          ISD_SPD_NOOUT:   nothing, out may be NULL.
+ *                 eigvals [n][C] or NULL: the eigenvalues in no promised order.
+ *                 info [n] int32 or NULL: the number of Jacobi sweeps used (> 0);  -1 if the cap of 30 sweeps was
+ *                 reached (out then holds the unconverged result);  -2 if an eigenvalue is not finite, the matrix is
+ *                 indefinite, or fn is log, 1/sqrt or 1/x and an eigenvalue is <= 0: that matrix's out is then NaN.
+ *                 One-sided Jacobi on A itself: like LAPACK's eigh it resolves an eigenvalue to about
+ *                 eps * l_max absolute, so log and the inverses of a matrix of condition k carry about eps * k.
+ *                 Only the magnitudes of the eigenvalues survive the iteration; a negative one is detected through
+ *                 trace(A) < sum |l_j| (1 - 64 C eps), so one below that share of the trace is taken by magnitude.
+ *                 out must not be a.
+ * ---------------------------------------------------------------------- */
+enum { ISD_SPD_LOG = 0, ISD_SPD_SQRT = 1, ISD_SPD_INVSQRT = 2, ISD_SPD_INV = 3, ISD_SPD_NONE = 4 };
+enum { ISD_SPD_FULL = 0, ISD_SPD_TANGENT = 1, ISD_SPD_NOOUT = 2 };
+int isd_spd_congruence(const void* cov, int cov_f64, const double* W, const int32_t* widx, double* out, int64_t n,
+                       int C, int K, void* stream);
+int isd_spd_eigfun(const double* a, double* out, double* eigvals, int32_t* info, int64_t n, int C, int fn,
+                   int out_kind, void* stream);
+
+/* ------------------------------------------------------------------------
  * Welch power spectral density: the data-sized step of
  *   raw.compute_psd(method='welch') -> mne.time_frequency.psd_array_welch   scripts/artifact_analysis.py:45
  * as scipy.signal.welch / spectrogram(scaling='density') compute it.  Segment s of a row is samples
