@@ -332,6 +332,49 @@ int isd_psd_welch_f64(const isd_psd_plan* plan, const double* x, double* out, in
                       void* work, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Complex FIR bank with decimation: the data-sized step of a time-frequency transform
+ * (isd_amd.tfr_array_morlet, the counterpart of mne.time_frequency.tfr_array_morlet; isd_amd.tfr.cwt).  The library
+ * knows nothing about wavelets: the plan takes n_freqs complex tap vectors of odd lengths and
+ *   z[row][f][t] = sum_k w_f[k] x[row][t decim + h_f - k],   h_f = (n_taps[f] - 1) / 2,   x zero outside [0, T),
+ * which is np.convolve(x[row], w_f, 'same')[::decim]; T_out = ceil(T / decim) (isd_tfr_plan_out_len).  Only kept
+ * samples are computed.  The product runs on the fp32 / fp64 matrix cores with eight frequencies x (re, im) side by
+ * side, the taps of a group of eight (sorted by length) centred and zero-padded to the longest: useful and padded
+ * tap counts differ by isd_tfr_plan_padded_taps / sum(n_taps).
+ *
+ * x [n][C][T] -> out by `mode`:
+ *   0  complex    [n][C][F][T_out][2]  (re, im)
+ *   1  power      [n][C][F][T_out]     re^2 + im^2
+ *   2  avg_power  [C][F][T_out]        mean over the n trials of the power
+ *   3  itc        [C][F][T_out]        | mean over trials of z / |z| |; a sample with |z| = 0 contributes 0
+ *   4  both       [C][F][T_out][2]     (avg_power, itc), the same bits as modes 2 and 3
+ *   5  phase      [n][C][F][T_out]     atan2(im, re), taken in fp64
+ * The _f32 entry multiplies and accumulates in fp32, the _f64 entry in fp64, out has x's type; the exceptions are the
+ * phase and the coherence of the _f32 entry (modes 5, 3 and the second half of mode 4), whose product runs in fp64
+ * over the widened samples, because the phase of a weak sample does not survive fp32 (mode 4 then costs modes
+ * 2 + 3).  Modes 2-4 write
+ * nothing per trial: the owner of an output element walks the trials in index order, sums in fp64 in both entries and
+ * stores once.  No atomics: every mode is bitwise repeatable.  Each row's mean (fp64, a pre-pass into `work`) is taken
+ * off before the product and its share, mean x the sum of the taps that met the row, is added back in fp64: the
+ * result is the same and an offset of the data costs no precision.  `work`: isd_tfr_work_bytes bytes of scratch (the
+ * n C means).  x needs element alignment only; out the alignment of its element, which for modes 0 and 4 is the (re, im)
+ * pair.  All data pointers are device memory; taps and n_taps are host memory; no call synchronises with the host.
+ * Envelope: 1 <= n_freqs <= 256, odd 1 <= n_taps <= 4095, 1 <= decim <= 128, finite taps, any n, C, T >= 0 with
+ * n, C < 2^31 (an empty array returns at once, but n = 0 with modes 2-4 is ISD_ERR_INVALID), at most 2^31 - 1
+ * (row, time tile) pairs; outside it ISD_ERR_UNSUPPORTED with the reason in isd_last_error().
+ * ---------------------------------------------------------------------- */
+typedef struct isd_tfr_plan isd_tfr_plan;
+int isd_tfr_plan_create(isd_tfr_plan** out, int n_freqs, const int* n_taps /* host [F], odd */,
+                        const double* taps /* host, (re, im) pairs, sum(n_taps) of them */, int decim);
+int isd_tfr_plan_destroy(isd_tfr_plan* plan);
+int64_t isd_tfr_plan_out_len(const isd_tfr_plan* plan, int64_t T);   /* ceil(T / decim) */
+int64_t isd_tfr_plan_padded_taps(const isd_tfr_plan* plan);          /* taps multiplied per output column, zeros included */
+int64_t isd_tfr_work_bytes(const isd_tfr_plan* plan, int64_t n, int64_t C, int64_t T, int mode, int is_f64);
+int isd_tfr_cwt_f32(const isd_tfr_plan* plan, const float* x, void* out, int64_t n, int64_t C, int64_t T, int mode,
+                    void* work, void* stream);
+int isd_tfr_cwt_f64(const isd_tfr_plan* plan, const double* x, void* out, int64_t n, int64_t C, int64_t T, int mode,
+                    void* work, void* stream);
+
+/* ------------------------------------------------------------------------
  * Zone-wise Conv4Layers stack over sliding windows: the reference's
  *   FAST.forward_head   src/fast/models/fast.py:242-252  (unfold window_len / slide_step)
  *   Head.forward        src/fast/models/fast.py:209-210  (zone gather, one encoder per zone, stack)
