@@ -122,6 +122,7 @@ SIGNATURES = {
     "isd_eegnet_plan_create": (_i, [C.POINTER(_p), _i, _i, _i, _i]),
     "isd_featcnn_supported": (_i, [_p, _i64, _i64, _i]),
     "isd_first_layer_last_path": (_i, []),
+    "isd_first_wgrad_last_stage_loop": (_i, []),
     "isd_featcnn_step": (_i, [_p, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _i64, _i64, _i, _f, _p]),
     "isd_featcnn_step_bf16": (_i, [_p, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _i64, _i64, _i, _f, _p]),
     "isd_paperhead_plan_create": (_i, [C.POINTER(_p), _i, _i, _i]),

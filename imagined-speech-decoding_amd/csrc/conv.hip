@@ -3153,8 +3153,39 @@ __host__ __device__ constexpr Conv5WgradWideLds conv5_wgrad_wide_layout(int IPS,
   l.end = c.end;
   return l;
 }
-template <int GT>
+// The instances with a compile-time stage (TOUT > 0: Tout == TOUT, IPS == kWgradStageIps, LDS-DMA staging by glds_run;
+// first_layer_backward checks) run a full stage as straight-line code.  Lane q's K index at step s is 4 s + q, so its
+// byte offset within the buffer is 16 s + 4 (item_len - TOUT) * ((4 s + q) / TOUT): 16 s goes into the ds_read
+// immediates and the item term grows, by one item, in the lanes of conv5_wgrad_stage_cross(TOUT, s) at step s.
+constexpr int kWgradStageIps = 4;
+__host__ __device__ constexpr unsigned conv5_wgrad_stage_cross(int tout, int s) {   // bit q: lane group q enters a new item
+  unsigned m = 0;
+  for (int q = 0; q < 4; ++q)
+    if (s > 0 && (4 * s + q) / tout != (4 * (s - 1) + q) / tout) m |= 1u << q;
+  return m;
+}
+// (the crossings up to step s add up to the item of K index 4 s + q, and the last K index is in the stage's last item)
+__host__ __device__ constexpr bool conv5_wgrad_stage_cross_ok(int tout) {
+  const int ns = kWgradStageIps * tout / 4;
+  for (int q = 0; q < 4; ++q) {
+    int item = 0;
+    for (int s = 0; s < ns; ++s) {
+      item += (conv5_wgrad_stage_cross(tout, s) >> q) & 1;
+      if (item != (4 * s + q) / tout) return false;
+    }
+    if (q == 3 && item != kWgradStageIps - 1) return false;
+  }
+  return true;
+}
+static_assert(conv5_wgrad_stage_cross_ok(13) && conv5_wgrad_stage_cross_ok(4) && conv5_wgrad_stage_cross_ok(7),
+              "conv5_wgrad_stage_cross: item crossings of a full stage");
+template <class Fn, int... S>
+__device__ __forceinline__ void static_steps(Fn&& fn, std::integer_sequence<int, S...>) {
+  (fn(std::integral_constant<int, S>{}), ...);
+}
+template <int GT, int TOUT = 0>
 __global__ __launch_bounds__(256) void conv5_wgrad_wide_kernel(WgradArgs a) {
+  static_assert(TOUT == 0 || (TOUT >= 4 && (kWgradStageIps * TOUT) % 4 == 0), "a full stage is a whole number of K steps");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int z = blockIdx.y;
   const ZoneDesc zd = a.zones[z];
@@ -3237,6 +3268,30 @@ __global__ __launch_bounds__(256) void conv5_wgrad_wide_kernel(WgradArgs a) {
   };
   constexpr int kSetReads = GT + 3;
   const unsigned zero_addr = smem_base + (unsigned)L.zero * 4;
+  // wait until at most `behind` LDS reads are outstanding, then take the set (its registers pass through the statement)
+  auto take = [&](FragSet& f, auto behind) {
+    if constexpr (GT == 2)
+      asm volatile("s_waitcnt lgkmcnt(%5)" : "+v"(f.af[0]), "+v"(f.af[GT - 1]), "+v"(f.b01), "+v"(f.b23), "+v"(f.b4)
+                   : "i"(decltype(behind)::value) : "memory");
+    else
+      asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(f.af[0]), "+v"(f.b01), "+v"(f.b23), "+v"(f.b4)
+                   : "i"(decltype(behind)::value) : "memory");
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  auto mma_set = [&](auto bias, const FragSet& f) {
+    const float bf[kTaps] = {f.b01[0], f.b01[1], f.b23[0], f.b23[1], f.b4};
+#pragma unroll
+    for (int k = 0; k < kTaps; ++k)
+#pragma unroll
+      for (int g = 0; g < GT; ++g) acc[g][k] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.af[g], bf[k], acc[g][k], 0, 0, 0);
+    if constexpr (decltype(bias)::value) {
+#pragma unroll
+      for (int g = 0; g < GT; ++g) accb[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.af[g], 1.f, accb[g], 0, 0, 0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  const std::integral_constant<int, kSetReads> one_set;
+  const std::integral_constant<int, 0> none;
   auto run_packed = [&](auto bias, int sbuf, int n_it) {
     const unsigned buf_addr = smem_base + (unsigned)(sbuf * buf_len) * 4;
     unsigned a0 = buf_addr + (unsigned)a_off * 4, a1 = a0 + (unsigned)(16 * a.Tout) * 4, b = buf_addr + (unsigned)b_off * 4;
@@ -3263,52 +3318,80 @@ __global__ __launch_bounds__(256) void conv5_wgrad_wide_kernel(WgradArgs a) {
       a0 += d; a1 += d; b += d;
       if (w) { p_t -= a.Tout; ++p_ii; }
     };
-    // wait until at most `behind` LDS reads are outstanding, then take the set (its registers pass through the statement)
-    auto take = [&](FragSet& f, auto behind) {
-      if constexpr (GT == 2)
-        asm volatile("s_waitcnt lgkmcnt(%5)" : "+v"(f.af[0]), "+v"(f.af[GT - 1]), "+v"(f.b01), "+v"(f.b23), "+v"(f.b4)
-                     : "i"(decltype(behind)::value) : "memory");
-      else
-        asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(f.af[0]), "+v"(f.b01), "+v"(f.b23), "+v"(f.b4)
-                     : "i"(decltype(behind)::value) : "memory");
-      __builtin_amdgcn_sched_barrier(0);
-    };
-    auto mma_set = [&](const FragSet& f) {
-      const float bf[kTaps] = {f.b01[0], f.b01[1], f.b23[0], f.b23[1], f.b4};
-#pragma unroll
-      for (int k = 0; k < kTaps; ++k)
-#pragma unroll
-        for (int g = 0; g < GT; ++g) acc[g][k] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.af[g], bf[k], acc[g][k], 0, 0, 0);
-      if constexpr (decltype(bias)::value) {
-#pragma unroll
-        for (int g = 0; g < GT; ++g) accb[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.af[g], 1.f, accb[g], 0, 0, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    };
     const int n_step = (n_it * a.Tout + 3) >> 2;
-    const std::integral_constant<int, kSetReads> one_set;
-    const std::integral_constant<int, 0> none;
     FragSet f0, f1;
     issue(f0);
     int st = 1;
     for (; st + 1 < n_step; st += 2) {                                 // f0 holds step st - 1; steps st and st + 1 exist
       issue(f1);
       take(f0, one_set);
-      mma_set(f0);
+      mma_set(bias, f0);
       issue(f0);
       take(f1, one_set);
-      mma_set(f1);
+      mma_set(bias, f1);
     }
     if (st < n_step) {                                                 // two steps left
       issue(f1);
       take(f0, one_set);
-      mma_set(f0);
+      mma_set(bias, f0);
       take(f1, none);
-      mma_set(f1);
+      mma_set(bias, f1);
     } else {                                                           // the odd last step
       take(f0, none);
-      mma_set(f0);
+      mma_set(bias, f0);
     }
+  };
+  // A full stage of a compile-time-stage instance: kWgradStageIps * TOUT / 4 K steps as straight-line code.  Same reads,
+  // waits and MFMAs in the same order as run_packed with n_it == IPS (no lane of a full stage is past the last pair);
+  // the two addresses (the second filter tile is 64 TOUT bytes behind the first: an immediate, too) are rebuilt per
+  // stage and move only where lanes enter a new item, behind the MFMAs of the step two before.
+  auto run_full = [&](auto bias, int sbuf) {
+    constexpr int T = TOUT > 0 ? TOUT : 4;
+    constexpr int NS = kWgradStageIps * T / 4;
+    const unsigned buf_addr = smem_base + (unsigned)(sbuf * buf_len) * 4;
+    unsigned pa = buf_addr + (unsigned)a_off * 4, pb = buf_addr + (unsigned)b_off * 4;
+    const unsigned item_skip = (unsigned)(item_len - T) * 4;
+    auto issue = [](FragSet& f, unsigned pa, unsigned pb, auto sc) {    // (addresses by value: a generic lambda's asm operands)
+      constexpr int S = decltype(sc)::value;
+      if constexpr (GT == 2)
+        asm volatile("ds_read_b32 %0, %5 offset:%7\n\tds_read_b32 %1, %5 offset:%8\n\t"
+                     "ds_read2_b32 %2, %6 offset0:%9 offset1:%10\n\tds_read2_b32 %3, %6 offset0:%11 offset1:%12\n\t"
+                     "ds_read_b32 %4, %6 offset:%13"
+                     : "=&v"(f.af[0]), "=&v"(f.af[GT - 1]), "=&v"(f.b01), "=&v"(f.b23), "=&v"(f.b4)
+                     : "v"(pa), "v"(pb), "i"(16 * S), "i"(16 * S + 64 * T), "i"(4 * S), "i"(4 * S + 1), "i"(4 * S + 2),
+                       "i"(4 * S + 3), "i"(16 * S + 16)
+                     : "memory");
+      else
+        asm volatile("ds_read_b32 %0, %4 offset:%6\n\tds_read2_b32 %1, %5 offset0:%7 offset1:%8\n\t"
+                     "ds_read2_b32 %2, %5 offset0:%9 offset1:%10\n\tds_read_b32 %3, %5 offset:%11"
+                     : "=&v"(f.af[0]), "=&v"(f.b01), "=&v"(f.b23), "=&v"(f.b4)
+                     : "v"(pa), "v"(pb), "i"(16 * S), "i"(4 * S), "i"(4 * S + 1), "i"(4 * S + 2), "i"(4 * S + 3),
+                       "i"(16 * S + 16)
+                     : "memory");
+    };
+    auto cross = [&](auto sc) {                                          // the lanes that step S takes into the next item
+      constexpr unsigned M = conv5_wgrad_stage_cross(T, decltype(sc)::value);
+      if constexpr (M != 0) {
+        const unsigned d = M == 15u ? item_skip : ((M >> q) & 1u) ? item_skip : 0u;
+        pa += d; pb += d;
+      }
+    };
+    FragSet f0, f1;
+    issue(f0, pa, pb, std::integral_constant<int, 0>{});
+    cross(std::integral_constant<int, 1>{});
+    static_steps([&](auto sc) {
+      constexpr int S = decltype(sc)::value;
+      FragSet& cur = (S & 1) ? f1 : f0;
+      FragSet& nxt = (S & 1) ? f0 : f1;
+      if constexpr (S + 1 < NS) {
+        issue(nxt, pa, pb, std::integral_constant<int, S + 1>{});
+        take(cur, one_set);
+      } else {
+        take(cur, none);
+      }
+      mma_set(bias, cur);
+      if constexpr (S + 2 < NS) cross(std::integral_constant<int, S + 2>{});
+    }, std::make_integer_sequence<int, NS>{});
   };
   // Tout < 4: one K step per item, masked after the load (plain C++ loads, the compiler's schedule)
   auto run_single = [&](int sbuf, int n_it) {
@@ -3360,17 +3443,33 @@ __global__ __launch_bounds__(256) void conv5_wgrad_wide_kernel(WgradArgs a) {
       else stage(is, sb);
     };
     if (i_lo < i_hi) stage_any(i_lo, 0);
-    for (int64_t is = i_lo; is < i_hi; is += a.IPS, s ^= 1) {
+    auto arrive = [&](int64_t is) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                 // (stage_fast's DMA is not the compiler's to wait for)
       __syncthreads();                                                 // DMA of this stage retired; previous stage consumed
       if (is + a.IPS < i_hi) stage_any(is + a.IPS, s ^ 1);
+    };
+    constexpr int M = decltype(mode)::value;
+    const std::integral_constant<bool, M == 2> bias;
+    // compile-time stages: the loop holds full stages only, the ragged last stage of the range follows it (the
+    // accumulators then meet one body per loop and stay in one register set)
+    constexpr bool split = TOUT > 0 && (M == 1 || M == 2);
+    int64_t is = i_lo;
+    for (; split ? is + a.IPS <= i_hi : is < i_hi; is += a.IPS, s ^= 1) {
+      arrive(is);
       const int n_it = (int)((i_hi - is) < a.IPS ? (i_hi - is) : a.IPS);
-      if constexpr (decltype(mode)::value == 0) run_single(s, n_it);
-      else if constexpr (decltype(mode)::value != 3) run_packed(std::integral_constant<bool, decltype(mode)::value == 2>{}, s, n_it);
+      if constexpr (M == 0) run_single(s, n_it);
+      else if constexpr (split) run_full(bias, s);
+      else if constexpr (M != 3) run_packed(bias, s, n_it);
+    }
+    if constexpr (split) {
+      if (is < i_hi) {
+        arrive(is);
+        run_packed(bias, s, (int)(i_hi - is));
+      }
     }
   };
   if (!wave_live) run_stages(std::integral_constant<int, 3>{});
-  else if (a.Tout < 4) run_stages(std::integral_constant<int, 0>{});
+  else if (TOUT == 0 && a.Tout < 4) run_stages(std::integral_constant<int, 0>{});
   else if (!with_bias) run_stages(std::integral_constant<int, 1>{});
   else run_stages(std::integral_constant<int, 2>{});
   if (!wave_live) return;
@@ -4232,6 +4331,10 @@ static bool bf16_mfma_ok(const isd_conv4_plan* p, const Geo& g, const void* x) {
 // 1 conv5_wgrad_wide_kernel, 2 conv5_wgrad_wide_bf16_kernel (the fused backward kernels leave it as it was).
 static thread_local int g_first_fwd_path = 0, g_first_wgrad_path = 0;
 extern "C" int isd_first_layer_last_path(void) { return g_first_fwd_path + 16 * g_first_wgrad_path; }
+// The stage loop of the calling thread's last conv5_wgrad_wide_kernel launch: 0 the generic loop (instances <GT>),
+// 1 full stages as compile-time code (instances <GT, 13>).
+static thread_local int g_first_wgrad_stage_loop = 0;
+extern "C" int isd_first_wgrad_last_stage_loop(void) { return g_first_wgrad_stage_loop; }
 
 // cnn1 o cnn2 forward into the A2 buffer; `a` comes back filled with the shared fields for the later layers
 static int first_layer_forward(const isd_conv4_plan* p, const Geo& g, const float* x, int64_t T, float* ws,
@@ -4429,9 +4532,16 @@ static int first_layer_backward(const isd_conv4_plan* p, const Geo& g, const flo
   } else if (g.lin0 && p->dma_ok && !p->act_bf16 && p->max_cz >= 64 && (F * g.T1) % 4 == 0 && lds <= kLdsStage64K &&
              ((uintptr_t)x & 15) == 0 && ((uintptr_t)g2 & 15) == 0) {
     w.items_per_wg = ipw; w.IPS = ips;
-    rc = launch_lds(F == 32 ? conv5_wgrad_wide_kernel<2> : conv5_wgrad_wide_kernel<1>, grid, dim3(256), lds, st, w);
+    // 13 output steps, four items a stage and the kernel's straight-line staging (glds_run: at most kGldsRunMax4 pieces
+    // of gradient and of input rows per item): the instances whose full stages are compile-time code
+    const bool stage13 = g.T1 == 13 && ips == kWgradStageIps && (F * g.T1) / 4 <= kGldsRunMax4 && in_len / 4 <= kGldsRunMax4;
+    void (*k)(WgradArgs);
+    if (stage13) k = F == 32 ? conv5_wgrad_wide_kernel<2, 13> : conv5_wgrad_wide_kernel<1, 13>;
+    else k = F == 32 ? conv5_wgrad_wide_kernel<2> : conv5_wgrad_wide_kernel<1>;
+    rc = launch_lds(k, grid, dim3(256), lds, st, w);
     n_slabs0 = R;
     g_first_wgrad_path = 1;
+    g_first_wgrad_stage_loop = stage13 ? 1 : 0;
   } else {
     g_first_wgrad_path = 0;
     rc = launch_wgrad(0, p->act_bf16, w, p->Z, p->max_cz + 1, st);

@@ -600,6 +600,9 @@ int isd_featcnn_supported(const isd_conv4_plan* plan, int64_t B, int64_t T, int 
  * weight-gradient code as it was).  Weight gradient: 0 general, 1 wide fp32, 2 wide bf16.  For tests: a fall-back to
  * another kernel must not pass for the intended one. */
 int isd_first_layer_last_path(void);
+/* The stage loop of the calling thread's last wide fp32 weight gradient (code 1 above): 0 the generic loop, 1 the
+ * instance that runs full stages of four 13-step items as straight-line code.  Both compute the same bits. */
+int isd_first_wgrad_last_stage_loop(void);
 int isd_featcnn_step(const isd_conv4_plan* plan, const float* x, const float* params, const float* fc_w,
                      const float* fc_b, const void* labels, int label_bytes, float* dparams, float* dfc,
                      float* logits, int64_t* pred, float* loss, void* workspace, int64_t B, int64_t T, int n_cls,
