@@ -1,0 +1,250 @@
+"""Cross-spectral density and spectral connectivity on the GPU: the frequency-resolved cross-channel estimates next to
+``psd_array_welch`` (one channel, per frequency) and the trial covariances of ``CSP`` / ``riemann`` (all channels,
+broadband).
+
+``csd_array_welch(x, sfreq, ...)`` -> ``(csd, freqs)``: x [n, C, T] (or [C, T]) -> the Welch cross-spectral density
+``S[i, j] = mean X_i conj(X_j)`` over the bins with ``fmin <= f <= fmax``, complex, [n, K, C, C] for
+``average='segments'`` (the mean over a trial's segments) or [K, C, C] for ``average='trials'`` (over every segment of
+every trial).  In scipy's terms ``S[i, j]`` is ``scipy.signal.csd(x_j, x_i, window=..., nperseg=..., noverlap=...,
+nfft=..., detrend='constant', scaling='density')`` -- scipy conjugates its first argument -- and the diagonal is
+``psd_array_welch`` with the same window.
+
+``spectral_connectivity(x, sfreq, method=...)`` -> ``(con, freqs)`` derives from it
+
+    'cohy'  = S_ij / sqrt(S_ii S_jj)        'coh' = |cohy|        'imcoh' = Im cohy
+
+and from a second pass in which every segment spectrum is first divided by its modulus, E = mean u_i conj(u_j) over
+the N (trial, segment) pairs averaged,
+
+    'plv' = |E|        'ciplv' = |Im E| / sqrt(1 - (Re E)^2)        'ppc' = (N |E|^2 - 1) / (N - 1).
+
+The names and formulas follow the documentation of mne-connectivity (``spectral_connectivity_epochs``); that library is
+not installed here and **parity with it is unpinned**: the tests pin the formulas above against a NumPy restatement and
+scipy (``scipy.signal.csd`` / ``coherence``).  Measures that are not Hermitian products of segment spectra ('pli',
+'dpli', 'wpli', 'wpli2_debiased'), multitaper and wavelet modes and ``indices=`` are not provided and raise
+NotImplementedError by name.
+
+The segment bookkeeping, the window and the argument checks are ``psd.welch_design``; the data-sized work runs in
+libisd_hip.so (csrc/csd.hip: segment spectra as a dense product on the plan's tables, then a Hermitian product per
+bin); the step from the density to a measure is elementwise torch ops on the device.  A call that asks for 'ciplv'
+runs its unit-modulus pass in fp64 for float32 input too.  There is no CPU fallback.
+ndarray in -> computed in fp64 on the GPU -> float64 / complex128 ndarray out; float32 / float64 CUDA tensor in ->
+CUDA tensor of the matching real or complex dtype out.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+from .constants import BANDS_5, band_edges
+from .psd import MAX_N_FFT, _cached_design, _cached_plan
+
+MAX_CHANNELS = 128                   # isd_csd_welch_*: 1 <= C <= 128
+CSD_CHUNK_BYTES = None               # bound on the spectra workspace of one trial chunk inside the library call
+#                                      (None: the library's 256 MiB)
+CON_CHUNK_BYTES = 256 << 20          # spectral_connectivity(average='segments'): bound on one [chunk, K, C, C] density
+
+DENSITY_METHODS = ("coh", "cohy", "imcoh")
+PHASE_METHODS = ("plv", "ciplv", "ppc")
+METHODS = DENSITY_METHODS + PHASE_METHODS
+NOT_PROVIDED = ("pli", "dpli", "wpli", "wpli2_debiased", "pli2_unbiased", "gc", "gc_tr", "mic", "mim", "cacoh")
+
+
+def _check_input(x):
+    """-> (x as [n, C, T], is_tensor, squeeze): every check that needs no GPU."""
+    is_tensor = isinstance(x, torch.Tensor)
+    if is_tensor:
+        if not x.is_cuda:
+            raise TypeError("tensor input must live on the GPU (there is no CPU fallback)")
+        if x.dtype not in (torch.float32, torch.float64):
+            raise TypeError("x must be float32 or float64")
+    else:
+        x = np.asarray(x)
+        if x.dtype.kind != "f":
+            raise TypeError("x must be floating point")
+    if x.ndim not in (2, 3):
+        raise ValueError(f"x must be [n, C, T] or [C, T], got {tuple(x.shape)}")
+    squeeze = x.ndim == 2
+    if squeeze:
+        x = x[None]
+    if not 1 <= x.shape[1] <= MAX_CHANNELS:
+        raise NotImplementedError(f"{x.shape[1]} channels: 1 to {MAX_CHANNELS} are provided")
+    return x, is_tensor, squeeze
+
+
+def _design(T, sfreq, fmin, fmax, n_fft, n_overlap, n_per_seg, window):
+    if isinstance(window, str):
+        d = _cached_design(float(sfreq), T, float(fmin), float(fmax), int(n_fft), int(n_overlap), n_per_seg, window,
+                           None)
+    else:
+        taps = np.ascontiguousarray(window, dtype=np.float64)
+        d = _cached_design(float(sfreq), T, float(fmin), float(fmax), int(n_fft), int(n_overlap), n_per_seg,
+                           taps.shape, taps.tobytes())
+    if d.n_fft > MAX_N_FFT:
+        raise NotImplementedError(f"n_fft={d.n_fft}: at most {MAX_N_FFT} is provided")
+    return d
+
+
+def _to_device(x, is_tensor):
+    if is_tensor:
+        return x.contiguous()
+    if not torch.cuda.is_available():
+        raise RuntimeError("isd_amd.connectivity needs an MI355X GPU: there is no CPU fallback")
+    arr = np.ascontiguousarray(x, dtype=np.float64)
+    return torch.from_numpy(arr if arr.flags.writeable else arr.copy()).to(
+        torch.device("cuda", torch.cuda.current_device()))
+
+
+def csd_launch(plan, x, over_trials, unit_modulus=False, out=None):
+    """One library call: x contiguous CUDA [n, C, T] (f32 / f64) -> complex [n, K, C, C], or over_trials [K, C, C];
+    ``out`` (a contiguous complex tensor of that shape) receives the result if given."""
+    L = _lib.lib()
+    n, Cc, T = x.shape
+    f64 = x.dtype == torch.float64
+    K = plan.bins
+    shape = (K, Cc, Cc) if over_trials else (n, K, Cc, Cc)
+    cdtype = torch.complex128 if f64 else torch.complex64
+    if out is None:
+        out = torch.empty(shape, dtype=cdtype, device=x.device)
+    elif tuple(out.shape) != shape or out.dtype != cdtype or not out.is_contiguous() or out.device != x.device:
+        raise ValueError(f"out must be a contiguous {cdtype} tensor of shape {shape} on {x.device}")
+    if n == 0:
+        return out.zero_() if over_trials else out
+    L.isd_csd_chunk_bytes(0 if CSD_CHUNK_BYTES is None else int(CSD_CHUNK_BYTES))
+    need = int(L.isd_csd_work_bytes(plan._h, n, Cc, T, int(bool(over_trials)), int(f64)))
+    if need < 0:
+        _lib.check(need)
+    with torch.cuda.device(x.device):
+        work = torch.empty(need, dtype=torch.uint8, device=x.device)
+        fn = L.isd_csd_welch_f64 if f64 else L.isd_csd_welch_f32
+        _lib.check(fn(plan._h, x.data_ptr(), out.data_ptr(), n, Cc, T, int(bool(over_trials)),
+                      int(bool(unit_modulus)), work.data_ptr(),
+                      C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return out
+
+
+def _plan_for(d, sfreq, remove_dc, device):
+    return _cached_plan(d.n_fft, d.n_per_seg, d.n_overlap, d.k_lo, d.k_hi, d.window.tobytes(), float(sfreq),
+                        bool(remove_dc), device.index)
+
+
+def csd_array_welch(x, sfreq, fmin=0, fmax=np.inf, n_fft=256, n_overlap=0, n_per_seg=None, window="hann",
+                    remove_dc=True, average="segments"):
+    """Welch cross-spectral density of x [n, C, T] ([C, T] is n = 1) -> (csd, freqs): csd complex [n, K, C, C] for
+    ``average='segments'``, [K, C, C] for ``average='trials'``; freqs a float64 ndarray [K].  A density,
+    ``S[i, j] = mean X_i conj(X_j) c_k / (sfreq Σw²)``; the Welch arguments are those of ``psd_array_welch``.
+    ``csd[..., i, j] == conj(csd[..., j, i])`` bit for bit and the diagonal is real."""
+    if average not in ("segments", "trials"):
+        raise ValueError(f"average={average!r} (need 'segments' or 'trials')")
+    x, is_tensor, squeeze = _check_input(x)
+    d = _design(int(x.shape[-1]), sfreq, fmin, fmax, n_fft, n_overlap, n_per_seg, window)
+    xd = _to_device(x, is_tensor)
+    out = csd_launch(_plan_for(d, sfreq, remove_dc, xd.device), xd, average == "trials")
+    if squeeze and average == "segments":
+        out = out[0]
+    return (out if is_tensor else out.cpu().numpy()), d.freqs.copy()
+
+
+def band_bins(freqs, bands=BANDS_5):
+    """Per band (name, lo, hi) the indices of ``freqs`` with lo <= f <= hi (both ends inclusive, as ``band_power``)."""
+    freqs = np.asarray(freqs, dtype=np.float64)
+    return [np.flatnonzero((freqs >= lo) & (freqs <= hi)) for lo, hi in band_edges(bands)]
+
+
+def check_methods(method):
+    """-> (list of names, whether a single name was given); raises by name for what is not provided."""
+    single = isinstance(method, str)
+    names = [method] if single else list(method)
+    if not names:
+        raise ValueError("method is empty")
+    for m in names:
+        if m in NOT_PROVIDED:
+            raise NotImplementedError(f"method={m!r} is not a Hermitian product of segment spectra and is not "
+                                      f"provided; provided: {', '.join(METHODS)}")
+        if m not in METHODS:
+            raise ValueError(f"method={m!r} (provided: {', '.join(METHODS)})")
+    return names, single
+
+
+def _measure(name, S, E, N):
+    """One measure from the density S and / or the mean phase product E ([..., K, C, C] complex tensors)."""
+    if name in DENSITY_METHODS:
+        dg = torch.diagonal(S, dim1=-2, dim2=-1).real
+        cohy = S / torch.sqrt(dg[..., :, None] * dg[..., None, :])
+        return cohy if name == "cohy" else (cohy.abs() if name == "coh" else cohy.imag)
+    if name == "plv":
+        return E.abs()
+    if name == "ciplv":                                            # 1 - Re^2 as (1 - Re)(1 + Re): 1 - Re is exact near 1
+        return E.imag.abs() / torch.sqrt((1.0 - E.real) * (1.0 + E.real))
+    return (N * (E.real * E.real + E.imag * E.imag) - 1.0) / (N - 1.0)          # ppc
+
+
+def _band_mean(v, bins):
+    """[..., K, C, C] -> [..., n_bands, C, C]: the mean over each band's bins."""
+    return torch.stack([v[..., torch.as_tensor(b, device=v.device), :, :].mean(-3) for b in bins], dim=-3)
+
+
+def spectral_connectivity(x, sfreq, method="coh", fmin=0, fmax=np.inf, n_fft=256, n_overlap=0, n_per_seg=None,
+                          window="hann", remove_dc=True, average="trials", faverage=False, bands=None, mode="welch",
+                          indices=None):
+    """Connectivity of x [n, C, T] between every pair of channels -> (con, freqs).
+
+    ``method``: one of 'coh', 'cohy', 'imcoh', 'plv', 'ciplv', 'ppc' or a list of them (a list returns a list; all
+    share one density pass and / or one unit-modulus pass).  ``average='trials'`` estimates over every segment of every
+    trial, con [K, C, C]; ``'segments'`` per trial over its own segments, con [n, K, C, C] (computed in trial chunks
+    of at most CON_CHUNK_BYTES).  ``faverage=True`` averages the measure over the kept bins of each band of ``bands``
+    (default BANDS_5): con [..., n_bands, C, C] and freqs the bands' mean frequencies; a band without a kept bin is an
+    error.  'cohy' is complex, the others real.  'ppc' needs at least two (trial, segment) pairs.  The diagonal of
+    'ciplv' is 0 / 0 = NaN; when 'ciplv' is asked for, the unit-modulus pass runs in fp64 for float32 input too
+    (its denominator 1 - (Re E)^2 amplifies the rounding of E) and 'plv' / 'ppc' of the same call come from it.  Names and formulas follow mne-connectivity's documentation; parity with that library is
+    unpinned (it is not installed here)."""
+    names, single = check_methods(method)
+    if mode != "welch":
+        raise NotImplementedError(f"mode={mode!r}: only the Welch estimate is provided (no multitaper, no wavelets)")
+    if indices is not None:
+        raise NotImplementedError("indices= is not provided: every pair of channels is computed")
+    if average not in ("segments", "trials"):
+        raise ValueError(f"average={average!r} (need 'segments' or 'trials')")
+    x, is_tensor, _ = _check_input(x)
+    n, Cc, T = (int(v) for v in x.shape)
+    d = _design(T, sfreq, fmin, fmax, n_fft, n_overlap, n_per_seg, window)
+    K = d.k_hi - d.k_lo + 1
+    freqs = d.freqs.copy()
+    bins = None
+    if faverage:
+        bands = BANDS_5 if bands is None else bands
+        bins = band_bins(freqs, bands)
+        for b, band in zip(bins, bands):
+            if b.size == 0:
+                raise ValueError(f"band {band!r} holds no kept frequency bin")
+        freqs = np.array([d.freqs[b].mean() for b in bins])
+    over = average == "trials"
+    N = float(n * d.n_segments if over else d.n_segments)
+    if "ppc" in names and N < 2:
+        raise ValueError("method='ppc' needs at least two (trial, segment) pairs")
+    need_s = any(m in DENSITY_METHODS for m in names)
+    need_e = any(m in PHASE_METHODS for m in names)
+
+    def run(xd):
+        plan = _plan_for(d, sfreq, remove_dc, xd.device)
+        S = csd_launch(plan, xd, over) if need_s else None
+        # ciplv divides by d = 1 - (Re E)^2 and so multiplies the error of E by up to 1 / d: nearly locked pairs
+        # (d ~ 1e-5) would keep two digits of a float32 E.  When it is asked for, the one unit-modulus pass runs in
+        # fp64 whatever the input type, and the phase measures are rounded to the input's type at the end.
+        xe = xd.double() if "ciplv" in names else xd
+        E = csd_launch(plan, xe, over, unit_modulus=True) if need_e else None
+        vals = [_measure(m, S, E, N) for m in names]
+        vals = [v if m in DENSITY_METHODS else v.to(xd.dtype) for m, v in zip(names, vals)]
+        return [_band_mean(v, bins) for v in vals] if faverage else vals
+
+    if over or n == 0:
+        res = run(_to_device(x, is_tensor))
+    else:
+        per = K * Cc * Cc * 16 * (int(need_s) + int(need_e))
+        step = max(1, CON_CHUNK_BYTES // per)
+        parts = [run(_to_device(x[s:s + step], is_tensor)) for s in range(0, n, step)]
+        res = [torch.cat([p[i] for p in parts]) for i in range(len(names))]
+    if not is_tensor:
+        res = [r.cpu().numpy() for r in res]
+    return (res[0] if single else res), freqs

@@ -9,7 +9,8 @@ matrices by a batched one-sided Jacobi eigen-decomposition.  What works on the [
 roots, exp, the step control of the mean iteration) is host work in float64 with NumPy ``eigh``, as ``csp.decompose``.
 pyriemann is not vendored in the reference and is not installed here: the behaviour is restated from the published
 method and pinned against a NumPy restatement (tests/riemann_ref.py); parity with pyriemann itself is unpinned.
-There is no CPU fallback.
+``CoSpectra`` gives one SPD matrix per trial and frequency (the real part of ``connectivity.csd_array_welch``) for a
+tangent space per frequency.  There is no CPU fallback.
 """
 import numpy as np
 import torch
@@ -366,6 +367,41 @@ class Covariances(_Estimator):
         if isinstance(X, torch.Tensor):
             return torch.cat(parts) if parts else torch.empty(0, C_, C_, dtype=X.dtype, device=X.device)
         return torch.cat(parts).cpu().numpy() if parts else np.empty((0, C_, C_))
+
+    def fit_transform(self, X, y=None, **fit_params):
+        return self.fit(X, y).transform(X)
+
+
+class CoSpectra(_Estimator):
+    """The shape of ``pyriemann.estimation.CoSpectra``: X [n, C, T] -> the cospectral matrices [n, C, C, K], one SPD
+    matrix per trial and frequency, frequency last (pyriemann's axis order) so that ``TangentSpace`` can be fitted
+    per frequency on ``out[..., k]``.  It is the real part of ``connectivity.csd_array_welch`` per trial with taps
+    ``np.hanning(window)``, ``n_fft = window`` and ``n_overlap = int(overlap * window)``, over the bins with
+    ``fmin <= f <= fmax`` at sampling rate ``fs`` (None: 1, frequencies in cycles per sample); ``freqs_`` holds them
+    after ``transform``.  **The scaling is this package's**: a density, c_k / (fs Σw²) times the mean over segments
+    with each segment's mean removed; pyriemann is not installed here and parity with it is unpinned."""
+    _param_names = ("window", "overlap", "fmin", "fmax", "fs")
+
+    def __init__(self, window=128, overlap=0.75, fmin=None, fmax=None, fs=None):
+        self.window, self.overlap, self.fmin, self.fmax, self.fs = window, overlap, fmin, fmax, fs
+
+    def fit(self, X, y=None):
+        return self
+
+    def transform(self, X):
+        from .connectivity import csd_array_welch
+        from .csp import CSP
+        X = CSP._check_X(X)
+        window = int(self.window)
+        if not 0 <= self.overlap < 1:
+            raise ValueError(f"overlap={self.overlap!r} (need 0 <= overlap < 1)")
+        csd, self.freqs_ = csd_array_welch(
+            X, 1.0 if self.fs is None else self.fs, 0.0 if self.fmin is None else self.fmin,
+            np.inf if self.fmax is None else self.fmax, n_fft=window, n_overlap=int(self.overlap * window),
+            n_per_seg=window, window=np.hanning(window), average="segments")
+        re = csd.real
+        return re.permute(0, 2, 3, 1).contiguous() if isinstance(re, torch.Tensor) else \
+            np.ascontiguousarray(re.transpose(0, 2, 3, 1))
 
     def fit_transform(self, X, y=None, **fit_params):
         return self.fit(X, y).transform(X)

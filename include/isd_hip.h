@@ -332,6 +332,29 @@ int isd_psd_welch_f64(const isd_psd_plan* plan, const double* x, double* out, in
                       void* work, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Cross-spectral density by Welch's method on a Welch PSD plan: its segments, window, kept bins, scale and remove_dc.
+ *   S[k][i][j] = scale[k] / N  sum X_i[k] conj(X_j[k]),   X[k] = sum_t (x[t] - mean) w[t] exp(-2 pi i k t / n_fft),
+ * which is scipy.signal.csd(x_j, x_i, detrend='constant', scaling='density') (scipy conjugates its first argument).
+ * x [n][C][T] -> out complex, (re, im) interleaved:  over_trials == 0: [n][K][C][C][2], the sum over the S segments of
+ * a trial, N = S;  over_trials != 0: [K][C][C][2], the sum over every (trial, segment), N = n S.  With unit_modulus
+ * every X[k] is first divided by its modulus (an exact zero stays zero) and the factor is 1 / N: the mean phase
+ * difference behind the phase-locking measures.  out[.., i, j] is the exact conjugate of out[.., j, i] and the
+ * diagonal's imaginary part is exactly 0.  Sums run in (trial, segment) order with no atomics: bitwise repeatable.
+ * `work`: isd_csd_work_bytes bytes, 256-byte aligned; it is bounded: the trials run in chunks inside the call, of
+ * at most isd_csd_chunk_bytes of intermediate spectra each (default 256 MiB; isd_csd_chunk_bytes(b) sets it for
+ * later calls of the calling thread, b = 0 restores the default, b < 0 only asks; returns the value before), and over_trials adds the
+ * chunks in order.  x needs element alignment only, out that of one complex element.  No call synchronises with the
+ * host.  Envelope: the plan's, 1 <= C <= 128, T >= n_per_seg, n >= 0 (n = 0 returns at once); outside it
+ * ISD_ERR_UNSUPPORTED.
+ * ---------------------------------------------------------------------- */
+int64_t isd_csd_chunk_bytes(int64_t bytes);
+int64_t isd_csd_work_bytes(const isd_psd_plan* plan, int64_t n, int64_t C, int64_t T, int over_trials, int is_f64);
+int isd_csd_welch_f32(const isd_psd_plan* plan, const float* x, float* out, int64_t n, int64_t C, int64_t T,
+                      int over_trials, int unit_modulus, void* work, void* stream);
+int isd_csd_welch_f64(const isd_psd_plan* plan, const double* x, double* out, int64_t n, int64_t C, int64_t T,
+                      int over_trials, int unit_modulus, void* work, void* stream);
+
+/* ------------------------------------------------------------------------
  * Complex FIR bank with decimation: the data-sized step of a time-frequency transform
  * (isd_amd.tfr_array_morlet, the counterpart of mne.time_frequency.tfr_array_morlet; isd_amd.tfr.cwt).  The library
  * knows nothing about wavelets: the plan takes n_freqs complex tap vectors of odd lengths and
