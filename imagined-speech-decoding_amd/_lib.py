@@ -95,6 +95,11 @@ SIGNATURES = {
     "isd_tfr_work_bytes": (_i64, [_p, _i64, _i64, _i64, _i, _i]),
     "isd_tfr_cwt_f32": (_i, [_p, _p, _p, _i64, _i64, _i64, _i, _p, _p]),
     "isd_tfr_cwt_f64": (_i, [_p, _p, _p, _i64, _i64, _i64, _i, _p, _p]),
+    "isd_resample_plan_create": (_i, [C.POINTER(_p), _i, _i, _i, _pd, _i]),
+    "isd_resample_plan_destroy": (_i, [_p]),
+    "isd_resample_out_len": (_i64, [_p, _i64]),
+    "isd_resample_poly_f32": (_i, [_p, _p, _p, _i64, _i, _i, C.c_double, _p, _p]),
+    "isd_resample_poly_f64": (_i, [_p, _p, _p, _i64, _i, _i, C.c_double, _p, _p]),
     "isd_conv4_plan_create": (_i, [C.POINTER(_p), _i, _i, _pi, _pi, _i, _i, _i, _i]),
     "isd_conv4_plan_destroy": (_i, [_p]),
     "isd_conv4_plan_set_activation_dtype": (_i, [_p, _i]),

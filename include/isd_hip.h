@@ -398,6 +398,39 @@ int isd_tfr_cwt_f64(const isd_tfr_plan* plan, const double* x, void* out, int64_
                     void* work, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Polyphase rational resampling of rows: scipy.signal.resample_poly (isd_amd.resample_poly, isd_amd.resample).
+ *   y[row][n] = bg + sum_m xe[m] h[half_len + n down - m up]   over the m with 0 <= half_len + n down - m up < n_taps,
+ *   0 <= n < n_out = ceil(T up / down)  (isd_resample_out_len),
+ * xe the row minus bg extended beyond 0 .. T-1 by `mode`: ISD_RESAMPLE_CONSTANT the value cval, _EDGE the end
+ * samples, _REFLECT the whole-sample mirror (period 2T - 2), _SYMMETRIC the half-sample mirror (period 2T), _LINE the
+ * straight line through x[0] and x[T-1].  bg = background[row] (device, fp64) or 0 when background is NULL; it is
+ * taken off in fp64 while the row is read and added back to y, which is how the host provides scipy's 'mean',
+ * 'median', 'minimum' and 'maximum' pad types (mode _CONSTANT, cval 0).  The library designs no filter: the plan takes
+ * up / down already reduced by their gcd, and the taps (host, fp64) already multiplied by up, with their centre.
+ *
+ * x [rows][T] -> y [rows][n_out], distinct buffers, element alignment only.  _f32 computes on the fp32 matrix cores,
+ * _f64 on the fp64 ones; no atomics, a row's result does not depend on the other rows of the call, and a sample
+ * outside 0 .. T-1 is never read.  Within a row an infinite sample reaches the up to 15 neighbouring outputs of its
+ * block of 16 through a zero tap (inf . 0), which scipy's loop would skip.  No call synchronises with the host.
+ *
+ * Envelope: up, down <= ISD_RESAMPLE_MAX_RATE, n_taps <= ISD_RESAMPLE_MAX_TAPS, device tables within 16 MiB,
+ * n_out < 2^31, T >= 1 (T >= 2 for _REFLECT and _LINE: ISD_ERR_INVALID); outside it ISD_ERR_UNSUPPORTED with the
+ * reason in the last-error string.
+ * ---------------------------------------------------------------------- */
+enum { ISD_RESAMPLE_CONSTANT = 0, ISD_RESAMPLE_EDGE = 1, ISD_RESAMPLE_REFLECT = 2, ISD_RESAMPLE_SYMMETRIC = 3,
+       ISD_RESAMPLE_LINE = 4 };
+enum { ISD_RESAMPLE_MAX_RATE = 1024, ISD_RESAMPLE_MAX_TAPS = 20481 };
+typedef struct isd_resample_plan isd_resample_plan;
+int isd_resample_plan_create(isd_resample_plan** out, int up, int down, int n_taps, const double* taps /* host */,
+                             int half_len);
+int isd_resample_plan_destroy(isd_resample_plan* plan);
+int64_t isd_resample_out_len(const isd_resample_plan* plan, int64_t T);
+int isd_resample_poly_f32(const isd_resample_plan* plan, const float* x, float* y, int64_t rows, int T, int mode,
+                          double cval, const double* background /* device [rows] or NULL */, void* stream);
+int isd_resample_poly_f64(const isd_resample_plan* plan, const double* x, double* y, int64_t rows, int T, int mode,
+                          double cval, const double* background /* device [rows] or NULL */, void* stream);
+
+/* ------------------------------------------------------------------------
  * Zone-wise Conv4Layers stack over sliding windows: the reference's
  *   FAST.forward_head   src/fast/models/fast.py:242-252  (unfold window_len / slide_step)
  *   Head.forward        src/fast/models/fast.py:209-210  (zone gather, one encoder per zone, stack)
