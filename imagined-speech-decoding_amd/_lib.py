@@ -7,6 +7,9 @@ product raises.  Build it with ``python -m isd_amd.build`` (or
 import ctypes as C
 import os
 
+import numpy as np
+import torch
+
 from .build import LIB_PATH
 
 ISD_OK = 0
@@ -222,6 +225,46 @@ class Handle:
                 getattr(lib(), self._destroy)(h)
             except Exception:
                 pass
+
+
+def stream():
+    """The current stream of the current device, as the library's ``stream`` argument."""
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def workspace(nbytes, device):
+    """The uint8 scratch tensor a ``*_work_bytes`` entry point asked for; its negative answer is the library's error."""
+    if nbytes < 0:
+        check(int(nbytes))
+    return torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+
+
+def check_array(x, name, dtypes=(torch.float32, torch.float64)):
+    """The type rules of an array argument, none of which needs a GPU -> (x, is_tensor): a CUDA tensor of one of
+    ``dtypes`` as it is, anything else as a floating-point ndarray.  Rank and shape are the caller's."""
+    if isinstance(x, torch.Tensor):
+        if not x.is_cuda:
+            raise TypeError("tensor input must live on the GPU (there is no CPU fallback)")
+        if x.dtype not in dtypes:
+            raise TypeError(f"{name} must be {' or '.join(str(d).replace('torch.', '') for d in dtypes)}")
+        return x, True
+    x = np.asarray(x)
+    if x.dtype.kind != "f":
+        raise TypeError(f"{name} must be floating point")
+    return x, False
+
+
+def to_device(x, is_tensor, who, dtype=np.float64, device=None):
+    """x of ``check_array`` on the GPU: a tensor made contiguous, an ndarray uploaded as ``dtype`` to ``device`` (the
+    current one by default).  A read-only array (np.frombuffer, a memory map) is copied first: torch warns about
+    sharing one."""
+    if is_tensor:
+        return x.contiguous()
+    if not torch.cuda.is_available():
+        raise RuntimeError(f"isd_amd.{who} needs an MI355X GPU: there is no CPU fallback")
+    arr = np.ascontiguousarray(x, dtype=dtype)
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    return torch.from_numpy(arr if arr.flags.writeable else arr.copy()).to(dev)
 
 
 def int_array(vals):

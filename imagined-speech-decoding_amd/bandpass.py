@@ -8,8 +8,6 @@ compensation, 'reflect_limited' edge padding).  The taps are designed on the hos
 the reference and is not installed here: parity is pinned against scipy / NumPy (oracle/fir.py), not against MNE.
 There is no CPU fallback.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
@@ -45,8 +43,7 @@ class FirFilter(_lib.Handle):
             return out
         fn = _lib.lib().isd_fir_zero_phase_f32 if x.dtype == torch.float32 else _lib.lib().isd_fir_zero_phase_f64
         with torch.cuda.device(x.device):
-            _lib.check(fn(self._h, x.data_ptr(), out.data_ptr(), rows, T,
-                          C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+            _lib.check(fn(self._h, x.data_ptr(), out.data_ptr(), rows, T, _lib.stream()))
         return out
 
 
@@ -64,15 +61,6 @@ def filter_data(data, sfreq, l_freq, h_freq, picks=None, filter_length="auto", l
     if picks is not None or iir_params is not None:
         raise NotImplementedError("picks / iir_params are not provided")
     flt = FirFilter(sfreq, l_freq, h_freq, filter_length, l_trans_bandwidth, h_trans_bandwidth, fir_window)
-    if isinstance(data, torch.Tensor):
-        if not data.is_cuda:
-            raise TypeError("tensor input must live on the GPU (there is no CPU fallback)")
-        return flt(data)
-    if not torch.cuda.is_available():
-        raise RuntimeError("isd_amd.filter_data needs an MI355X GPU: there is no CPU fallback")
-    arr = np.asarray(data)
-    if arr.dtype.kind != "f":
-        raise TypeError("data must be floating point")
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    x = torch.as_tensor(np.ascontiguousarray(arr, dtype=np.float64)).to(dev)
-    return flt(x).cpu().numpy()
+    data, is_tensor = _lib.check_array(data, "data")
+    y = flt(_lib.to_device(data, is_tensor, "filter_data", device=device))
+    return y if is_tensor else y.cpu().numpy()

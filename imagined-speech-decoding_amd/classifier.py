@@ -15,7 +15,7 @@ import torch.nn as nn
 from . import _lib
 from .constants import BANDS_9, BANDS_40, CLASSES, ELECTRODES, ZONES
 from .features import FeatureExtractor
-from .nn import (FAST, EEGNet_Encoder, FeatureCNN, TSception, _bn_sync_world, _FlatParamMixin, _stream,
+from .nn import (FAST, EEGNet_Encoder, FeatureCNN, TSception, _bn_sync_world, _FlatParamMixin,
                  bn_head_backward, bn_head_forward, bn_head_workspace_floats, fast_config, token_mean_predict)
 
 
@@ -163,7 +163,7 @@ class HotPath:
         plan = m.conv_plan(x)
         B, _, T = x.shape
         N = plan.windows(T)
-        dev, st = x.device, _stream()
+        dev, st = x.device, _lib.stream()
         fp, f4 = flat.data_ptr(), 4
         ws_bytes = int(L.isd_conv4_workspace_bytes(plan._h, B, T))
         ws = self._buf("conv", ws_bytes // 4, dev)
@@ -199,7 +199,7 @@ class HotPath:
         feature block ``feat`` [B*N, K].  Returns (dict(logits, pred[, loss]), the gradient w.r.t. ``feat``); with
         labels and a gradient block ``gflat`` the dense layers' gradients are written into it, else the second is None."""
         L, want_grad = _lib.lib(), gflat is not None
-        dev, st = feat.device, _stream()
+        dev, st = feat.device, _lib.stream()
         fp, f4 = flat.data_ptr(), 4
         acts, pres = [feat], []
         M = B * N
@@ -331,7 +331,7 @@ class TSceptionPath(HotPath):
         B, _, T = x.shape
         if B > self.MAX_BATCH:
             raise ValueError(f"TSception takes at most {self.MAX_BATCH} trials per pass (got {B}): split the batch")
-        dev, st, n_cls = x.device, _stream(), m.num_classes
+        dev, st, n_cls = x.device, _lib.stream(), m.num_classes
         training = want_grad and labels is not None
         if _bn_sync_world(True, training) > 1:
             raise NotImplementedError("TSception trains on one device: data parallelism would need synchronised "
@@ -491,7 +491,7 @@ class Trainer:
         _lib.check(_lib.lib().isd_adamw_step(
             self.flat.data_ptr(), self.flat_grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
             self.flat.numel(), self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, self.global_step,
-            None, None, _stream()))
+            None, None, _lib.stream()))
 
     def optimizer_state(self):
         """The moment estimates and the step count (``load_optimizer_state`` puts them back)."""

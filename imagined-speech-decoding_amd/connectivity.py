@@ -31,7 +31,6 @@ runs its unit-modulus pass in fp64 for float32 input too.  There is no CPU fallb
 ndarray in -> computed in fp64 on the GPU -> float64 / complex128 ndarray out; float32 / float64 CUDA tensor in ->
 CUDA tensor of the matching real or complex dtype out.
 """
-import ctypes as C
 
 import numpy as np
 import torch
@@ -53,16 +52,7 @@ NOT_PROVIDED = ("pli", "dpli", "wpli", "wpli2_debiased", "pli2_unbiased", "gc", 
 
 def _check_input(x):
     """-> (x as [n, C, T], is_tensor, squeeze): every check that needs no GPU."""
-    is_tensor = isinstance(x, torch.Tensor)
-    if is_tensor:
-        if not x.is_cuda:
-            raise TypeError("tensor input must live on the GPU (there is no CPU fallback)")
-        if x.dtype not in (torch.float32, torch.float64):
-            raise TypeError("x must be float32 or float64")
-    else:
-        x = np.asarray(x)
-        if x.dtype.kind != "f":
-            raise TypeError("x must be floating point")
+    x, is_tensor = _lib.check_array(x, "x")
     if x.ndim not in (2, 3):
         raise ValueError(f"x must be [n, C, T] or [C, T], got {tuple(x.shape)}")
     squeeze = x.ndim == 2
@@ -86,16 +76,6 @@ def _design(T, sfreq, fmin, fmax, n_fft, n_overlap, n_per_seg, window):
     return d
 
 
-def _to_device(x, is_tensor):
-    if is_tensor:
-        return x.contiguous()
-    if not torch.cuda.is_available():
-        raise RuntimeError("isd_amd.connectivity needs an MI355X GPU: there is no CPU fallback")
-    arr = np.ascontiguousarray(x, dtype=np.float64)
-    return torch.from_numpy(arr if arr.flags.writeable else arr.copy()).to(
-        torch.device("cuda", torch.cuda.current_device()))
-
-
 def csd_launch(plan, x, over_trials, unit_modulus=False, out=None):
     """One library call: x contiguous CUDA [n, C, T] (f32 / f64) -> complex [n, K, C, C], or over_trials [K, C, C];
     ``out`` (a contiguous complex tensor of that shape) receives the result if given."""
@@ -112,15 +92,11 @@ def csd_launch(plan, x, over_trials, unit_modulus=False, out=None):
     if n == 0:
         return out.zero_() if over_trials else out
     L.isd_csd_chunk_bytes(0 if CSD_CHUNK_BYTES is None else int(CSD_CHUNK_BYTES))
-    need = int(L.isd_csd_work_bytes(plan._h, n, Cc, T, int(bool(over_trials)), int(f64)))
-    if need < 0:
-        _lib.check(need)
+    work = _lib.workspace(L.isd_csd_work_bytes(plan._h, n, Cc, T, int(bool(over_trials)), int(f64)), x.device)
     with torch.cuda.device(x.device):
-        work = torch.empty(need, dtype=torch.uint8, device=x.device)
         fn = L.isd_csd_welch_f64 if f64 else L.isd_csd_welch_f32
         _lib.check(fn(plan._h, x.data_ptr(), out.data_ptr(), n, Cc, T, int(bool(over_trials)),
-                      int(bool(unit_modulus)), work.data_ptr(),
-                      C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+                      int(bool(unit_modulus)), work.data_ptr(), _lib.stream()))
     return out
 
 
@@ -139,7 +115,7 @@ def csd_array_welch(x, sfreq, fmin=0, fmax=np.inf, n_fft=256, n_overlap=0, n_per
         raise ValueError(f"average={average!r} (need 'segments' or 'trials')")
     x, is_tensor, squeeze = _check_input(x)
     d = _design(int(x.shape[-1]), sfreq, fmin, fmax, n_fft, n_overlap, n_per_seg, window)
-    xd = _to_device(x, is_tensor)
+    xd = _lib.to_device(x, is_tensor, "connectivity")
     out = csd_launch(_plan_for(d, sfreq, remove_dc, xd.device), xd, average == "trials")
     if squeeze and average == "segments":
         out = out[0]
@@ -239,11 +215,11 @@ def spectral_connectivity(x, sfreq, method="coh", fmin=0, fmax=np.inf, n_fft=256
         return [_band_mean(v, bins) for v in vals] if faverage else vals
 
     if over or n == 0:
-        res = run(_to_device(x, is_tensor))
+        res = run(_lib.to_device(x, is_tensor, "connectivity"))
     else:
         per = K * Cc * Cc * 16 * (int(need_s) + int(need_e))
         step = max(1, CON_CHUNK_BYTES // per)
-        parts = [run(_to_device(x[s:s + step], is_tensor)) for s in range(0, n, step)]
+        parts = [run(_lib.to_device(x[s:s + step], is_tensor, "connectivity")) for s in range(0, n, step)]
         res = [torch.cat([p[i] for p in parts]) for i in range(len(names))]
     if not is_tensor:
         res = [r.cpu().numpy() for r in res]

@@ -11,7 +11,6 @@ method.  MNE is not vendored in the reference and is not installed here: parity 
 (tests/test_csp_*.py), not against MNE.  There is no CPU fallback.  One CSP per band of a filterbank, on the raw
 trials: ``isd_amd.FBCSP`` (fbcsp.py).
 """
-import ctypes as C
 
 import numpy as np
 import torch
@@ -22,10 +21,6 @@ from .classifier import NotFittedError
 MAX_COMPONENTS = 16                  # isd_csp_power_*: 1 <= m <= 16
 MAX_CHANNELS = 128                   # isd_trial_cov_*: 1 <= C <= 128
 COV_CHUNK_BYTES = 256 << 20          # bound on the [chunk, C, C] covariance buffer of fit
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _check_x(x):
@@ -47,7 +42,7 @@ def trial_covariances(x):
     if n:
         fn = _lib.lib().isd_trial_cov_f32 if x.dtype == torch.float32 else _lib.lib().isd_trial_cov_f64
         with torch.cuda.device(x.device):
-            _lib.check(fn(x.data_ptr(), cov.data_ptr(), n, Cc, T, _stream()))
+            _lib.check(fn(x.data_ptr(), cov.data_ptr(), n, Cc, T, _lib.stream()))
     return cov
 
 
@@ -73,7 +68,7 @@ def cov_group_mean(cov, idx, offs, norm_trace=False):
     with torch.cuda.device(cov.device):
         _lib.check(_lib.lib().isd_cov_group_mean(cov.data_ptr(), int(cov.dtype == torch.float64), idx_d.data_ptr(),
                                                  offs_d.data_ptr(), int(bool(norm_trace)), out.data_ptr(), n,
-                                                 cov.shape[1], K, _stream()))
+                                                 cov.shape[1], K, _lib.stream()))
     return out
 
 
@@ -89,7 +84,7 @@ def csp_power(x, w, log=True):
     if n:
         fn = _lib.lib().isd_csp_power_f32 if x.dtype == torch.float32 else _lib.lib().isd_csp_power_f64
         with torch.cuda.device(x.device):
-            _lib.check(fn(x.data_ptr(), w.data_ptr(), out.data_ptr(), n, Cc, T, w.shape[0], int(bool(log)), _stream()))
+            _lib.check(fn(x.data_ptr(), w.data_ptr(), out.data_ptr(), n, Cc, T, w.shape[0], int(bool(log)), _lib.stream()))
     return out
 
 
@@ -218,34 +213,17 @@ class CSP:
 
     @staticmethod
     def _check_X(X):
-        if isinstance(X, torch.Tensor):
-            if X.ndim != 3:
-                raise ValueError(f"X must be [n, C, T], got {tuple(X.shape)}")
-            if not X.is_cuda:
-                raise TypeError("tensor input must live on the GPU (there is no CPU fallback)")
-            if X.dtype not in (torch.float32, torch.float64):
-                raise TypeError("X must be float32 or float64")
-            return X
-        X = np.asarray(X)
+        X, _ = _lib.check_array(X, "X")
         if X.ndim != 3:
-            raise ValueError(f"X must be [n, C, T], got {X.shape}")
-        if X.dtype.kind != "f":
-            raise TypeError("X must be floating point")
+            raise ValueError(f"X must be [n, C, T], got {tuple(X.shape)}")
         return X
 
     @staticmethod
     def _chunks(X, rows):
         """CUDA [<= rows, C, T] slices of X in order; an ndarray is uploaded slice by slice as float64."""
-        if not isinstance(X, torch.Tensor):
-            if not torch.cuda.is_available():
-                raise RuntimeError("isd_amd.CSP needs an MI355X GPU: there is no CPU fallback")
-            dev = torch.device("cuda", torch.cuda.current_device())
+        is_tensor = isinstance(X, torch.Tensor)
         for s in range(0, X.shape[0], rows):
-            part = X[s:s + rows]
-            if isinstance(part, torch.Tensor):
-                yield s, part.contiguous()
-            else:
-                yield s, torch.as_tensor(np.ascontiguousarray(part, dtype=np.float64)).to(dev)
+            yield s, _lib.to_device(X[s:s + rows], is_tensor, "CSP")
 
     def _power(self, X, log):
         """[n, m] average power of the picked components, in X's kind (ndarray -> float64 ndarray)."""

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <vector>
 #include "../../include/isd_hip.h"
 
 namespace isd {
@@ -16,6 +17,15 @@ bool zone_batch_open();             // a zone batch is recording on this thread 
     if (!(cond)) {                               \
       isd::set_error(__VA_ARGS__);               \
       return ISD_ERR_INVALID;                    \
+    }                                            \
+  } while (0)
+
+// a well-formed request that the kernels do not cover
+#define ISD_CHECK_SUPPORTED(cond, ...)           \
+  do {                                           \
+    if (!(cond)) {                               \
+      isd::set_error(__VA_ARGS__);               \
+      return ISD_ERR_UNSUPPORTED;                \
     }                                            \
   } while (0)
 
@@ -38,6 +48,35 @@ static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 #if defined(__HIPCC__)
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));   // an MFMA accumulator fragment
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef double f64x4 __attribute__((ext_vector_type(4)));
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+
+// v_mfma_{f32,f64}_16x16x4: Acc is the C/D fragment, Vec 16 bytes of one LDS row (VEC elements), row(q, r) the row of
+// C/D register r in lane group q = lane >> 4 (the column is lane & 15); lane_row(lane, r) is the same for a kernel that
+// has the lane in hand, not q.  A transform's own tile constants go in a struct derived from this one.
+template <typename S> struct Mfma16;
+template <> struct Mfma16<float> {
+  using Acc = f32x4;
+  using Vec = f32x4;
+  static constexpr int VEC = 4;
+  static __device__ __forceinline__ Acc mma(float a, float b, Acc c) {
+    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+  }
+  static __device__ __forceinline__ int row(int q, int r) { return 4 * q + r; }
+  static __device__ __forceinline__ int lane_row(int lane, int r) { return row(lane >> 4, r); }
+};
+template <> struct Mfma16<double> {
+  using Acc = f64x4;
+  using Vec = f64x2;
+  static constexpr int VEC = 2;
+  static __device__ __forceinline__ Acc mma(double a, double b, Acc c) {
+    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
+  }
+  // the f64 C/D map: a lane group's four registers are rows q, q + 4, q + 8, q + 12, not four consecutive rows
+  static __device__ __forceinline__ int row(int q, int r) { return q + 4 * r; }
+  static __device__ __forceinline__ int lane_row(int lane, int r) { return row(lane >> 4, r); }
+};
 
 // DPP row shift right by N inside each 16-lane row; lanes with no source get 0 (bound_ctrl: no `old` operand to
 // initialise, and the shift can fold into a consuming VOP2).
@@ -127,6 +166,27 @@ static inline int launch_lds(void (*kernel)(Params...), dim3 grid, dim3 block, s
   hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, args...);
   ISD_LAUNCH_CHECK();
   return ISD_OK;
+}
+
+// ISD_OK when there is a HIP device; what a plan creator asks before it allocates
+static inline int require_device(const char* who) {
+  int n_dev = 0;
+  if (hipGetDeviceCount(&n_dev) == hipSuccess && n_dev > 0) return ISD_OK;
+  set_error("%s: no HIP device", who);
+  return ISD_ERR_NO_DEVICE;
+}
+
+// A host table of n elements into a new device buffer at *dst: never a zero-byte allocation, no copy of nothing.
+// A plan creator chains these on the hipError_t and leaves the freeing to its *_plan_destroy.
+template <typename T>
+static inline hipError_t upload(T** dst, const T* src, size_t n) {
+  hipError_t e = hipMalloc((void**)dst, (n > 0 ? n : 1) * sizeof(T));
+  if (e == hipSuccess && n > 0) e = hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice);
+  return e;
+}
+template <typename T>
+static inline hipError_t upload(T** dst, const std::vector<T>& v) {
+  return upload(dst, v.data(), v.size());
 }
 
 #endif  // __HIPCC__

@@ -20,8 +20,6 @@
 
 namespace isd {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
 constexpr int kTaps = 5;
 constexpr int kCK = 32;          // input channels staged per chunk
 constexpr int kMaxZones = 64;

@@ -49,14 +49,6 @@ constexpr int64_t kCsdChunkBytes = 256LL << 20;                 // Z + means of 
 // another thread sets in between.
 static thread_local int64_t g_csd_chunk_bytes = kCsdChunkBytes;
 
-template <typename S> struct CsdVec;
-template <> struct CsdVec<float> {
-  typedef float V2 __attribute__((ext_vector_type(2)));
-};
-template <> struct CsdVec<double> {
-  typedef double V2 __attribute__((ext_vector_type(2)));
-};
-
 // Z [K][nt][2 S][C] of this chunk's nt trials
 template <typename S>
 __global__ __launch_bounds__(kPsdThreads, 2) void csd_spectra_kernel(const S* __restrict__ x, const S* __restrict__ tab,
@@ -215,7 +207,7 @@ __global__ __launch_bounds__(kPsdThreads) void csd_product_kernel(const S* __res
                                                                   double N, int use_scale, int partial) {
   using O = PsdOps<S>;
   using Acc = typename O::Acc;
-  using V2 = typename CsdVec<S>::V2;
+  using V2 = S __attribute__((ext_vector_type(2)));              // f32x2 / f64x2: (re, im), one store
   const int lane = threadIdx.x & 63, g = lane >> 4, c16 = lane & 15;
   const int64_t w = (int64_t)blockIdx.x * (kPsdThreads / 64) + (threadIdx.x >> 6);
   if (w >= waves) return;                                        // wave-uniform
@@ -261,7 +253,7 @@ __global__ __launch_bounds__(kPsdThreads) void csd_product_kernel(const S* __res
   const int y = c16;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    const int xr = O::row(lane, r);
+    const int xr = O::lane_row(lane, r);
     if (I != J) {
       if (16 * I + xr < C && in_j) {
         V2 v = {re[r] * sc, imn[r] * sc};
@@ -351,13 +343,13 @@ int csd_launch(const isd_psd_plan* p, const S* x, S* out, int64_t n, int64_t C, 
                int unit_modulus, void* work, void* stream, const char* who) {
   ISD_CHECK_ARG(p, "%s: null plan", who);
   ISD_CHECK_ARG(n >= 0, "%s: n=%lld", who, (long long)n);
-  PSD_UNSUPPORTED(C >= 1 && C <= kCsdMaxChannels, "%s: C=%lld (need 1 <= C <= %d)", who, (long long)C,
-                  kCsdMaxChannels);
+  ISD_CHECK_SUPPORTED(C >= 1 && C <= kCsdMaxChannels, "%s: C=%lld (need 1 <= C <= %d)", who, (long long)C,
+                      kCsdMaxChannels);
   if (n == 0) return ISD_OK;
-  PSD_UNSUPPORTED(T >= p->n_per_seg, "%s: T=%lld is shorter than n_per_seg=%d", who, (long long)T, p->n_per_seg);
+  ISD_CHECK_SUPPORTED(T >= p->n_per_seg, "%s: T=%lld is shorter than n_per_seg=%d", who, (long long)T, p->n_per_seg);
   const bool f64 = sizeof(S) == 8;
   const CsdLayout L = csd_layout(p, n, C, T, over_trials, f64);
-  PSD_UNSUPPORTED(L.S_ <= (1LL << 28), "%s: %lld segments (at most 2^28)", who, (long long)L.S_);
+  ISD_CHECK_SUPPORTED(L.S_ <= (1LL << 28), "%s: %lld segments (at most 2^28)", who, (long long)L.S_);
   ISD_CHECK_ARG(x && out && work, "%s: null argument", who);
   hipStream_t st = (hipStream_t)stream;
   const S* tab = f64 ? (const S*)p->d_tab64 : (const S*)p->d_tab32;
@@ -391,7 +383,7 @@ int csd_launch(const isd_psd_plan* p, const S* x, S* out, int64_t n, int64_t C, 
     int64_t Zs = base >= kPsdSplitBelow ? 1 : std::min<int64_t>(L.S_, cdiv(kPsdSplitTarget, base));
     const int64_t seg_per_z = cdiv(L.S_, Zs);
     Zs = cdiv(L.S_, seg_per_z);
-    PSD_UNSUPPORTED(Zs <= 65535, "%s: %lld segment ranges", who, (long long)Zs);
+    ISD_CHECK_SUPPORTED(Zs <= 65535, "%s: %lld segment ranges", who, (long long)Zs);
     hipLaunchKernelGGL((csd_spectra_kernel<S>), dim3((unsigned)row_tiles, (unsigned)bin_tiles, (unsigned)Zs),
                        dim3(kPsdThreads), 0, st, xc, tab, p->remove_dc ? (const double*)means : nullptr, Z, rows, Ci,
                        nt, T, L.S_, (int)seg_per_z, p->n_per_seg, p->step, np, K, p->Kp, unit_modulus);

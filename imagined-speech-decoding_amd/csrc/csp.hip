@@ -18,25 +18,12 @@
 
 namespace isd {
 
-typedef float cf4 __attribute__((ext_vector_type(4)));
-typedef double cd4 __attribute__((ext_vector_type(4)));
-
 template <typename S> struct CovOps;
-template <> struct CovOps<float> {
-  using Acc = cf4;
+template <> struct CovOps<float> : Mfma16<float> {
   static constexpr int KC = 64;                                 // time steps staged per pass
-  static __device__ __forceinline__ Acc mma(float a, float b, Acc c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ int row(int lane, int r) { return 4 * (lane >> 4) + r; }
 };
-template <> struct CovOps<double> {
-  using Acc = cd4;
+template <> struct CovOps<double> : Mfma16<double> {
   static constexpr int KC = 32;
-  static __device__ __forceinline__ Acc mma(double a, double b, Acc c) {
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ int row(int lane, int r) { return (lane >> 4) + 4 * r; }   // the f64 C/D map
 };
 
 constexpr int kCovPad = 4;                                      // LDS row skew (elements)
@@ -89,7 +76,7 @@ __global__ __launch_bounds__(64 * kCovWaves) void trial_cov_kernel(const S* __re
     if (q * kCovWaves + wave < U) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int a = ti[q] * 16 + O::row(lane, r), b = tj[q] * 16 + (lane & 15);
+        const int a = ti[q] * 16 + O::lane_row(lane, r), b = tj[q] * 16 + (lane & 15);
         if (a <= b && b < C) {                                   // a <= b < C; the lower triangle is the mirror
           const S v = acc[q][r] / den;
           ci[a * C + b] = v;

@@ -170,29 +170,19 @@ extern "C" int isd_fir_plan_create(isd_fir_plan** out, int n_taps, const double*
   ISD_CHECK_ARG(n_taps >= 1 && (n_taps & 1) && n_taps <= 65535, "isd_fir_plan_create: n_taps=%d (need an odd count <= 65535)", n_taps);
   for (int k = 0; k < n_taps / 2; ++k)
     ISD_CHECK_ARG(taps[k] == taps[n_taps - 1 - k], "isd_fir_plan_create: taps are not symmetric (zero-phase needs a linear-phase type-I filter)");
-  int n_dev = 0;
-  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) {
-    set_error("isd_fir_plan_create: no HIP device");
-    return ISD_ERR_NO_DEVICE;
-  }
+  if (int rc = require_device("isd_fir_plan_create")) return rc;
   isd_fir_plan* p = new isd_fir_plan();
   p->n_taps = n_taps;
   p->n_blk = (n_taps + kFirR - 1) / kFirR;
   const int n = (p->n_blk + 3) * kFirR;                         // the kernel prefetches up to 3 blocks past the end
-  double* hd = new double[n]();
-  float* hf = new float[2 * n]();                                 // every tap twice: (h, h)
+  std::vector<double> hd(n, 0.0);
+  std::vector<float> hf(2 * n, 0.f);                              // every tap twice: (h, h)
   for (int k = 0; k < n_taps; ++k) { hd[k] = taps[k]; hf[2 * k] = hf[2 * k + 1] = (float)taps[k]; }
-  hipError_t e = hipMalloc(&p->d_hd, n * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc(&p->d_hf, 2 * n * sizeof(float));
-  if (e == hipSuccess) e = hipMemcpy(p->d_hd, hd, n * sizeof(double), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(p->d_hf, hf, 2 * n * sizeof(float), hipMemcpyHostToDevice);
-  delete[] hd;
-  delete[] hf;
+  hipError_t e = upload(&p->d_hd, hd);
+  if (e == hipSuccess) e = upload(&p->d_hf, hf);
   if (e != hipSuccess) {
     set_error("isd_fir_plan_create: %s", hipGetErrorString(e));
-    if (p->d_hd) (void)hipFree(p->d_hd);
-    if (p->d_hf) (void)hipFree(p->d_hf);
-    delete p;
+    isd_fir_plan_destroy(p);
     return ISD_ERR_HIP;
   }
   *out = p;

@@ -27,32 +27,14 @@
 
 namespace isd {
 
-typedef float if4 __attribute__((ext_vector_type(4)));
-typedef double id4 __attribute__((ext_vector_type(4)));
-typedef double id2 __attribute__((ext_vector_type(2)));
-
 template <typename S> struct IcaOps;
-template <> struct IcaOps<float> {
-  using Acc = if4;
-  using Vec = if4;                                              // 16 bytes of one LDS row
+template <> struct IcaOps<float> : Mfma16<float> {
   static constexpr int KC = 64;                                 // time steps staged per unit
-  static constexpr int VEC = 4;
   static constexpr int LDX = KC + 4, LDG = KC + 8, PADM = 8;    // row strides (elements): chunk, G, U / M (Cp + PADM)
-  static __device__ __forceinline__ Acc mma(float a, float b, Acc c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ int row(int lane, int r) { return 4 * (lane >> 4) + r; }
 };
-template <> struct IcaOps<double> {
-  using Acc = id4;
-  using Vec = id2;
+template <> struct IcaOps<double> : Mfma16<double> {
   static constexpr int KC = 32;
-  static constexpr int VEC = 2;
   static constexpr int LDX = KC + 4, LDG = KC + 4, PADM = 4;
-  static __device__ __forceinline__ Acc mma(double a, double b, Acc c) {
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ int row(int lane, int r) { return (lane >> 4) + 4 * r; }   // the f64 C/D map
 };
 
 constexpr int kIcaWaves = 4;
@@ -150,7 +132,7 @@ __global__ __launch_bounds__(kIcaThreads) void ica_step_kernel(const S* __restri
     const int u = a * kIcaWaves + wave, mi = u / TT;             // tile u of the projection: rows mi, time tile u % TT
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int row = mi * 16 + O::row(lane, r);
+      const int row = mi * 16 + O::lane_row(lane, r);
       bq[a][r] = (u < nA && row < m) ? b[row] : (S)0;
     }
     sacc[a] = (Acc)(0);
@@ -179,7 +161,7 @@ __global__ __launch_bounds__(kIcaThreads) void ica_step_kernel(const S* __restri
         const bool live = t0 + tj * 16 + (lane & 15) < T;        // a padded time step adds nothing
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const int row = mi * 16 + O::row(lane, r);
+          const int row = mi * 16 + O::lane_row(lane, r);
           const S t = tanh(y[r] - bq[a][r]);                     // saturates to +-1: 1 - t*t is then 0, never NaN
           const S g = (live && row < m) ? t : (S)0;
           sacc[a][r] += g;
@@ -214,7 +196,7 @@ __global__ __launch_bounds__(kIcaThreads) void ica_step_kernel(const S* __restri
       const int mi = u / nt, cj = u % nt;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int row = mi * 16 + O::row(lane, r), col = cj * 16 + (lane & 15);
+        const int row = mi * 16 + O::lane_row(lane, r), col = cj * 16 + (lane & 15);
         if (row < m && col < C) wp[row * C + col] = pacc[q][r];
       }
     }
@@ -229,8 +211,8 @@ __global__ __launch_bounds__(kIcaThreads) void ica_step_kernel(const S* __restri
       for (int r = 0; r < 4; ++r) {
         const S sv = ica_row_sum16(sacc[a][r]), qv = ica_row_sum16(qacc[a][r]);
         if ((lane & 15) == 0) {
-          red[u * 16 + O::row(lane, r)] = sv;
-          red[(nA + u) * 16 + O::row(lane, r)] = qv;
+          red[u * 16 + O::lane_row(lane, r)] = sv;
+          red[(nA + u) * 16 + O::lane_row(lane, r)] = qv;
         }
       }
     }
@@ -285,7 +267,7 @@ __global__ __launch_bounds__(kIcaThreads) void spatial_apply_kernel(const S* __r
     const int u = a * kIcaWaves + wave;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int row = row0 + (u / TT) * 16 + O::row(lane, r);
+      const int row = row0 + (u / TT) * 16 + O::lane_row(lane, r);
       bq[a][r] = (bias != nullptr && u < nA && row < R) ? bias[row] : (S)0;
     }
   }
@@ -311,7 +293,7 @@ __global__ __launch_bounds__(kIcaThreads) void spatial_apply_kernel(const S* __r
         const Acc y = ica_project<S>(ms, xs, mi, tj, Cp, ldm, lane);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const int row = row0 + mi * 16 + O::row(lane, r);
+          const int row = row0 + mi * 16 + O::lane_row(lane, r);
           if (row < R && t < T) oi[(int64_t)row * T + t] = y[r] + bq[a][r];  // never past a row, never past R rows
         }
       }

@@ -138,7 +138,7 @@ __global__ __launch_bounds__(kPsdThreads, 2) void psd_welch_kernel(const S* __re
           for (int r = 0; r < 4; ++r) {
             const S p = re[b][r] * re[b][r] + im[b][r] * im[b][r];
             if (per_segment) {
-              const int64_t row = row0 + wave * 16 + O::row(lane, r);
+              const int64_t row = row0 + wave * 16 + O::lane_row(lane, r);
               if (row < rows && bin < K) out[(row * K + bin) * S_ + s] = p * scale[bin];
             } else {
               pw[b][r] += p;                                     // segment order, one thread: no reduction
@@ -160,7 +160,7 @@ __global__ __launch_bounds__(kPsdThreads, 2) void psd_welch_kernel(const S* __re
       const S sc = (partial || bin >= K) ? (S)1 : scale[bin] / (S)S_;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int64_t row = row0 + wave * 16 + O::row(lane, r);
+        const int64_t row = row0 + wave * 16 + O::lane_row(lane, r);
         if (row < rows && bin < K) o[row * K + bin] = pw[b][r] * sc;
       }
     }
@@ -201,25 +201,18 @@ PsdSplit psd_split(const isd_psd_plan* p, int64_t rows, int64_t S_) {
   return sp;
 }
 
-template <typename T_>
-hipError_t psd_upload(T_** dst, const std::vector<T_>& v) {
-  hipError_t e = hipMalloc((void**)dst, v.size() * sizeof(T_));
-  if (e == hipSuccess) e = hipMemcpy(*dst, v.data(), v.size() * sizeof(T_), hipMemcpyHostToDevice);
-  return e;
-}
-
 template <typename S>
 int psd_launch(const isd_psd_plan* p, const S* x, S* out, int64_t rows, int64_t T, int per_segment, void* work,
                void* stream, const char* who) {
   ISD_CHECK_ARG(p, "%s: null plan", who);
   ISD_CHECK_ARG(rows >= 0, "%s: rows=%lld", who, (long long)rows);
   if (rows == 0) return ISD_OK;
-  PSD_UNSUPPORTED(T >= p->n_per_seg, "%s: T=%lld is shorter than n_per_seg=%d", who, (long long)T, p->n_per_seg);
+  ISD_CHECK_SUPPORTED(T >= p->n_per_seg, "%s: T=%lld is shorter than n_per_seg=%d", who, (long long)T, p->n_per_seg);
   const int64_t S_ = psd_segments(p, T);
-  PSD_UNSUPPORTED(S_ <= 2147483647LL, "%s: %lld segments (at most 2^31 - 1)", who, (long long)S_);
+  ISD_CHECK_SUPPORTED(S_ <= 2147483647LL, "%s: %lld segments (at most 2^31 - 1)", who, (long long)S_);
   ISD_CHECK_ARG(x && out && work, "%s: null argument", who);
   const PsdSplit sp = psd_split(p, rows, S_);
-  PSD_UNSUPPORTED(sp.row_tiles <= 2147483647LL, "%s: rows=%lld", who, (long long)rows);
+  ISD_CHECK_SUPPORTED(sp.row_tiles <= 2147483647LL, "%s: rows=%lld", who, (long long)rows);
   hipStream_t st = (hipStream_t)stream;
   const bool f64 = sizeof(S) == 8;
   const S* tab = f64 ? (const S*)p->d_tab64 : (const S*)p->d_tab32;
@@ -255,26 +248,23 @@ int psd_launch(const isd_psd_plan* p, const S* x, S* out, int64_t rows, int64_t 
 extern "C" int isd_psd_plan_create(isd_psd_plan** out, int n_fft, int n_per_seg, int n_overlap, int k_lo, int k_hi,
                                    const double* window, double sfreq, int remove_dc) {
   ISD_CHECK_ARG(out && window, "isd_psd_plan_create: null argument");
-  PSD_UNSUPPORTED(n_fft >= 2 && n_fft <= kPsdMaxFft, "isd_psd_plan_create: n_fft=%d (need 2 <= n_fft <= %d)", n_fft,
-                  kPsdMaxFft);
-  PSD_UNSUPPORTED(n_per_seg >= 1 && n_per_seg <= n_fft,
-                  "isd_psd_plan_create: n_per_seg=%d (need 1 <= n_per_seg <= n_fft=%d)", n_per_seg, n_fft);
-  PSD_UNSUPPORTED(n_overlap >= 0 && n_overlap < n_per_seg,
-                  "isd_psd_plan_create: n_overlap=%d (need 0 <= n_overlap < n_per_seg=%d)", n_overlap, n_per_seg);
-  PSD_UNSUPPORTED(k_lo >= 0 && k_lo <= k_hi && k_hi <= n_fft / 2,
-                  "isd_psd_plan_create: bins %d..%d (need 0 <= k_lo <= k_hi <= n_fft/2 = %d)", k_lo, k_hi, n_fft / 2);
+  ISD_CHECK_SUPPORTED(n_fft >= 2 && n_fft <= kPsdMaxFft, "isd_psd_plan_create: n_fft=%d (need 2 <= n_fft <= %d)", n_fft,
+                      kPsdMaxFft);
+  ISD_CHECK_SUPPORTED(n_per_seg >= 1 && n_per_seg <= n_fft,
+                      "isd_psd_plan_create: n_per_seg=%d (need 1 <= n_per_seg <= n_fft=%d)", n_per_seg, n_fft);
+  ISD_CHECK_SUPPORTED(n_overlap >= 0 && n_overlap < n_per_seg,
+                      "isd_psd_plan_create: n_overlap=%d (need 0 <= n_overlap < n_per_seg=%d)", n_overlap, n_per_seg);
+  ISD_CHECK_SUPPORTED(k_lo >= 0 && k_lo <= k_hi && k_hi <= n_fft / 2,
+                      "isd_psd_plan_create: bins %d..%d (need 0 <= k_lo <= k_hi <= n_fft/2 = %d)", k_lo, k_hi,
+                      n_fft / 2);
   double sw2 = 0.0;
   for (int t = 0; t < n_per_seg; ++t) {
-    PSD_UNSUPPORTED(std::isfinite(window[t]), "isd_psd_plan_create: window[%d] is not finite", t);
+    ISD_CHECK_SUPPORTED(std::isfinite(window[t]), "isd_psd_plan_create: window[%d] is not finite", t);
     sw2 += window[t] * window[t];
   }
-  PSD_UNSUPPORTED(std::isfinite(sfreq) && sfreq > 0 && sw2 > 0,
-                  "isd_psd_plan_create: sfreq=%g, sum of squared taps %g (both must be positive)", sfreq, sw2);
-  int n_dev = 0;
-  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) {
-    set_error("isd_psd_plan_create: no HIP device");
-    return ISD_ERR_NO_DEVICE;
-  }
+  ISD_CHECK_SUPPORTED(std::isfinite(sfreq) && sfreq > 0 && sw2 > 0,
+                      "isd_psd_plan_create: sfreq=%g, sum of squared taps %g (both must be positive)", sfreq, sw2);
+  if (int rc = require_device("isd_psd_plan_create")) return rc;
   isd_psd_plan* p = new isd_psd_plan();
   p->n_fft = n_fft;
   p->n_per_seg = n_per_seg;
@@ -310,10 +300,10 @@ extern "C" int isd_psd_plan_create(isd_psd_plan** out, int n_fft, int n_per_seg,
       t32[((size_t)p->Kp + i) * p->np32 + t] = (float)ws;
     }
   }
-  hipError_t e = psd_upload(&p->d_tab64, t64);
-  if (e == hipSuccess) e = psd_upload(&p->d_tab32, t32);
-  if (e == hipSuccess) e = psd_upload(&p->d_scale64, sc64);
-  if (e == hipSuccess) e = psd_upload(&p->d_scale32, sc32);
+  hipError_t e = upload(&p->d_tab64, t64);
+  if (e == hipSuccess) e = upload(&p->d_tab32, t32);
+  if (e == hipSuccess) e = upload(&p->d_scale64, sc64);
+  if (e == hipSuccess) e = upload(&p->d_scale32, sc32);
   if (e != hipSuccess) {
     set_error("isd_psd_plan_create: %s", hipGetErrorString(e));
     isd_psd_plan_destroy(p);

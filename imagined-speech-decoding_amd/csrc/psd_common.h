@@ -14,28 +14,12 @@ struct isd_psd_plan {
 
 namespace isd {
 
-typedef float pf4 __attribute__((ext_vector_type(4)));
-typedef double pd4 __attribute__((ext_vector_type(4)));
-typedef double pd2 __attribute__((ext_vector_type(2)));
-
-template <typename S> struct PsdOps;
-template <> struct PsdOps<float> {
-  using Acc = pf4;
-  using Vec = pf4;                                              // 16 bytes of one LDS row
-  static constexpr int KC = 64, VEC = 4, LD = KC + 4;
-  static __device__ __forceinline__ Acc mma(float a, float b, Acc c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ int row(int lane, int r) { return 4 * (lane >> 4) + r; }
+template <typename S> struct PsdOps;                            // chunk length and LDS row stride (elements)
+template <> struct PsdOps<float> : Mfma16<float> {
+  static constexpr int KC = 64, LD = KC + 4;
 };
-template <> struct PsdOps<double> {
-  using Acc = pd4;
-  using Vec = pd2;
-  static constexpr int KC = 32, VEC = 2, LD = KC + 4;
-  static __device__ __forceinline__ Acc mma(double a, double b, Acc c) {
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ int row(int lane, int r) { return (lane >> 4) + 4 * r; }   // the f64 C/D map
+template <> struct PsdOps<double> : Mfma16<double> {
+  static constexpr int KC = 32, LD = KC + 4;
 };
 
 constexpr int kPsdThreads = 256;
@@ -126,14 +110,6 @@ __global__ __launch_bounds__(kPsdThreads) void psd_mean_kernel(const S* __restri
 
 // ------------------------------------------------------------------ host side
 namespace isd {
-
-#define PSD_UNSUPPORTED(cond, ...)   \
-  do {                               \
-    if (!(cond)) {                   \
-      set_error(__VA_ARGS__);        \
-      return ISD_ERR_UNSUPPORTED;    \
-    }                                \
-  } while (0)
 
 static inline int64_t psd_segments(const isd_psd_plan* p, int64_t T) {
   return T < p->n_per_seg ? 0 : (T - p->n_per_seg) / p->step + 1;

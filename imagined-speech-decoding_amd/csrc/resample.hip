@@ -49,27 +49,12 @@ constexpr int kRsBatch = 8;                               // staging passes (of 
 constexpr int64_t kRsTableBudget = (int64_t)16 << 20;      // bytes of device tables (fp32 + fp64) a plan may hold
 enum { kRsConstant = 0, kRsEdge = 1, kRsReflect = 2, kRsSymmetric = 3, kRsLine = 4 };
 
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-
 template <typename S> struct RsOps;
-template <> struct RsOps<float> {
-  using Acc = f32x4;
-  using Vec = f32x4;                                      // 16 bytes of samples
+template <> struct RsOps<float> : Mfma16<float> {
   static constexpr int KC = 64, LD = KC + 4;               // LD = 4 mod 64 dwords: the 64 A reads hit 64 banks
-  static __device__ __forceinline__ Acc mma(float a, float b, Acc c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ int out_row(int lane, int reg) { return 4 * (lane >> 4) + reg; }
 };
-template <> struct RsOps<double> {
-  using Acc = f64x4;
-  using Vec = f64x2;
+template <> struct RsOps<double> : Mfma16<double> {
   static constexpr int KC = 32, LD = KC + 2;               // 2 LD = 4 mod 64 dwords
-  static __device__ __forceinline__ Acc mma(double a, double b, Acc c) {
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ int out_row(int lane, int reg) { return (lane >> 4) + 4 * reg; }
 };
 
 // sample m of the row (minus bg) extended by `mode`; only indices inside 0 .. T-1 are read
@@ -105,7 +90,7 @@ __global__ __launch_bounds__(64) void resample_kernel(const S* __restrict__ x, S
   using O = RsOps<S>;
   using Acc = typename O::Acc;
   using Vec = typename O::Vec;
-  constexpr int KC = O::KC, LD = O::LD, VEC = 16 / sizeof(S), STEPS = KC / 4;
+  constexpr int KC = O::KC, LD = O::LD, VEC = O::VEC, STEPS = KC / 4;
   __shared__ __attribute__((aligned(16))) S xs[kRsRows * LD];
   const int lane = threadIdx.x;
   // workgroups are dealt to the eight XCDs in turn: renumber so that an XCD's workgroups are consecutive blocks of
@@ -203,7 +188,7 @@ __global__ __launch_bounds__(64) void resample_kernel(const S* __restrict__ x, S
   for (int g = 0; g < 4; ++g) {
 #pragma unroll
     for (int reg = 0; reg < 4; ++reg) {
-      const int r = 16 * g + O::out_row(lane, reg);
+      const int r = 16 * g + O::lane_row(lane, reg);
       if (r < n_rows) {
         const S v = acc[g][reg];
         y[(row0 + r) * n_out + n] = has_bg ? (S)((double)v + background[row0 + r]) : v;
@@ -220,22 +205,14 @@ static int64_t gcd64(int64_t a, int64_t b) { while (b) { const int64_t t = a % b
 
 using namespace isd;
 
-#define RS_SUPPORTED(cond, ...)      \
-  do {                               \
-    if (!(cond)) {                   \
-      set_error(__VA_ARGS__);        \
-      return ISD_ERR_UNSUPPORTED;    \
-    }                                \
-  } while (0)
-
 extern "C" int isd_resample_plan_create(isd_resample_plan** out, int up, int down, int n_taps, const double* taps,
                                         int half_len) {
   ISD_CHECK_ARG(out && taps, "isd_resample_plan_create: null argument");
   ISD_CHECK_ARG(up >= 1 && down >= 1 && n_taps >= 1, "isd_resample_plan_create: up=%d down=%d n_taps=%d (need >= 1)", up, down, n_taps);
   ISD_CHECK_ARG(gcd64(up, down) == 1, "isd_resample_plan_create: up=%d down=%d are not reduced", up, down);
   ISD_CHECK_ARG(half_len >= 0 && half_len < n_taps, "isd_resample_plan_create: half_len=%d outside the %d taps", half_len, n_taps);
-  RS_SUPPORTED(up <= ISD_RESAMPLE_MAX_RATE && down <= ISD_RESAMPLE_MAX_RATE, "isd_resample_plan_create: up=%d down=%d (at most %d is provided)", up, down, ISD_RESAMPLE_MAX_RATE);
-  RS_SUPPORTED(n_taps <= ISD_RESAMPLE_MAX_TAPS, "isd_resample_plan_create: %d taps (at most %d are provided)", n_taps, ISD_RESAMPLE_MAX_TAPS);
+  ISD_CHECK_SUPPORTED(up <= ISD_RESAMPLE_MAX_RATE && down <= ISD_RESAMPLE_MAX_RATE, "isd_resample_plan_create: up=%d down=%d (at most %d is provided)", up, down, ISD_RESAMPLE_MAX_RATE);
+  ISD_CHECK_SUPPORTED(n_taps <= ISD_RESAMPLE_MAX_TAPS, "isd_resample_plan_create: %d taps (at most %d are provided)", n_taps, ISD_RESAMPLE_MAX_TAPS);
   const int L = n_taps;
   const int step = (int)gcd64(up, (int64_t)16 * down), n_phase = up / step;
   std::vector<int> c0(n_phase);
@@ -248,12 +225,8 @@ extern "C" int isd_resample_plan_create(isd_resample_plan** out, int up, int dow
   }
   K = (K + 3) / 4 * 4;
   const int64_t n_el = (int64_t)n_phase * K * 16;
-  RS_SUPPORTED(n_el * (int64_t)(sizeof(float) + sizeof(double)) <= kRsTableBudget, "isd_resample_plan_create: the phase tables need %lld bytes (budget %lld)", (long long)(n_el * 12), (long long)kRsTableBudget);
-  int n_dev = 0;
-  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) {
-    set_error("isd_resample_plan_create: no HIP device");
-    return ISD_ERR_NO_DEVICE;
-  }
+  ISD_CHECK_SUPPORTED(n_el * (int64_t)(sizeof(float) + sizeof(double)) <= kRsTableBudget, "isd_resample_plan_create: the phase tables need %lld bytes (budget %lld)", (long long)(n_el * 12), (long long)kRsTableBudget);
+  if (int rc = require_device("isd_resample_plan_create")) return rc;
   std::vector<double> bd((size_t)n_el, 0.0);
   std::vector<float> bf((size_t)n_el, 0.f);
   for (int i = 0; i < n_phase; ++i)
@@ -269,12 +242,9 @@ extern "C" int isd_resample_plan_create(isd_resample_plan** out, int up, int dow
   isd_resample_plan* p = new isd_resample_plan();
   p->up = up; p->down = down; p->n_taps = n_taps; p->half_len = half_len;
   p->n_phase = n_phase; p->phase_step = step; p->K = (int)K;
-  hipError_t e = hipMalloc(&p->d_c0, n_phase * sizeof(int));
-  if (e == hipSuccess) e = hipMalloc(&p->d_bf, n_el * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(&p->d_bd, n_el * sizeof(double));
-  if (e == hipSuccess) e = hipMemcpy(p->d_c0, c0.data(), n_phase * sizeof(int), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(p->d_bf, bf.data(), n_el * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(p->d_bd, bd.data(), n_el * sizeof(double), hipMemcpyHostToDevice);
+  hipError_t e = upload(&p->d_c0, c0);
+  if (e == hipSuccess) e = upload(&p->d_bf, bf);
+  if (e == hipSuccess) e = upload(&p->d_bd, bd);
   if (e != hipSuccess) {
     set_error("isd_resample_plan_create: %s", hipGetErrorString(e));
     isd_resample_plan_destroy(p);
@@ -307,7 +277,7 @@ static int resample_launch(const isd_resample_plan* p, const S* x, S* y, int64_t
   ISD_CHECK_ARG(T >= 2 || (mode != kRsReflect && mode != kRsLine), "isd_resample_poly: mode %d needs T >= 2", mode);
   ISD_CHECK_ARG((const void*)x != (const void*)y, "isd_resample_poly: in-place resampling is not supported");
   const int64_t n_out = isd_resample_out_len(p, T);
-  RS_SUPPORTED(n_out <= INT32_MAX, "isd_resample_poly: %lld output samples per row (need < 2^31)", (long long)n_out);
+  ISD_CHECK_SUPPORTED(n_out <= INT32_MAX, "isd_resample_poly: %lld output samples per row (need < 2^31)", (long long)n_out);
   if (rows == 0) return ISD_OK;
   const int64_t n_blocks = cdiv(n_out, 16), slabs = cdiv(rows, kRsRows);
   // one workgroup per (slab, block) on grid.x; a launch takes as many whole slabs as fit under 2^31 - 1 workgroups

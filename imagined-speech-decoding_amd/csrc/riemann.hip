@@ -33,8 +33,6 @@
 
 namespace isd {
 
-typedef double rd4 __attribute__((ext_vector_type(4)));
-
 constexpr int kSpdMaxC = 128;
 constexpr int kSpdMaxSweeps = 30;
 constexpr int kCongWaves = 4;
@@ -56,6 +54,7 @@ __global__ __launch_bounds__(64 * kCongWaves) void spd_congruence_kernel(const S
                                                                          const double* __restrict__ W,
                                                                          const int* __restrict__ widx,
                                                                          double* __restrict__ out, int C, int K) {
+  using O = Mfma16<double>;                                      // both products run in fp64 whatever S is
   extern __shared__ __attribute__((aligned(16))) unsigned char cong_smem[];
   double* ys = reinterpret_cast<double*>(cong_smem);             // [Cp][ldy]: Y = cov W^T, zero beyond C
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -75,9 +74,9 @@ __global__ __launch_bounds__(64 * kCongWaves) void spd_congruence_kernel(const S
   for (int ti = wave; ti < nt; ti += kCongWaves) {
     const int ra = ti * 16 + lr;
     const S* pa = ci + (int64_t)min(ra, C - 1) * C;              // clamped: never past C rows
-    rd4 acc[NT];
+    f64x4 acc[NT];
 #pragma unroll
-    for (int tj = 0; tj < NT; ++tj) acc[tj] = (rd4)(0);
+    for (int tj = 0; tj < NT; ++tj) acc[tj] = (f64x4)(0);
     // Sixteen channels (four k steps) per turn: all their loads are issued first, unconditionally at clamped
     // addresses, and zeroed by selects afterwards.  Behind a test each load would be waited for by itself; spd_pin
     // keeps the compiler from putting them back there.
@@ -103,14 +102,14 @@ __global__ __launch_bounds__(64 * kCongWaves) void spd_congruence_kernel(const S
 #pragma unroll
         for (int tj = 0; tj < NT; ++tj) {
           const double b = (tj * 16 + lr < C && inc) ? bv[s][tj] : 0.0;
-          acc[tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[tj], 0, 0, 0);
+          acc[tj] = O::mma(a, b, acc[tj]);
         }
       }
     }
 #pragma unroll
     for (int tj = 0; tj < NT; ++tj)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) ys[(ti * 16 + lk + 4 * r) * ldy + tj * 16 + lr] = acc[tj][r];   // the f64 C/D map
+      for (int r = 0; r < 4; ++r) ys[(ti * 16 + O::row(lk, r)) * ldy + tj * 16 + lr] = acc[tj][r];
   }
   __syncthreads();
 
@@ -122,9 +121,9 @@ __global__ __launch_bounds__(64 * kCongWaves) void spd_congruence_kernel(const S
       if (h && ti == pp) break;                                  // the middle row of an odd nt, once
       const int ra = ti * 16 + lr;
       const double* pa = wk + (int64_t)min(ra, C - 1) * C;
-      rd4 acc[NT];
+      f64x4 acc[NT];
 #pragma unroll
-      for (int tj = 0; tj < NT; ++tj) acc[tj] = (rd4)(0);
+      for (int tj = 0; tj < NT; ++tj) acc[tj] = (f64x4)(0);
       for (int c0 = 0; c0 < Cp; c0 += 16) {
         double av[4];
 #pragma unroll
@@ -138,7 +137,7 @@ __global__ __launch_bounds__(64 * kCongWaves) void spd_congruence_kernel(const S
           const double* pb = ys + c * ldy + lr;
 #pragma unroll
           for (int tj = 0; tj < NT; ++tj)
-            if (tj >= ti) acc[tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, pb[tj * 16], acc[tj], 0, 0, 0);
+            if (tj >= ti) acc[tj] = O::mma(a, pb[tj * 16], acc[tj]);
         }
       }
 #pragma unroll
@@ -146,7 +145,7 @@ __global__ __launch_bounds__(64 * kCongWaves) void spd_congruence_kernel(const S
         if (tj >= ti) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const int a = ti * 16 + lk + 4 * r, b = tj * 16 + lr;
+            const int a = ti * 16 + O::row(lk, r), b = tj * 16 + lr;
             if (a <= b && b < C) {                               // a <= b < C; the lower triangle is the mirror
               oi[a * C + b] = acc[tj][r];
               oi[b * C + a] = acc[tj][r];

@@ -264,22 +264,12 @@ extern "C" int isd_stft_plan_create(isd_stft_plan** out, int T, int nperseg, int
     }
   }
   p->d_win = nullptr; p->d_tw = nullptr; p->d_dft = nullptr; p->d_blk = nullptr; p->d_sym = nullptr;
-  hipError_t e = hipMalloc(&p->d_win, sizeof(float) * nperseg);
-  if (e == hipSuccess) e = hipMalloc(&p->d_tw, sizeof(float2) * (nperseg / 2));
-  if (e == hipSuccess) e = hipMemcpy(p->d_win, win.data(), sizeof(float) * nperseg, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(p->d_tw, tw.data(), sizeof(float2) * (nperseg / 2), hipMemcpyHostToDevice);
-  if (e == hipSuccess && !dft.empty()) {
-    e = hipMalloc(&p->d_dft, sizeof(float2) * dft.size());
-    if (e == hipSuccess) e = hipMemcpy(p->d_dft, dft.data(), sizeof(float2) * dft.size(), hipMemcpyHostToDevice);
-  }
-  if (e == hipSuccess && !sym.empty()) {
-    e = hipMalloc(&p->d_sym, sizeof(float2) * sym.size());
-    if (e == hipSuccess) e = hipMemcpy(p->d_sym, sym.data(), sizeof(float2) * sym.size(), hipMemcpyHostToDevice);
-  }
-  if (e == hipSuccess && !blk.empty()) {
-    e = hipMalloc(&p->d_blk, sizeof(float2) * blk.size());
-    if (e == hipSuccess) e = hipMemcpy(p->d_blk, blk.data(), sizeof(float2) * blk.size(), hipMemcpyHostToDevice);
-  }
+  hipError_t e = upload(&p->d_win, win);
+  if (e == hipSuccess) e = upload(&p->d_tw, tw);
+  // a table this plan has no use for stays null: the launchers choose their kernel by it
+  if (e == hipSuccess && !dft.empty()) e = upload(&p->d_dft, dft);
+  if (e == hipSuccess && !sym.empty()) e = upload(&p->d_sym, sym);
+  if (e == hipSuccess && !blk.empty()) e = upload(&p->d_blk, blk);
   if (e != hipSuccess) {
     set_error("isd_stft_plan_create: %s", hipGetErrorString(e));
     isd_stft_plan_destroy(p);

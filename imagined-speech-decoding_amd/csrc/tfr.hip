@@ -58,10 +58,6 @@ struct isd_tfr_plan {
 
 namespace isd {
 
-typedef double td4 __attribute__((ext_vector_type(4)));
-typedef double td2 __attribute__((ext_vector_type(2)));
-typedef float tf2 __attribute__((ext_vector_type(2)));
-
 constexpr int kTfrThreads = 256;
 constexpr int kTfrMT = 8;                       // M tiles (of 16 outputs) of an item
 constexpr int kTfrChunk = 16 * kTfrMT;          // outputs of an item
@@ -70,26 +66,6 @@ constexpr int kTfrSpan = 2048;                  // TT * decim stays below this (
 constexpr int kTfrMaxTaps = 4095, kTfrMaxFreqs = 256, kTfrMaxDecim = 128;
 constexpr int kTfrKB = 16;                      // k steps of one B fragment load: K is padded to whole blocks
 constexpr int kTfrTabTail = kTfrKB;             // zero rows behind a table: the prefetch after the last block
-
-template <typename X> struct TfrPair;                             // two results side by side, one store
-template <> struct TfrPair<float> { using type = tf2; };
-template <> struct TfrPair<double> { using type = td2; };
-
-template <typename S> struct TfrOps;
-template <> struct TfrOps<float> {
-  using Acc = f32x4;
-  static __device__ __forceinline__ Acc mma(float a, float b, Acc c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ int row(int q, int r) { return 4 * q + r; }
-};
-template <> struct TfrOps<double> {
-  using Acc = td4;
-  static __device__ __forceinline__ Acc mma(double a, double b, Acc c) {
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ int row(int q, int r) { return q + 4 * r; }          // the f64 C/D map
-};
 
 struct TfrGeo {
   int64_t T, T_out, ntile, CF;        // CF = C (modes 2-4: rows of a trial) or 0
@@ -122,12 +98,12 @@ __global__ __launch_bounds__(kTfrThreads) void tfr_cwt_kernel(const X* __restric
                                                               const int* __restrict__ fmap,
                                                               const int* __restrict__ ntaps,
                                                               const int64_t* __restrict__ poff,
-                                                              const td2* __restrict__ pre,
+                                                              const f64x2* __restrict__ pre,
                                                               const double* __restrict__ means, X* __restrict__ out,
                                                               TfrGeo g) {
-  using O = TfrOps<S>;
+  using O = Mfma16<S>;
   using Acc = typename O::Acc;
-  using Pair = typename TfrPair<X>::type;
+  using Pair = X __attribute__((ext_vector_type(2)));             // two results side by side, one store
   extern __shared__ __attribute__((aligned(16))) unsigned char tfr_lds[];
   S* xs = reinterpret_cast<S*>(tfr_lds);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -184,8 +160,8 @@ __global__ __launch_bounds__(kTfrThreads) void tfr_cwt_kernel(const X* __restric
       // ... and goes back on as mu x (the sum of the taps that met a sample of the row): exact in fp64 from the
       // prefix sums P of the taps.  Away from the row's ends that is the whole sum.
       const int h = f >= 0 ? (ntaps[f] - 1) >> 1 : 0;
-      const td2* P = pre + (f >= 0 ? poff[f] : 0);
-      const td2 whole = f >= 0 ? P[2 * h + 1] : td2{0.0, 0.0};
+      const f64x2* P = pre + (f >= 0 ? poff[f] : 0);
+      const f64x2 whole = f >= 0 ? P[2 * h + 1] : f64x2{0.0, 0.0};
 #pragma unroll
       for (int m = 0; m < kTfrMT; ++m) {
         if (m < nm) {
@@ -199,12 +175,12 @@ __global__ __launch_bounds__(kTfrThreads) void tfr_cwt_kernel(const X* __restric
           for (int e = 0; e < 2; ++e) {
             const int lo = chunk * kTfrChunk + 16 * m + O::row(q, 2 * c + e);
             const bool ok = f >= 0 && lo < n_out;
-            td2 sw = whole;
+            f64x2 sw = whole;
             if (ok) {
               const int64_t td = (o0 + lo) * g.decim;              // < T
               const int64_t after = g.T - 1 - td;
               if (td < h || after < h) {                           // the wavelet hangs over an end of the row
-                const td2 hi = P[h + (int)min((int64_t)h, td) + 1], lw = P[h - (int)min((int64_t)h, after)];
+                const f64x2 hi = P[h + (int)min((int64_t)h, td) + 1], lw = P[h - (int)min((int64_t)h, after)];
                 sw = hi - lw;
               }
             }
@@ -275,14 +251,6 @@ using namespace isd;
 
 namespace {
 
-#define TFR_UNSUPPORTED(cond, ...)   \
-  do {                               \
-    if (!(cond)) {                   \
-      set_error(__VA_ARGS__);        \
-      return ISD_ERR_UNSUPPORTED;    \
-    }                                \
-  } while (0)
-
 int64_t tfr_out_len(const isd_tfr_plan* p, int64_t T) { return T <= 0 ? 0 : (T + p->decim - 1) / p->decim; }
 
 // the tiling: a function of (plan, shape, mode) alone
@@ -311,13 +279,6 @@ TfrGeo tfr_geometry(const isd_tfr_plan* p, int64_t n, int64_t C, int64_t T, int 
   return g;
 }
 
-template <typename T_>
-hipError_t tfr_upload(T_** dst, const std::vector<T_>& v) {
-  hipError_t e = hipMalloc((void**)dst, std::max<size_t>(v.size(), 1) * sizeof(T_));
-  if (e == hipSuccess && !v.empty()) e = hipMemcpy(*dst, v.data(), v.size() * sizeof(T_), hipMemcpyHostToDevice);
-  return e;
-}
-
 template <typename X, typename S, int MODE>
 int tfr_launch_mode(const isd_tfr_plan* p, const X* x, X* out, const double* means, const TfrGeo& g, int64_t rows,
                     hipStream_t st) {
@@ -326,7 +287,7 @@ int tfr_launch_mode(const isd_tfr_plan* p, const X* x, X* out, const double* mea
   const dim3 grid((unsigned)(rows * g.ntile), (unsigned)cdiv(g.G, g.gpw));
   return launch_lds(tfr_cwt_kernel<X, S, MODE>, grid, dim3(kTfrThreads), lds, st, x, tab, (const int*)p->d_gH,
                     (const int*)p->d_gK, (const int64_t*)p->d_goff, (const int*)p->d_fmap, (const int*)p->d_ntaps,
-                    (const int64_t*)p->d_poff, (const td2*)p->d_pre, means, out, g);
+                    (const int64_t*)p->d_poff, (const f64x2*)p->d_pre, means, out, g);
 }
 
 template <typename S>
@@ -341,13 +302,13 @@ int tfr_launch(const isd_tfr_plan* p, const S* x, void* out, int64_t n, int64_t 
   ISD_CHECK_ARG(!(avg && n == 0), "%s: an average over n=0 trials", who);
   if (n == 0 || C == 0 || T == 0) return ISD_OK;
   ISD_CHECK_ARG(x && out && work, "%s: null argument", who);
-  TFR_UNSUPPORTED(n <= 2147483647LL && C <= 2147483647LL, "%s: n=%lld, C=%lld (at most 2^31 - 1 each)", who,
-                  (long long)n, (long long)C);
-  TFR_UNSUPPORTED(T <= (1LL << 40), "%s: T=%lld (at most 2^40)", who, (long long)T);
+  ISD_CHECK_SUPPORTED(n <= 2147483647LL && C <= 2147483647LL, "%s: n=%lld, C=%lld (at most 2^31 - 1 each)", who,
+                      (long long)n, (long long)C);
+  ISD_CHECK_SUPPORTED(T <= (1LL << 40), "%s: T=%lld (at most 2^40)", who, (long long)T);
   TfrGeo g = tfr_geometry(p, n, C, T, mode);
   const int64_t rows = avg ? C : n * C;
-  TFR_UNSUPPORTED(rows <= 2147483647LL / g.ntile, "%s: %lld rows x %lld time tiles (at most 2^31 - 1 workgroups)", who,
-                  (long long)rows, (long long)g.ntile);
+  ISD_CHECK_SUPPORTED(rows <= 2147483647LL / g.ntile, "%s: %lld rows x %lld time tiles (at most 2^31 - 1 workgroups)",
+                      who, (long long)rows, (long long)g.ntile);
   hipStream_t st = (hipStream_t)stream;
   S* o = static_cast<S*>(out);
   double* means = static_cast<double*>(work);                     // [n C]
@@ -377,24 +338,20 @@ int tfr_launch(const isd_tfr_plan* p, const S* x, void* out, int64_t n, int64_t 
 
 extern "C" int isd_tfr_plan_create(isd_tfr_plan** out, int n_freqs, const int* n_taps, const double* taps, int decim) {
   ISD_CHECK_ARG(out && n_taps && taps, "isd_tfr_plan_create: null argument");
-  TFR_UNSUPPORTED(n_freqs >= 1 && n_freqs <= kTfrMaxFreqs, "isd_tfr_plan_create: n_freqs=%d (need 1 <= n_freqs <= %d)",
-                  n_freqs, kTfrMaxFreqs);
-  TFR_UNSUPPORTED(decim >= 1 && decim <= kTfrMaxDecim, "isd_tfr_plan_create: decim=%d (need 1 <= decim <= %d)", decim,
-                  kTfrMaxDecim);
+  ISD_CHECK_SUPPORTED(n_freqs >= 1 && n_freqs <= kTfrMaxFreqs,
+                      "isd_tfr_plan_create: n_freqs=%d (need 1 <= n_freqs <= %d)", n_freqs, kTfrMaxFreqs);
+  ISD_CHECK_SUPPORTED(decim >= 1 && decim <= kTfrMaxDecim, "isd_tfr_plan_create: decim=%d (need 1 <= decim <= %d)",
+                      decim, kTfrMaxDecim);
   int64_t total = 0;
   for (int f = 0; f < n_freqs; ++f) {
-    TFR_UNSUPPORTED(n_taps[f] >= 1 && n_taps[f] <= kTfrMaxTaps && (n_taps[f] & 1),
-                    "isd_tfr_plan_create: n_taps[%d]=%d (need an odd count, 1 <= n_taps <= %d)", f, n_taps[f],
-                    kTfrMaxTaps);
+    ISD_CHECK_SUPPORTED(n_taps[f] >= 1 && n_taps[f] <= kTfrMaxTaps && (n_taps[f] & 1),
+                        "isd_tfr_plan_create: n_taps[%d]=%d (need an odd count, 1 <= n_taps <= %d)", f, n_taps[f],
+                        kTfrMaxTaps);
     total += n_taps[f];
   }
   for (int64_t e = 0; e < 2 * total; ++e)
-    TFR_UNSUPPORTED(std::isfinite(taps[e]), "isd_tfr_plan_create: taps[%lld] is not finite", (long long)e);
-  int n_dev = 0;
-  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) {
-    set_error("isd_tfr_plan_create: no HIP device");
-    return ISD_ERR_NO_DEVICE;
-  }
+    ISD_CHECK_SUPPORTED(std::isfinite(taps[e]), "isd_tfr_plan_create: taps[%lld] is not finite", (long long)e);
+  if (int rc = require_device("isd_tfr_plan_create")) return rc;
   std::vector<int64_t> start(n_freqs);                            // offset of a frequency's taps, in complex elements
   for (int64_t f = 0, s = 0; f < n_freqs; s += n_taps[f], ++f) start[f] = s;
   std::vector<int> order(n_freqs);                                // longest first; equal lengths keep their order
@@ -447,15 +404,15 @@ extern "C" int isd_tfr_plan_create(isd_tfr_plan** out, int n_freqs, const int* n
       }
     }
   }
-  hipError_t e = tfr_upload(&p->d_tab64, t64);
-  if (e == hipSuccess) e = tfr_upload(&p->d_ntaps, nt);
-  if (e == hipSuccess) e = tfr_upload(&p->d_poff, poff);
-  if (e == hipSuccess) e = tfr_upload(&p->d_pre, pre);
-  if (e == hipSuccess) e = tfr_upload(&p->d_tab32, t32);
-  if (e == hipSuccess) e = tfr_upload(&p->d_gH, gH);
-  if (e == hipSuccess) e = tfr_upload(&p->d_gK, gK);
-  if (e == hipSuccess) e = tfr_upload(&p->d_fmap, fmap);
-  if (e == hipSuccess) e = tfr_upload(&p->d_goff, goff);
+  hipError_t e = upload(&p->d_tab64, t64);
+  if (e == hipSuccess) e = upload(&p->d_ntaps, nt);
+  if (e == hipSuccess) e = upload(&p->d_poff, poff);
+  if (e == hipSuccess) e = upload(&p->d_pre, pre);
+  if (e == hipSuccess) e = upload(&p->d_tab32, t32);
+  if (e == hipSuccess) e = upload(&p->d_gH, gH);
+  if (e == hipSuccess) e = upload(&p->d_gK, gK);
+  if (e == hipSuccess) e = upload(&p->d_fmap, fmap);
+  if (e == hipSuccess) e = upload(&p->d_goff, goff);
   if (e != hipSuccess) {
     set_error("isd_tfr_plan_create: %s", hipGetErrorString(e));
     isd_tfr_plan_destroy(p);

@@ -16,7 +16,6 @@ rows: device memory beyond the staged ``X`` and background is ``O(batch_size * C
 accumulator per requested class.  Every class gets a forward pass of its own: the HIP modules' backward kernels work in
 place on what the forward saved and release it, so a graph cannot be walked twice.
 """
-import ctypes as C
 
 import numpy as np
 import torch
@@ -40,17 +39,13 @@ def draw_samples(n, nsamples, n_background, rseed=0):
     return ridx, alpha
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def attr_mix(x, bg, ridx, alpha, out, pair0, n_pairs, S):
     """``isd_attr_mix`` on float32 CUDA ``x [n, E]``, ``bg [M, E]``, int32 ``ridx [n*S]``, float32 ``alpha [n*S]``:
     ``out[q] = bg[r] + alpha[p] (x[p // S] - bg[r])`` for the pairs ``p = pair0 + q``, ``q < n_pairs``."""
     E, M = x.shape[-1], bg.shape[0]
     with torch.cuda.device(x.device):
         _lib.check(_lib.lib().isd_attr_mix(x.data_ptr(), bg.data_ptr(), ridx.data_ptr(), alpha.data_ptr(),
-                                           out.data_ptr(), int(n_pairs), int(pair0), int(S), E, M, _stream()))
+                                           out.data_ptr(), int(n_pairs), int(pair0), int(S), E, M, _lib.stream()))
     return out
 
 
@@ -61,7 +56,7 @@ def attr_accumulate(x, bg, ridx, grad, acc, pair0, n_pairs, S, scale):
     with torch.cuda.device(x.device):
         _lib.check(_lib.lib().isd_attr_accumulate(x.data_ptr(), bg.data_ptr(), ridx.data_ptr(), grad.data_ptr(),
                                                   acc.data_ptr(), int(n_pairs), int(pair0), int(S), E, M, float(scale),
-                                                  _stream()))
+                                                  _lib.stream()))
     return acc
 
 

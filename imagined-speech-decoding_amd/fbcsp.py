@@ -44,7 +44,7 @@ def fb_trial_covariances(x, fb):
     cov = torch.empty(n, fb.n_bands, Cc, Cc, dtype=torch.float32, device=x.device)
     if n:
         with torch.cuda.device(x.device):
-            _lib.check(_lib.lib().isd_fb_trial_cov(fb._h, x.data_ptr(), cov.data_ptr(), n, Cc, T, csp._stream()))
+            _lib.check(_lib.lib().isd_fb_trial_cov(fb._h, x.data_ptr(), cov.data_ptr(), n, Cc, T, _lib.stream()))
     return cov
 
 
@@ -64,7 +64,7 @@ def fb_csp_power(x, fb, w, log=True):
     if n:
         with torch.cuda.device(x.device):
             _lib.check(_lib.lib().isd_fb_csp_power(fb._h, x.data_ptr(), w.data_ptr(), out.data_ptr(), n, Cc, T, m,
-                                                   int(bool(log)), csp._stream()))
+                                                   int(bool(log)), _lib.stream()))
     return out
 
 
@@ -144,34 +144,19 @@ class FBCSP:
 
     @staticmethod
     def _check_X(X):
-        if isinstance(X, torch.Tensor):
-            if X.ndim != 3:
-                raise ValueError(f"X must be [n, C, T], got {tuple(X.shape)}")
-            if not X.is_cuda:
-                raise TypeError("tensor input must live on the GPU (there is no CPU fallback)")
-            if X.dtype != torch.float32:
-                raise TypeError("a tensor X must be float32 (the data path is fp32)")
-            return X
-        X = np.asarray(X)
+        if isinstance(X, torch.Tensor) and X.is_cuda and X.dtype != torch.float32:
+            raise TypeError("a tensor X must be float32 (the data path is fp32)")
+        X, _ = _lib.check_array(X, "X", (torch.float32,))
         if X.ndim != 3:
-            raise ValueError(f"X must be [n, C, T], got {X.shape}")
-        if X.dtype.kind != "f":
-            raise TypeError("X must be floating point")
+            raise ValueError(f"X must be [n, C, T], got {tuple(X.shape)}")
         return X
 
     @staticmethod
     def _chunks(X, rows):
         """CUDA float32 [<= rows, C, T] slices of X in order; an ndarray is uploaded slice by slice."""
-        if not isinstance(X, torch.Tensor):
-            if not torch.cuda.is_available():
-                raise RuntimeError("isd_amd.FBCSP needs an MI355X GPU: there is no CPU fallback")
-            dev = torch.device("cuda", torch.cuda.current_device())
+        is_tensor = isinstance(X, torch.Tensor)
         for s in range(0, X.shape[0], rows):
-            part = X[s:s + rows]
-            if isinstance(part, torch.Tensor):
-                yield s, part.contiguous()
-            else:
-                yield s, torch.as_tensor(np.ascontiguousarray(part, dtype=np.float32)).to(dev)
+            yield s, _lib.to_device(X[s:s + rows], is_tensor, "FBCSP", np.float32)
 
     def _filterbank(self):
         key = (tuple(self.bands_), float(self.sfreq), int(self.order), self.precision)

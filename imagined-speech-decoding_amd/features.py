@@ -6,7 +6,6 @@ filters, owns the plans and passes raw device pointers.  Reference anchors:
 scripts/global_shap_analysis.py:132-156 (STFT + band means) and
 notebooks/svm_baseline.ipynb:238 (band-pass in front of the classifier).
 """
-import ctypes as C
 import functools
 
 import numpy as np
@@ -19,10 +18,6 @@ from .filter_design import filterbank_tables
 
 _PREC = {"f32": _lib.FB_F32, "f64": _lib.FB_F64, "auto": _lib.FB_AUTO}
 _MODE = {"magnitude": _lib.BP_MAGNITUDE, "power": _lib.BP_POWER, "logpower": _lib.BP_LOGPOWER}
-
-
-def _stream_ptr():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _require_cuda(t, name):
@@ -68,7 +63,7 @@ class Filterbank(_lib.Handle):
             _require_cuda(out, "out")
             assert out.shape == (B, self.n_bands, Cc, T)
         with torch.cuda.device(x.device):
-            _lib.check(_lib.lib().isd_fb_forward(self._h, x.data_ptr(), out.data_ptr(), B, Cc, T, _stream_ptr()))
+            _lib.check(_lib.lib().isd_fb_forward(self._h, x.data_ptr(), out.data_ptr(), B, Cc, T, _lib.stream()))
         return out
 
 
@@ -90,7 +85,7 @@ class Stft(_lib.Handle):
         R = x.numel() // self.T
         Z = torch.empty(tuple(x.shape[:-1]) + (self.n_bins, self.n_frames, 2), dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
-            _lib.check(_lib.lib().isd_stft_forward(self._h, x.data_ptr(), Z.data_ptr(), R, _stream_ptr()))
+            _lib.check(_lib.lib().isd_stft_forward(self._h, x.data_ptr(), Z.data_ptr(), R, _lib.stream()))
         return torch.view_as_complex(Z)
 
     def bandpower(self, y, bins, mode="logpower", eps=1e-10, shared_signal=False, out=None):
@@ -104,7 +99,7 @@ class Stft(_lib.Handle):
         klo, khi = _lib.int_array([b[0] for b in bins]), _lib.int_array([b[1] for b in bins])
         with torch.cuda.device(y.device):
             _lib.check(_lib.lib().isd_stft_bandpower(self._h, y.data_ptr(), out.data_ptr(), B, Cc, nbi, nb, klo, khi,
-                                                     _MODE[mode], float(eps), _stream_ptr()))
+                                                     _MODE[mode], float(eps), _lib.stream()))
         return out
 
 
@@ -170,13 +165,13 @@ class FeatureExtractor:
             with torch.cuda.device(x.device):
                 _lib.check(_lib.lib().isd_features_fused_bf16(self.fb._h, self.stft._h, x.data_ptr(), out.data_ptr(), B,
                                                               Cc, self._klo, self._khi, _MODE[self.mode], self.eps,
-                                                              _stream_ptr()))
+                                                              _lib.stream()))
             return out
         if fused:
             with torch.cuda.device(x.device):
                 _lib.check(_lib.lib().isd_features_fused(self.fb._h, self.stft._h, x.data_ptr(), out.data_ptr(), B, Cc,
                                                          self._klo, self._khi, _MODE[self.mode], self.eps,
-                                                         _stream_ptr()))
+                                                         _lib.stream()))
             return out
         y = self.fb.forward(x)
         return self.stft.bandpower(y, self.bins, self.mode, self.eps, out=out)
@@ -198,7 +193,7 @@ class FeatureExtractor:
         with torch.cuda.device(x.device):
             _lib.check(L.isd_features_backward(self.fb._h, self.stft._h, x.data_ptr(), dfeat.data_ptr(), dx.data_ptr(),
                                                ws.data_ptr(), B, Cc, self._klo, self._khi, _MODE[self.mode], self.eps,
-                                               _stream_ptr()))
+                                               _lib.stream()))
         return dx
 
 

@@ -12,7 +12,6 @@ which one pass of ``ica_step`` over the raw trials returns (csrc/ica.hip).  Ever
 in float64 on the host (``fastica``), as ``csp.decompose`` does.  ``get_sources`` and ``apply`` are one
 ``spatial_apply`` each.  There is no CPU fallback.
 """
-import ctypes as C
 import warnings
 
 import numpy as np
@@ -25,10 +24,6 @@ from .csp import COV_CHUNK_BYTES, cov_group_mean, trial_covariances
 MAX_COMPONENTS = 64                  # isd_ica_step_*: 1 <= m <= 64
 MAX_CHANNELS = 128                   # 1 <= C <= 128
 MAX_ROWS = 128                       # isd_spatial_apply_*: 1 <= R <= 128
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _check_x(x):
@@ -63,7 +58,7 @@ def ica_step(x, U, b, work=None):
     b = _like(b, x, (m,), "b")
     need = ica_step_work_bytes(n, Cc, T, m, x.dtype)
     if work is None:
-        work = torch.empty(need, dtype=torch.uint8, device=x.device)
+        work = _lib.workspace(need, x.device)
     elif not (isinstance(work, torch.Tensor) and work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous()
               and work.numel() >= need):
         raise ValueError(f"work must be a contiguous uint8 CUDA tensor of at least {need} bytes")
@@ -73,7 +68,7 @@ def ica_step(x, U, b, work=None):
     fn = _lib.lib().isd_ica_step_f32 if x.dtype == torch.float32 else _lib.lib().isd_ica_step_f64
     with torch.cuda.device(x.device):
         _lib.check(fn(x.data_ptr(), U.data_ptr(), b.data_ptr(), P.data_ptr(), s.data_ptr(), q.data_ptr(),
-                      work.data_ptr(), work.numel(), n, Cc, T, m, _stream()))
+                      work.data_ptr(), work.numel(), n, Cc, T, m, _lib.stream()))
     return P, s, q
 
 
@@ -110,7 +105,7 @@ def spatial_apply(x, M, bias=None, out=None):
         fn = _lib.lib().isd_spatial_apply_f32 if x.dtype == torch.float32 else _lib.lib().isd_spatial_apply_f64
         with torch.cuda.device(x.device):
             _lib.check(fn(x.data_ptr(), M.data_ptr(), None if bias is None else bias.data_ptr(), out.data_ptr(), n, Cc,
-                          T, R, _stream()))
+                          T, R, _lib.stream()))
     return out
 
 
@@ -239,30 +234,15 @@ class ICA:
 
     @staticmethod
     def _check_X(X):
-        if isinstance(X, torch.Tensor):
-            if X.ndim != 3:
-                raise ValueError(f"X must be [n, C, T], got {tuple(X.shape)}")
-            if not X.is_cuda:
-                raise TypeError("tensor input must live on the GPU (there is no CPU fallback)")
-            if X.dtype not in (torch.float32, torch.float64):
-                raise TypeError("X must be float32 or float64")
-            return X
-        X = np.asarray(X)
+        X, _ = _lib.check_array(X, "X")
         if X.ndim != 3:
-            raise ValueError(f"X must be [n, C, T], got {X.shape}")
-        if X.dtype.kind != "f":
-            raise TypeError("X must be floating point")
+            raise ValueError(f"X must be [n, C, T], got {tuple(X.shape)}")
         return X
 
     @staticmethod
     def _device(X):
         """X on the GPU: a CUDA tensor as it is (contiguous), an ndarray uploaded as float64."""
-        if isinstance(X, torch.Tensor):
-            return X.contiguous()
-        if not torch.cuda.is_available():
-            raise RuntimeError("isd_amd.ICA needs an MI355X GPU: there is no CPU fallback")
-        dev = torch.device("cuda", torch.cuda.current_device())
-        return torch.as_tensor(np.ascontiguousarray(X, dtype=np.float64)).to(dev)
+        return _lib.to_device(X, isinstance(X, torch.Tensor), "ICA")
 
     def _exclude(self, exclude):
         ex = self.exclude if exclude is None else exclude

@@ -23,10 +23,6 @@ from . import _lib
 from .constants import ELECTRODES, ZONES
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _f32c(t, name):
     if not (t.is_cuda and t.dtype == torch.float32):
         raise TypeError(f"{name} must be a float32 CUDA tensor (the product has no CPU path)")
@@ -85,7 +81,7 @@ class _ConvStackFn(torch.autograd.Function):
         ws = plan.workspace(B, T, x.device)
         with torch.cuda.device(x.device):
             _lib.check(_lib.lib().isd_conv4_forward(plan._h, x.data_ptr(), flat.data_ptr(), feat.data_ptr(),
-                                                    ws.data_ptr(), B, T, _stream()))
+                                                    ws.data_ptr(), B, T, _lib.stream()))
         ctx.plan, ctx.ws = plan, ws
         ctx.save_for_backward(x, flat)
         return feat
@@ -102,10 +98,10 @@ class _ConvStackFn(torch.autograd.Function):
                 dx = torch.empty_like(x)
                 _lib.check(_lib.lib().isd_conv4_backward_x(ctx.plan._h, x.data_ptr(), flat.data_ptr(),
                                                            dfeat.data_ptr(), dflat.data_ptr(), dx.data_ptr(),
-                                                           ctx.ws.data_ptr(), B, T, _stream()))
+                                                           ctx.ws.data_ptr(), B, T, _lib.stream()))
             else:
                 _lib.check(_lib.lib().isd_conv4_backward(ctx.plan._h, x.data_ptr(), flat.data_ptr(), dfeat.data_ptr(),
-                                                         dflat.data_ptr(), ctx.ws.data_ptr(), B, T, _stream()))
+                                                         dflat.data_ptr(), ctx.ws.data_ptr(), B, T, _lib.stream()))
         ctx.ws = None
         return dx, dflat, None
 
@@ -123,7 +119,7 @@ class _LinearFn(torch.autograd.Function):
         with torch.cuda.device(x.device):
             _lib.check(_lib.lib().isd_linear_forward(x.data_ptr(), w.data_ptr(), 0 if b is None else b.data_ptr(),
                                                      y.data_ptr(), 0 if pre is None else pre.data_ptr(), M, K, N,
-                                                     int(act), _stream()))
+                                                     int(act), _lib.stream()))
         ctx.act, ctx.has_bias = int(act), b is not None
         ctx.save_for_backward(x, w, pre)
         return y
@@ -146,7 +142,7 @@ class _LinearFn(torch.autograd.Function):
                                                       0 if pre is None else pre.data_ptr(),
                                                       0 if dx is None else dx.data_ptr(), dw.data_ptr(),
                                                       0 if db is None else db.data_ptr(), ws.data_ptr(), M, K, N,
-                                                      ctx.act, _stream()))
+                                                      ctx.act, _lib.stream()))
         return dx, dw, db, None
 
 
@@ -182,7 +178,7 @@ class _SoftmaxCEFn(torch.autograd.Function):
         with torch.cuda.device(lt.device):
             _lib.check(_lib.lib().isd_softmax_ce(lt.data_ptr(), labels.data_ptr(), labels.element_size(), 0,
                                                  loss.data_ptr(), dlt.data_ptr(), 0, B, n_tok, n_cls,
-                                                 float(grad_scale), ws.data_ptr(), _stream()))
+                                                 float(grad_scale), ws.data_ptr(), _lib.stream()))
         ctx.save_for_backward(dlt)
         return loss
 
@@ -324,7 +320,7 @@ def _staged_pass(call, stage_fn, direction, args, ws, B, world):
     k, L, h = call.kind, _lib.lib(), call.plan._h
     off, n = C.c_int64(), C.c_int64()
     for stage in range(k.stages):
-        _lib.check(getattr(L, stage_fn)(h, stage, *args, world, _stream()))
+        _lib.check(getattr(L, stage_fn)(h, stage, *args, world, _lib.stream()))
         if stage < k.stages - 1:
             _lib.check(getattr(L, k.sync_block)(h, B, direction, stage, C.byref(off), C.byref(n)))
             _all_reduce_block(dist, ws, off.value, n.value, bool(getattr(L, k.sync_block_kind)(direction, stage)))
@@ -344,7 +340,7 @@ def bn_head_forward(call, x, out, ws, keep=False):
     args = (x.data_ptr(), call.theta.data_ptr(), call.bufs.data_ptr(), out.data_ptr(), ws.data_ptr(), B,
             k.mode(call.training, keep), call.momentum, call.eps) + ((call.p, call.seed) if k.dropout else ())
     if world == 1:
-        _lib.check(getattr(_lib.lib(), k.forward)(call.plan._h, *args, _stream()))
+        _lib.check(getattr(_lib.lib(), k.forward)(call.plan._h, *args, _lib.stream()))
     else:
         _staged_pass(call, k.forward_stage, 0, args, ws, B, world)
     return world
@@ -362,9 +358,9 @@ def bn_head_backward(call, x, dout, dflat, ws, world, dx=None):
         if world != 1:
             raise NotImplementedError("the input gradient of the BatchNorm heads is single-device")
         _lib.check(getattr(L, k.backward_x)(h, *args, dx.data_ptr(), ws.data_ptr(), B, k.mode(call.training, True),
-                                            *drop, _stream()))
+                                            *drop, _lib.stream()))
     elif world == 1:
-        _lib.check(getattr(L, k.backward)(h, *args, ws.data_ptr(), B, *drop, _stream()))
+        _lib.check(getattr(L, k.backward)(h, *args, ws.data_ptr(), B, *drop, _lib.stream()))
     else:
         _staged_pass(call, k.backward_stage, 1, args + (ws.data_ptr(), B) + drop, ws, B, world)
 
@@ -476,7 +472,7 @@ class _BNZonesFn(torch.autograd.Function):
                     if z:
                         _lib.check(L.isd_zone_batch_next())
                     bn_head_forward(c, x, out, ws)
-                _lib.check(L.isd_zone_batch_launch(_stream()))
+                _lib.check(L.isd_zone_batch_launch(_lib.stream()))
             except Exception:
                 L.isd_zone_batch_abort()
                 raise
@@ -497,7 +493,7 @@ class _BNZonesFn(torch.autograd.Function):
                     if z:
                         _lib.check(L.isd_zone_batch_next())
                     bn_head_backward(c, x, dz[z], dfl, ws, 1)
-                _lib.check(L.isd_zone_batch_launch(_stream()))
+                _lib.check(L.isd_zone_batch_launch(_lib.stream()))
             except Exception:
                 L.isd_zone_batch_abort()
                 raise
@@ -516,7 +512,7 @@ class _LinearResFn(torch.autograd.Function):
         y = torch.empty(tuple(x.shape[:-1]) + (N,), dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
             _lib.check(_lib.lib().isd_linear_residual_forward(x.data_ptr(), w.data_ptr(), b.data_ptr(), res.data_ptr(),
-                                                              y.data_ptr(), M, K, N, _stream()))
+                                                              y.data_ptr(), M, K, N, _lib.stream()))
         ctx.save_for_backward(x, w)
         return y
 
@@ -533,7 +529,7 @@ class _LinearResFn(torch.autograd.Function):
         with torch.cuda.device(x.device):
             _lib.check(_lib.lib().isd_linear_backward(x.data_ptr(), w.data_ptr(), dy.data_ptr(), 0, dx.data_ptr(),
                                                       dw.data_ptr(), db.data_ptr(), ws.data_ptr(), M, K, N, 0,
-                                                      _stream()))
+                                                      _lib.stream()))
         return dx, dw, db, dy
 
 
@@ -547,7 +543,7 @@ class _LayerNormFn(torch.autograd.Function):
         stats = torch.empty((M, 2), dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
             _lib.check(_lib.lib().isd_layernorm_forward(x.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(),
-                                                        stats.data_ptr(), M, D, float(eps), _stream()))
+                                                        stats.data_ptr(), M, D, float(eps), _lib.stream()))
         ctx.save_for_backward(x, w, stats)
         return y
 
@@ -560,7 +556,7 @@ class _LayerNormFn(torch.autograd.Function):
         dx, dw, db = torch.empty_like(x), torch.empty_like(w), torch.empty_like(w)
         with torch.cuda.device(x.device):
             _lib.check(_lib.lib().isd_layernorm_backward(x.data_ptr(), w.data_ptr(), dy.data_ptr(), stats.data_ptr(),
-                                                         dx.data_ptr(), dw.data_ptr(), db.data_ptr(), M, D, _stream()))
+                                                         dx.data_ptr(), dw.data_ptr(), db.data_ptr(), M, D, _lib.stream()))
         return dx, dw, db, None
 
 
@@ -575,7 +571,7 @@ class _AttentionFn(torch.autograd.Function):
         with torch.cuda.device(qkv.device):
             _lib.check(_lib.lib().isd_attention_forward(qkv.data_ptr(), out.data_ptr(), probs.data_ptr(), B, S,
                                                         num_heads, D // num_heads, float(dropout_p), int(seed),
-                                                        _stream()))
+                                                        _lib.stream()))
         ctx.cfg = (num_heads, float(dropout_p), int(seed))
         ctx.save_for_backward(qkv, probs)
         return out
@@ -589,7 +585,7 @@ class _AttentionFn(torch.autograd.Function):
         dqkv = torch.empty_like(qkv)
         with torch.cuda.device(qkv.device):
             _lib.check(_lib.lib().isd_attention_backward(qkv.data_ptr(), probs.data_ptr(), dctx.data_ptr(),
-                                                         dqkv.data_ptr(), B, S, H, (D3 // 3) // H, p, seed, _stream()))
+                                                         dqkv.data_ptr(), B, S, H, (D3 // 3) // H, p, seed, _lib.stream()))
         return dqkv, None, None, None
 
 
@@ -603,7 +599,7 @@ class _EmbedFn(torch.autograd.Function):
         tok = torch.empty((B, N + 1, D), dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
             _lib.check(_lib.lib().isd_embed_forward(x.data_ptr(), cls.data_ptr(), pos.data_ptr(), tok.data_ptr(), B, N, D,
-                                                    _stream()))
+                                                    _lib.stream()))
         ctx.shape = (B, N, D, tuple(cls.shape), tuple(pos.shape))
         return tok
 
@@ -616,7 +612,7 @@ class _EmbedFn(torch.autograd.Function):
         dpos = torch.zeros(pshape, dtype=torch.float32, device=dtok.device)        # rows past N+1 get no gradient
         with torch.cuda.device(dtok.device):
             _lib.check(_lib.lib().isd_embed_backward(dtok.data_ptr(), dx.data_ptr(), dcls.data_ptr(), dpos.data_ptr(), B,
-                                                     N, D, _stream()))
+                                                     N, D, _lib.stream()))
         return dx, dcls.view(cshape), dpos
 
 
@@ -641,7 +637,7 @@ class _TailFusedFn(torch.autograd.Function):
             _lib.check(L_.isd_tail_fused_forward(flat.data_ptr(), tokin.data_ptr(), logits.data_ptr(),
                                                  save.data_ptr() if train else 0, xfinal.data_ptr() if train else 0,
                                                  B, N, n_pos, D, H, L, hidden, n_cls, p_attn, p_mlp, p_cls, seed,
-                                                 0 if seed_dev is None else seed_dev.data_ptr(), _stream()))
+                                                 0 if seed_dev is None else seed_dev.data_ptr(), _lib.stream()))
         ctx.cfg, ctx.dims = cfg, (B, N, D)
         ctx.shapes = [tuple(p.shape) for p in params]
         if train:
@@ -663,7 +659,7 @@ class _TailFusedFn(torch.autograd.Function):
             _lib.check(L_.isd_tail_fused_backward(flat.data_ptr(), save.data_ptr(), xfinal.data_ptr(),
                                                   dlogits.data_ptr(), dtok.data_ptr(), dflat.data_ptr(), ws.data_ptr(),
                                                   B, N, n_pos, D, H, L, hidden, n_cls, p_attn, p_mlp, p_cls, seed,
-                                                  0 if seed_dev is None else seed_dev.data_ptr(), _stream()))
+                                                  0 if seed_dev is None else seed_dev.data_ptr(), _lib.stream()))
         grads, off = [], 0
         for shp in ctx.shapes:
             n = math.prod(shp)
@@ -702,7 +698,7 @@ def token_mean_predict(logits_tok):
     pred = torch.empty((B,), dtype=torch.int64, device=lt.device)
     with torch.cuda.device(lt.device):
         _lib.check(_lib.lib().isd_softmax_ce(lt.data_ptr(), 0, 0, lm.data_ptr(), 0, 0, pred.data_ptr(), B, n_tok,
-                                             n_cls, 1.0, 0, _stream()))
+                                             n_cls, 1.0, 0, _lib.stream()))
     return lm, pred
 
 

@@ -86,8 +86,7 @@ class FusedAdamW(torch.optim.Optimizer):
         _lib.check(_lib.lib().isd_adamw_multi_step(
             len(g["params"]), self._p, self._g, self._m, self._v, self._n_active, 0.0 if lr_dev else float(lr),
             g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], self._step, lr_dev,
-            self._step_dev.data_ptr() if self._step_dev is not None else None,
-            C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+            self._step_dev.data_ptr() if self._step_dev is not None else None, _lib.stream()))
         return loss
 
     def state_dict(self):

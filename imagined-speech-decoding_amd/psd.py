@@ -13,7 +13,6 @@ check are host work (``welch_design``, pure NumPy); the transform runs in libisd
 product over the kept bins.  There is no CPU fallback.  Not provided: multitaper estimation, complex output,
 ``n_fft > 2048``, a gradient.
 """
-import ctypes as C
 import functools
 from collections import namedtuple
 
@@ -105,14 +104,11 @@ class WelchPlan(_lib.Handle):
         out = torch.empty((rows, self.bins, S) if per_segment else (rows, self.bins), dtype=x.dtype, device=x.device)
         if rows == 0:
             return out
-        need = int(L.isd_psd_work_bytes(self._h, rows, T, int(f64)))
-        if need < 0:
-            _lib.check(need)
+        work = _lib.workspace(L.isd_psd_work_bytes(self._h, rows, T, int(f64)), x.device)
         with torch.cuda.device(x.device):
-            work = torch.empty(need, dtype=torch.uint8, device=x.device)
             fn = L.isd_psd_welch_f64 if f64 else L.isd_psd_welch_f32
             _lib.check(fn(self._h, x.data_ptr(), out.data_ptr(), rows, T, int(bool(per_segment)), work.data_ptr(),
-                          C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+                          _lib.stream()))
         return out
 
 
@@ -142,16 +138,7 @@ def psd_array_welch(x, sfreq, fmin=0, fmax=np.inf, n_fft=256, n_overlap=0, n_per
         raise NotImplementedError(f"output={output!r}: only 'power' is provided")
     if average not in ("mean", "median", None):
         raise ValueError(f"average={average!r} (need 'mean', 'median' or None)")
-    is_tensor = isinstance(x, torch.Tensor)
-    if is_tensor:
-        if not x.is_cuda:
-            raise TypeError("tensor input must live on the GPU (there is no CPU fallback)")
-        if x.dtype not in (torch.float32, torch.float64):
-            raise TypeError("x must be float32 or float64")
-    else:
-        x = np.asarray(x)
-        if x.dtype.kind != "f":
-            raise TypeError("x must be floating point")
+    x, is_tensor = _lib.check_array(x, "x")
     if x.ndim < 1:
         raise ValueError("x must have a time axis")
     lead, T = tuple(x.shape[:-1]), int(x.shape[-1])
@@ -164,14 +151,7 @@ def psd_array_welch(x, sfreq, fmin=0, fmax=np.inf, n_fft=256, n_overlap=0, n_per
                            taps.shape, taps.tobytes())
     if d.n_fft > MAX_N_FFT:
         raise NotImplementedError(f"n_fft={d.n_fft}: at most {MAX_N_FFT} is provided")
-    if is_tensor:
-        xd = x.contiguous()
-    else:
-        if not torch.cuda.is_available():
-            raise RuntimeError("isd_amd.psd_array_welch needs an MI355X GPU: there is no CPU fallback")
-        arr = np.ascontiguousarray(x, dtype=np.float64)
-        xd = torch.from_numpy(arr if arr.flags.writeable else arr.copy()).to(
-            torch.device("cuda", torch.cuda.current_device()))
+    xd = _lib.to_device(x, is_tensor, "psd_array_welch")
     plan = _cached_plan(d.n_fft, d.n_per_seg, d.n_overlap, d.k_lo, d.k_hi, d.window.tobytes(), float(sfreq),
                         bool(remove_dc), xd.device.index)
     K, S = d.k_hi - d.k_lo + 1, d.n_segments

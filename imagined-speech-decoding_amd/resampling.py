@@ -18,7 +18,6 @@ The taps and every argument check are host work (``resample_design``, NumPy and 
 runs in libisd_hip.so (csrc/resample.hip) on the fp32 / fp64 matrix cores.  There is no CPU fallback.  Not provided:
 an FFT resampler, a gradient, bf16, and scipy's pad types 'wrap', 'smooth', 'antireflect' and 'antisymmetric'.
 """
-import ctypes as C
 import fractions
 import functools
 import math
@@ -157,8 +156,7 @@ class Resampler(_lib.Handle):
             fn = _lib.lib().isd_resample_poly_f32 if x.dtype == torch.float32 else _lib.lib().isd_resample_poly_f64
             try:
                 _lib.check(fn(self._h, x2.data_ptr(), out.data_ptr(), rows, T, mode, cval,
-                              bg.data_ptr() if bg is not None else None,
-                              C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+                              bg.data_ptr() if bg is not None else None, _lib.stream()))
             except _lib.IsdUnsupported as e:
                 raise NotImplementedError(str(e)) from None
         return out
@@ -223,16 +221,7 @@ def resample_poly(x, up, down, axis=-1, window=("kaiser", 5.0), padtype="constan
     NotImplementedError."""
     up_r, down_r = _rates(up, down)
     _resolve_pad(padtype, cval)
-    is_tensor = isinstance(x, torch.Tensor)
-    if is_tensor:
-        if not x.is_cuda:
-            raise TypeError("tensor input must live on the GPU (there is no CPU fallback)")
-        if x.dtype not in (torch.float32, torch.float64):
-            raise TypeError("x must be float32 or float64")
-    else:
-        x = np.asarray(x)
-        if x.dtype.kind != "f":
-            raise TypeError("x must be floating point")
+    x, is_tensor = _lib.check_array(x, "x")
     if x.ndim < 1:
         raise ValueError("x must have a time axis")
     axis = operator.index(axis)
@@ -242,14 +231,7 @@ def resample_poly(x, up, down, axis=-1, window=("kaiser", 5.0), padtype="constan
     key, taps_bytes = _window_key(window)
     if (up_r, down_r) != (1, 1):
         _check_envelope(_cached_design(up_r, down_r, key, taps_bytes))
-    if is_tensor:
-        xd = x
-    else:
-        if not torch.cuda.is_available():
-            raise RuntimeError("isd_amd.resample_poly needs an MI355X GPU: there is no CPU fallback")
-        arr = np.ascontiguousarray(x, dtype=np.float64)
-        xd = torch.from_numpy(arr if arr.flags.writeable else arr.copy()).to(
-            torch.device("cuda", torch.cuda.current_device()))
+    xd = x if is_tensor else _lib.to_device(x, False, "resample_poly")   # a tensor is made contiguous after movedim
     plan = _cached_plan(up_r, down_r, key, taps_bytes, xd.device.index)
     y = plan(xd.movedim(axis, -1).contiguous(), padtype, cval).movedim(-1, axis)
     return y if is_tensor else np.ascontiguousarray(y.cpu().numpy())

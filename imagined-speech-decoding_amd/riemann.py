@@ -17,7 +17,7 @@ import torch
 
 from . import _lib
 from .classifier import NotFittedError
-from .csp import COV_CHUNK_BYTES, MAX_CHANNELS, _stream, cov_group_mean, trial_covariances
+from .csp import COV_CHUNK_BYTES, MAX_CHANNELS, cov_group_mean, trial_covariances
 
 SPD_LOG, SPD_SQRT, SPD_INVSQRT, SPD_INV, SPD_NONE = range(5)     # ISD_SPD_* of include/isd_hip.h
 SPD_FULL, SPD_TANGENT, SPD_NOOUT = range(3)
@@ -38,19 +38,10 @@ def _check_stack(a, name):
 
 def _device_stack(a, name="covs"):
     """[n, C, C] ndarray (uploaded as float64) or CUDA tensor -> checked contiguous CUDA tensor."""
-    if isinstance(a, torch.Tensor):
-        if not a.is_cuda:
-            raise TypeError("tensor input must live on the GPU (there is no CPU fallback)")
-        return _check_stack(a, name)
-    a = np.asarray(a)
-    if a.dtype.kind != "f":
-        raise TypeError(f"{name} must be floating point")
+    a, is_tensor = _lib.check_array(a, name)
     if a.ndim != 3 or a.shape[1] != a.shape[2]:
-        raise ValueError(f"{name} must be [n, C, C], got {a.shape}")
-    if not torch.cuda.is_available():
-        raise RuntimeError("isd_amd.riemann needs an MI355X GPU: there is no CPU fallback")
-    dev = torch.device("cuda", torch.cuda.current_device())
-    return _check_stack(torch.from_numpy(np.array(a, dtype=np.float64)).to(dev), name)
+        raise ValueError(f"{name} must be [n, C, C], got {tuple(a.shape)}")
+    return _check_stack(_lib.to_device(a, is_tensor, "riemann"), name)
 
 
 def congruence(cov, W, widx=None):
@@ -78,7 +69,7 @@ def congruence(cov, W, widx=None):
     if n:
         with torch.cuda.device(cov.device):
             _lib.check(_lib.lib().isd_spd_congruence(cov.data_ptr(), int(cov.dtype == torch.float64), W.data_ptr(),
-                                                     idx_ptr, out.data_ptr(), n, Cc, K, _stream()))
+                                                     idx_ptr, out.data_ptr(), n, Cc, K, _lib.stream()))
     return out
 
 
@@ -97,7 +88,7 @@ def _eigfun(a, fn, out_kind, want_eigvals):
         with torch.cuda.device(a.device):
             _lib.check(_lib.lib().isd_spd_eigfun(a.data_ptr(), None if out is None else out.data_ptr(),
                                                  None if eig is None else eig.data_ptr(), info.data_ptr(), n, Cc, fn,
-                                                 out_kind, _stream()))
+                                                 out_kind, _lib.stream()))
     return out, eig, info
 
 

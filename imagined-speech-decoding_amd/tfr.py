@@ -151,14 +151,10 @@ class TfrPlan(_lib.Handle):
             raise ValueError(f"out must be a contiguous {dtype} tensor of shape {shape} on {x.device}")
         if out.numel() == 0:
             return out
-        need = int(L.isd_tfr_work_bytes(self._h, n, Cn, T, m, int(f64)))
-        if need < 0:
-            _lib.check(need)
+        work = _lib.workspace(L.isd_tfr_work_bytes(self._h, n, Cn, T, m, int(f64)), x.device)
         with torch.cuda.device(x.device):
-            work = torch.empty(need, dtype=torch.uint8, device=x.device)
             fn = L.isd_tfr_cwt_f64 if f64 else L.isd_tfr_cwt_f32
-            _lib.check(fn(self._h, x.data_ptr(), out.data_ptr(), n, Cn, T, m, work.data_ptr(),
-                          C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+            _lib.check(fn(self._h, x.data_ptr(), out.data_ptr(), n, Cn, T, m, work.data_ptr(), _lib.stream()))
         return out
 
 
@@ -170,29 +166,10 @@ def _cached_plan(n_taps, taps_bytes, decim, device_index):
 
 def _check_input(x, ndim, name):
     """-> (x as a tensor or ndarray, is_tensor); TypeError for CPU tensors and non-float dtypes, ValueError for the wrong rank."""
-    is_tensor = isinstance(x, torch.Tensor)
-    if is_tensor:
-        if not x.is_cuda:
-            raise TypeError("tensor input must live on the GPU (there is no CPU fallback)")
-        if x.dtype not in (torch.float32, torch.float64):
-            raise TypeError(f"{name} must be float32 or float64")
-    else:
-        x = np.asarray(x)
-        if x.dtype.kind != "f":
-            raise TypeError(f"{name} must be floating point")
+    x, is_tensor = _lib.check_array(x, name)
     if x.ndim != ndim:
         raise ValueError(f"{name} must have {ndim} axes, got shape {tuple(x.shape)}")
     return x, is_tensor
-
-
-def _to_device(x, is_tensor, who):
-    if is_tensor:
-        return x.contiguous()
-    if not torch.cuda.is_available():
-        raise RuntimeError(f"isd_amd.{who} needs an MI355X GPU: there is no CPU fallback")
-    arr = np.ascontiguousarray(x, dtype=np.float64)
-    return torch.from_numpy(arr if arr.flags.writeable else arr.copy()).to(
-        torch.device("cuda", torch.cuda.current_device()))
 
 
 def cwt(X, Ws, use_fft=True, mode="same", decim=1):
@@ -208,7 +185,7 @@ def cwt(X, Ws, use_fft=True, mode="same", decim=1):
         raise ValueError("every wavelet must be a 1-D array of taps")
     n_taps = tuple(int(W.shape[0]) for W in Ws)
     _check_taps(n_taps, int(X.shape[-1]))
-    xd = _to_device(X, is_tensor, "tfr.cwt")
+    xd = _lib.to_device(X, is_tensor, "tfr.cwt")
     plan = _cached_plan(n_taps, np.concatenate(Ws).tobytes(), decim, xd.device.index)
     out = plan(xd[None], "complex")[0]
     return out if is_tensor else out.cpu().numpy()
@@ -240,7 +217,7 @@ def tfr_array_morlet(data, sfreq, freqs, n_cycles=7.0, zero_mean=True, use_fft=T
     _check_taps(n_taps, T)
     if n == 0 and output in ("avg_power", "itc", "avg_power_itc"):
         raise ValueError(f"output={output!r} averages over the trials and there are n=0 of them")
-    xd = _to_device(data, is_tensor, "tfr_array_morlet")
+    xd = _lib.to_device(data, is_tensor, "tfr_array_morlet")
     plan = _cached_plan(n_taps, taps_bytes, decim, xd.device.index)
     out = plan(xd, output)
     return out if is_tensor else out.cpu().numpy()

@@ -278,3 +278,23 @@ def test_pipeline_matches_reference_features(isd):
     plain = copy.copy(f["est"]).set_params(log=False)               # mean_ / std_ are kept by every fit
     power = ref_power(Xt, plain.filters_[:5], False)
     assert _err(plain.transform(Xt), (power - plain.mean_) / plain.std_) < E2E_TOL
+
+
+def test_read_only_ndarray_fits_without_a_warning(isd):
+    """A read-only float64 array (np.frombuffer, a memory-mapped recording) is uploaded without torch's "not
+    writable" UserWarning and gives the bits of a writeable copy: both runs execute the same code on the same values."""
+    import warnings
+    rng = np.random.default_rng(11)
+    a = rng.standard_normal((8, 4, 64)) * np.array([1.0, 2.0, 0.5, 1.5])[None, :, None]
+    y = np.array([0, 1] * 4)
+    a[y == 1, 0] *= 3.0
+    ro = np.frombuffer(a.tobytes()).reshape(a.shape)
+    assert not ro.flags.writeable and np.array_equal(ro, a)
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        est = isd.CSP(n_components=2)
+        got = est.fit_transform(ro, y)
+    ref_est = isd.CSP(n_components=2)
+    ref = ref_est.fit_transform(a.copy(), y)
+    assert got.shape == (8, 2) and np.array_equal(got, ref)
+    assert np.array_equal(est.filters_, ref_est.filters_) and np.array_equal(est.covs_, ref_est.covs_)

@@ -335,3 +335,32 @@ def test_optimizers_reject_what_the_hip_kernels_cannot_take():
     from isd_amd.classifier import _FeatureModel
     with pytest.raises((RuntimeError, TypeError, isd_amd._lib.IsdError if hasattr(isd_amd, "_lib") else RuntimeError)):
         isd_amd.Trainer(_FeatureModel(8, 32, 5, 4))                        # parameters on the host
+
+
+@pytest.mark.parametrize("case", ["cpu_tensor", "int_array", "tensor_dtype", "no_gpu", "workspace"])
+def test_array_boundary_helpers_refuse_by_rule(case, monkeypatch):
+    """_lib.check_array / to_device / workspace: the one statement of "ndarray or CUDA tensor in, no CPU fallback"."""
+    import torch
+    from isd_amd import _lib
+    if case == "cpu_tensor":
+        with pytest.raises(TypeError, match="must live on the GPU"):
+            _lib.check_array(torch.zeros(2, 3, dtype=torch.float32), "x")
+    elif case == "int_array":
+        with pytest.raises(TypeError, match="data must be floating point"):
+            _lib.check_array(np.zeros((2, 3), dtype=np.int64), "data")
+    elif case == "tensor_dtype":                                 # the dtype rule, on a tensor that claims to be on the GPU
+        class OnGpu(torch.Tensor):
+            is_cuda = True
+        with pytest.raises(TypeError, match="X must be float32$"):
+            _lib.check_array(torch.zeros(2, dtype=torch.float64).as_subclass(OnGpu), "X", (torch.float32,))
+    elif case == "no_gpu":
+        monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
+        x, is_tensor = _lib.check_array([[0.5, 1.5]], "x")       # anything np.asarray takes
+        assert isinstance(x, np.ndarray) and x.dtype == np.float64 and not is_tensor
+        with pytest.raises(RuntimeError, match=r"isd_amd\.some_transform needs .* no CPU fallback"):
+            _lib.to_device(x, is_tensor, "some_transform")
+    else:
+        with pytest.raises(_lib.IsdUnsupported) as e:            # a *_work_bytes entry point's negative answer
+            _lib.workspace(-2, "cpu")
+        assert e.value.code == _lib.ISD_ERR_UNSUPPORTED
+        assert _lib.workspace(3, "cpu").dtype == torch.uint8 and _lib.workspace(3, "cpu").numel() == 3

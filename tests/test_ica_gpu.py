@@ -269,3 +269,19 @@ def test_apply(isd):
     assert _err(est6.apply(x6, exclude=[0]), ref6) < TOL64
     with pytest.raises(ValueError, match="exclude"):
         est6.apply(x6, exclude=[6])
+
+
+def test_read_only_ndarray_fits_without_a_warning(isd):
+    """As test_csp_gpu.py: a read-only float64 array is uploaded without torch's "not writable" UserWarning and the fit
+    has the bits of the fit on a writeable copy."""
+    import warnings
+    a = make(8, 4, 64, 4, SEED)[0]
+    ro = np.frombuffer(a.tobytes()).reshape(a.shape)
+    assert not ro.flags.writeable and np.array_equal(ro, a)
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")                              # the fit converges too (6 iterations in sklearn)
+        est = isd.ICA(4, fit_params=dict(w_init=w_init_for(4))).fit(ro)
+        src = est.get_sources(ro)
+    ref = isd.ICA(4, fit_params=dict(w_init=w_init_for(4))).fit(a.copy())
+    assert np.array_equal(est.unmixing_, ref.unmixing_) and np.array_equal(est.mean_, ref.mean_)
+    assert est.n_iter_ == ref.n_iter_ and np.array_equal(src, ref.get_sources(a.copy()))

@@ -28,7 +28,6 @@ import torch
 
 import isd_amd
 from isd_amd import _lib
-from isd_amd.nn import _stream
 from bench_csp import shader_clock_mhz, timed
 from tsception_ref import TSception as RefTSception
 
@@ -67,7 +66,7 @@ def bench_shape(B, C, T, fs, passes, warmup, hip_only):
     def temporal(backward):
         ws = tr.path._ws["ts"]      # the path's workspace: a training step has run on it (an eval forward since then
         #                             has rewritten the pooled map and BN_t's coefficients, which does not change the timing)
-        _lib.check(probe(plan._h, x.data_ptr(), m.flat_params().data_ptr(), ws.data_ptr(), B, backward, _stream()))
+        _lib.check(probe(plan._h, x.data_ptr(), m.flat_params().data_ptr(), ws.data_ptr(), B, backward, _lib.stream()))
 
     fns = {"hip_step": lambda: tr.step(x, y), "hip_eval": lambda: tr.path.forward(x)}
     if not hip_only:
