@@ -60,6 +60,10 @@ __global__ __launch_bounds__(256) void embed_bwd_kernel(const float* __restrict_
 }
 
 // LayerNorm over the last dim (D <= 64), eps inside the sqrt, biased variance (nn.LayerNorm).  One wave per row.
+// The mean is kept in two words, stats [M][3] = (mean, rstd, mean_lo): `mean` is the fp32 quotient sum / D, and
+// `mean_lo` the mean of the residuals x - mean, the part of the row's mean that `mean` rounded away.  x - mean is
+// (nearly) exact, so (x - mean) - mean_lo centres a row to fp32 relative to its SPREAD; with the one-word mean a row
+// at 1e3 +- 1 was centred to half an ulp of 1e3 (3e-5), and y, dx and dw carried that error.
 __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                             const float* __restrict__ b, float* __restrict__ y,
                                                             float* __restrict__ stats, int64_t M, int D, float eps) {
@@ -71,15 +75,21 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
   const float mu = s / (float)D;
-  const float c = lane < D ? v - mu : 0.f;
+  const float c0 = lane < D ? v - mu : 0.f;
+  float r = c0;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) r += __shfl_xor(r, o, 64);
+  const float lo = r / (float)D;
+  const float c = lane < D ? c0 - lo : 0.f;
   float q = c * c;
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
   const float rstd = rsqrtf(q / (float)D + eps);
   if (lane < D) y[row * D + lane] = c * rstd * w[lane] + b[lane];
   if (lane == 0) {
-    stats[row * 2] = mu;
-    stats[row * 2 + 1] = rstd;
+    stats[row * 3] = mu;
+    stats[row * 3 + 1] = rstd;
+    stats[row * 3 + 2] = lo;
   }
 }
 
@@ -91,9 +101,9 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (row >= M) return;
-  const float mu = stats[row * 2], rstd = stats[row * 2 + 1];
+  const float mu = stats[row * 3], rstd = stats[row * 3 + 1], lo = stats[row * 3 + 2];
   const bool in = lane < D;
-  const float xh = in ? (x[row * D + lane] - mu) * rstd : 0.f;
+  const float xh = in ? ((x[row * D + lane] - mu) - lo) * rstd : 0.f;
   const float g = in ? dy[row * D + lane] * w[lane] : 0.f;
   float s1 = g, s2 = g * xh;
 #pragma unroll
@@ -114,7 +124,7 @@ __global__ __launch_bounds__(256) void layernorm_wgrad_kernel(const float* __res
   float a = 0.f, c = 0.f;
   for (int64_t m = threadIdx.x; m < M; m += 256) {
     const float g = dy[m * D + d];
-    a += g * (x[m * D + d] - stats[m * 2]) * stats[m * 2 + 1];
+    a += g * ((x[m * D + d] - stats[m * 3]) - stats[m * 3 + 2]) * stats[m * 3 + 1];
     c += g;
   }
   r1[threadIdx.x] = a;

@@ -540,7 +540,7 @@ class _LayerNormFn(torch.autograd.Function):
         D = x.shape[-1]
         M = x.numel() // D
         y = torch.empty_like(x)
-        stats = torch.empty((M, 2), dtype=torch.float32, device=x.device)
+        stats = torch.empty((M, 3), dtype=torch.float32, device=x.device)      # (mean, rstd, mean_lo) per row
         with torch.cuda.device(x.device):
             _lib.check(_lib.lib().isd_layernorm_forward(x.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(),
                                                         stats.data_ptr(), M, D, float(eps), _lib.stream()))

@@ -587,7 +587,8 @@ int isd_eegnet_sync_block_kind(int backward, int stage);
  * Transformer tail of FAST (src/fast/models/fast.py:10-29 AttentionBlock, :260-268 forward_transformer).
  * The dense projections are isd_linear_* launches over the [B*S, D] token matrix; these are the pieces around them.
  *   embed:      tok[b,0] = cls + pos[0];  tok[b,1+n] = x[b,n] + pos[1+n]                 (fast.py:263-265)
- *   layernorm:  nn.LayerNorm(D), D <= 64; stats [M][2] = (mean, rstd) saved for backward (fast.py:11,13)
+ *   layernorm:  nn.LayerNorm(D), D <= 64; stats [M][3] = (mean, rstd, mean_lo) saved for backward: the row's mean
+ *               is mean + mean_lo, mean_lo the part below fp32's precision of mean              (fast.py:11,13)
  *   attention:  nn.MultiheadAttention core, batch_first: qkv [B][S][3D] (q|k|v) -> ctx [B][S][D], probs [B][H][S][S];
  *               S <= 8 tokens, head_dim <= 8; attention dropout through a counter-based mask (seed)   (fast.py:12,23)
  * ---------------------------------------------------------------------- */

@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from conftest import rel_err
+from tail_ref import torch_tail as _torch_tail
 
 pytestmark = pytest.mark.gpu
 
@@ -16,30 +17,6 @@ def inn():
     import isd_amd.nn as m
     assert torch.cuda.is_available()
     return m
-
-
-def _torch_tail(m, feature):
-    """fast.py:260-268 with the stock torch modules on the same parameters (fp64 on the CPU)."""
-    import torch.nn.functional as F
-    sd = {k: v.detach().cpu().double() for k, v in m.state_dict().items()}
-    p = {k: v.clone().requires_grad_() for k, v in sd.items()}
-    B, N, Z, Fd = feature.shape
-    x = feature.detach().cpu().double().reshape(B, N, Z * Fd)
-    tok = F.gelu(F.linear(x, p["input_layer.0.weight"], p["input_layer.0.bias"]))
-    tok = torch.cat([p["cls_token"].expand(B, -1, -1), tok], dim=1) + p["pos_embedding"][:, :N + 1]
-    D, H = m.config.dim_token, m.config.num_heads
-    for l in range(len(m.transformer)):
-        q = f"transformer.{l}."
-        h = F.layer_norm(tok, (D,), p[q + "layer_norm_1.weight"], p[q + "layer_norm_1.bias"])
-        a, _ = F.multi_head_attention_forward(
-            h.transpose(0, 1), h.transpose(0, 1), h.transpose(0, 1), D, H, p[q + "attn.in_proj_weight"],
-            p[q + "attn.in_proj_bias"], None, None, False, 0.0, p[q + "attn.out_proj.weight"],
-            p[q + "attn.out_proj.bias"], training=False, need_weights=False)
-        tok = tok + a.transpose(0, 1)
-        h = F.layer_norm(tok, (D,), p[q + "layer_norm_2.weight"], p[q + "layer_norm_2.bias"])
-        h = F.gelu(F.linear(h, p[q + "linear.0.weight"], p[q + "linear.0.bias"]))
-        tok = tok + F.linear(h, p[q + "linear.3.weight"], p[q + "linear.3.bias"])
-    return F.linear(tok[:, 0], p["last_layer.weight"], p["last_layer.bias"]), p
 
 
 @pytest.mark.parametrize("B,N,kw", [
