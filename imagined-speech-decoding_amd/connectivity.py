@@ -30,12 +30,28 @@ bin); the step from the density to a measure is elementwise torch ops on the dev
 runs its unit-modulus pass in fp64 for float32 input too.  There is no CPU fallback.
 ndarray in -> computed in fp64 on the GPU -> float64 / complex128 ndarray out; float32 / float64 CUDA tensor in ->
 CUDA tensor of the matching real or complex dtype out.
+
+``envelope_correlation(data, orthogonalize='pairwise', log=False, absolute=True)`` -> [n, C, C] is the amplitude side:
+the orthogonalised power-envelope correlation of Hipp et al. 2012, which does not mistake volume conduction for
+coupling.  Per trial, with z [C, T] the analytic signal (``analytic.hilbert`` of real data), m = |z|, u = conj(z) / m
+(0 where m = 0), e = log(m^2) if ``log`` else m, ec = e - mean_t e, se = |ec|_2 (1 where it is 0):
+
+    o[l, j, t] = |Im(z[l, t] u[j, t])|  (log(o^2) if ``log``),  oc = o - mean_t o,  so = |oc|_2 (1 where it is 0)
+    corr[l, j] = sum_t oc[l, j, t] ec[j, t] / (se[j] so[l, j]),  corr[l, l] = 0
+    result     = (A + A^T) / 2,  A = |corr| if ``absolute`` else corr
+
+and with ``orthogonalize=False`` corr[l, j] = sum_t ec[l, t] ec[j, t] / (se[l] se[j]), np.corrcoef of the envelopes
+(no abs, no symmetrisation).  The name and the arguments follow ``mne_connectivity.envelope_correlation``; that library
+is not installed here and **parity with it is unpinned**: the tests pin the formulas above against a NumPy restatement.
+It is one fused kernel (csrc/envcorr.hip) that reads z once per pair of channel tiles and writes [n, C, C]; in torch
+ops it is an [n, C, C, T] intermediate and several passes over it.
 """
 
 import numpy as np
 import torch
 
 from . import _lib
+from .analytic import hilbert_device
 from .constants import BANDS_5, band_edges
 from .psd import MAX_N_FFT, _cached_design, _cached_plan
 
@@ -224,3 +240,76 @@ def spectral_connectivity(x, sfreq, method="coh", fmin=0, fmax=np.inf, n_fft=256
     if not is_tensor:
         res = [r.cpu().numpy() for r in res]
     return (res[0] if single else res), freqs
+
+
+# ---------------------------------------------------------------------------------------------- envelope correlation
+ENVCORR_CHUNK = 16                   # samples per staged chunk of the pair kernel (kEnvChunk of csrc/envcorr.hip)
+ENV_LOG, ENV_ABSOLUTE, ENV_PLAIN = 1, 2, 4
+_REAL_OF = {torch.complex64: torch.float32, torch.complex128: torch.float64}
+_ENV_DTYPES = (torch.float32, torch.float64, torch.complex64, torch.complex128)
+
+
+def envcorr_launch(z, flags, out=None):
+    """One library call: z contiguous complex CUDA [n, C, T] -> real [n, C, C]; ``out`` (a contiguous real tensor of
+    that shape) receives the result if given."""
+    L = _lib.lib()
+    n, Cc, T = z.shape
+    rdtype = _REAL_OF[z.dtype]
+    f64 = rdtype == torch.float64
+    if out is None:
+        out = torch.empty((n, Cc, Cc), dtype=rdtype, device=z.device)
+    elif tuple(out.shape) != (n, Cc, Cc) or out.dtype != rdtype or not out.is_contiguous() or out.device != z.device:
+        raise ValueError(f"out must be a contiguous {rdtype} tensor of shape {(n, Cc, Cc)} on {z.device}")
+    if n == 0:
+        return out
+    work = _lib.workspace(L.isd_envcorr_work_bytes(n, Cc, T, int(f64)), z.device)
+    with torch.cuda.device(z.device):
+        fn = L.isd_envcorr_f64 if f64 else L.isd_envcorr_f32
+        _lib.check(fn(torch.view_as_real(z).data_ptr(), out.data_ptr(), n, Cc, T, int(flags), work.data_ptr(),
+                      _lib.stream()))
+    return out
+
+
+def envelope_correlation(data, orthogonalize="pairwise", log=False, absolute=True):
+    """Pairwise envelope correlation of data [n, C, T] -> [n, C, C] real ([C, T] -> [C, C]); the formulas are in the
+    module's docstring.
+
+    ``data`` real goes through ``analytic.hilbert`` first (as mne-connectivity does); complex data (a complex64 /
+    complex128 CUDA tensor or a complex ndarray) is taken as the analytic signal as it is.  ``orthogonalize`` is
+    'pairwise' or False.  1 <= C <= MAX_CHANNELS, T >= 1.  The orthogonalised result is symmetric bit for bit with an
+    exactly zero diagonal; a dead (all-zero) channel gives a row and a column of zeros for ``log=False``; with
+    ``log=True`` an exact zero of |z| or of an orthogonalised envelope makes the entries it enters NaN and no other.
+    ndarray in -> the fp64 route -> float64 ndarray out.  Names follow ``mne_connectivity.envelope_correlation``;
+    parity with that library is unpinned (it is not installed here)."""
+    if not (orthogonalize is False or (isinstance(orthogonalize, str) and orthogonalize == "pairwise")):
+        raise ValueError(f"orthogonalize={orthogonalize!r} (need 'pairwise' or False)")
+    is_tensor = isinstance(data, torch.Tensor)
+    if is_tensor:
+        data, _ = _lib.check_array(data, "data", _ENV_DTYPES)
+        is_complex = data.is_complex()
+    else:
+        data = np.asarray(data)
+        if data.dtype.kind not in "fc":
+            raise TypeError("data must be floating point or complex")
+        is_complex = data.dtype.kind == "c"
+    if data.ndim not in (2, 3):
+        raise ValueError(f"data must be [n, C, T] or [C, T], got {tuple(data.shape)}")
+    squeeze = data.ndim == 2
+    if squeeze:
+        data = data[None]
+    n, Cc, T = (int(v) for v in data.shape)
+    if not 1 <= Cc <= MAX_CHANNELS:
+        raise NotImplementedError(f"{Cc} channels: 1 to {MAX_CHANNELS} are provided")
+    if T < 1:
+        raise ValueError("data must have at least one sample")
+    if is_tensor:
+        z = data.resolve_conj().contiguous()
+    else:
+        z = _lib.to_device(data, False, "connectivity", dtype=np.complex128 if is_complex else np.float64)
+    if not is_complex:
+        z = hilbert_device(z, T)
+    flags = (ENV_LOG if log else 0) | (ENV_ABSOLUTE if absolute else 0) | (0 if orthogonalize else ENV_PLAIN)
+    out = envcorr_launch(z, flags)
+    if squeeze:
+        out = out[0]
+    return out if is_tensor else out.cpu().numpy()

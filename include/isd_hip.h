@@ -355,6 +355,27 @@ int isd_csd_welch_f64(const isd_psd_plan* plan, const double* x, double* out, in
                       int over_trials, int unit_modulus, void* work, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Pairwise envelope correlation (csrc/envcorr.hip; isd_amd.connectivity.envelope_correlation).  z [n][C][T][2] is the
+ * analytic signal of n trials, (re, im) interleaved; out [n][C][C] real.  Per trial, with m = |z|, e = m (flag 1:
+ * log m^2), ec = e - mean_t e and se = |ec|_2 (1 where it is 0):
+ *   orthogonalised (flag 4 clear): o[l|j] = |Im(z_l conj(z_j))| / m_j (0 where m_j = 0; flag 1: log o^2), centred over
+ *     t, correlated with ec_j: corr[l|j] = sum_t oc ec_j / (se_j |oc|_2) (|oc|_2 = 1 where it is 0);
+ *     out[l][j] = out[j][l] = (A[l|j] + A[j|l]) / 2 with A = |corr| under flag 2, else corr; the diagonal is 0.
+ *   plain (flag 4): out[l][j] = sum_t ec_l ec_j / (se_l se_j); the diagonal is 1, or 0 for a row of zero norm;
+ *     flag 2 is ignored.
+ * Sums over t are fp64 in both precisions, in sample order, with no atomics: bitwise repeatable, and out is symmetric
+ * bit for bit.  With flag 1 an exact zero of m or o makes the entries it enters NaN and no other.
+ * `work`: isd_envcorr_work_bytes bytes (about the size of z), 256-byte aligned.  z and out need the alignment of one
+ * complex / one real element.  No call synchronises with the host.  n == 0 returns 0 with nothing touched;
+ * C outside 1..128 is ISD_ERR_UNSUPPORTED; a null pointer, T < 1 with n > 0 or an unknown flag is ISD_ERR_INVALID.
+ * ---------------------------------------------------------------------- */
+int64_t isd_envcorr_work_bytes(int64_t n, int64_t C, int64_t T, int is_f64);      /* never 0; negative = error code */
+int isd_envcorr_f32(const float* z /* [n][C][T][2] */, float* out /* [n][C][C] */, int64_t n, int64_t C, int64_t T,
+                    int flags /* 1 log | 2 absolute | 4 plain */, void* work, void* stream);
+int isd_envcorr_f64(const double* z, double* out, int64_t n, int64_t C, int64_t T, int flags, void* work,
+                    void* stream);
+
+/* ------------------------------------------------------------------------
  * Complex FIR bank with decimation: the data-sized step of a time-frequency transform
  * (isd_amd.tfr_array_morlet, the counterpart of mne.time_frequency.tfr_array_morlet; isd_amd.tfr.cwt).  The library
  * knows nothing about wavelets: the plan takes n_freqs complex tap vectors of odd lengths and
