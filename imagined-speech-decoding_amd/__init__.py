@@ -14,10 +14,11 @@ from .fbcsp import FBCSP  # noqa: F401
 from .ica import ICA  # noqa: F401
 from .psd import psd_array_welch  # noqa: F401
 from .analytic import envelope, hilbert  # noqa: F401
+from .pac import phase_amplitude_coupling  # noqa: F401
 from .tfr import tfr_array_morlet  # noqa: F401
 from .resampling import Resampler, resample, resample_poly  # noqa: F401
 from .filter_design import butter_bandpass_resonators, butter_bandpass_sos, fir_design  # noqa: F401
-from . import analytic, connectivity, csp, data, experiment, explain, fbcsp, ica, psd, resampling, riemann, tfr  # noqa: F401
+from . import analytic, connectivity, csp, data, experiment, explain, fbcsp, ica, pac, psd, resampling, riemann, tfr  # noqa: F401
 from . import resampling as resample_mod  # noqa: F401  (isd_amd.resample is the function)
 from .optim import FusedAdamW  # noqa: F401
 from .classifier import (EEGNetPath, FASTHeadClassifier, FilterbankCNNClassifier,  # noqa: F401
@@ -30,4 +31,5 @@ __all__ = ["TSceptionClassifier", "TSceptionPath", "nn", "FusedAdamW", "Filterba
            "butter_bandpass_resonators", "BANDS_5", "BANDS_9", "BANDS_40", "CLASSES", "ELECTRODES", "ZONES",
            "zone_index_lists", "data", "experiment", "explain", "FirFilter", "filter_data", "fir_design", "CSP", "csp", "ICA", "ica",
            "psd_array_welch", "psd", "FBCSP", "fbcsp", "riemann", "tfr", "tfr_array_morlet", "connectivity",
-           "resample_poly", "resample", "Resampler", "resampling", "resample_mod", "analytic", "hilbert", "envelope"]
+           "resample_poly", "resample", "Resampler", "resampling", "resample_mod", "analytic", "hilbert", "envelope",
+           "pac", "phase_amplitude_coupling"]

@@ -94,6 +94,9 @@ SIGNATURES = {
     "isd_envcorr_work_bytes": (_i64, [_i64, _i64, _i64, _i]),
     "isd_envcorr_f32": (_i, [_p, _p, _i64, _i64, _i64, _i, _p, _p]),
     "isd_envcorr_f64": (_i, [_p, _p, _i64, _i64, _i64, _i, _p, _p]),
+    "isd_pac_work_bytes": (_i64, [_i64, _i64, _i64, _i64, _i]),
+    "isd_pac_f32": (_i, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i, C.c_double, _p, _p]),
+    "isd_pac_f64": (_i, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i, C.c_double, _p, _p]),
     "isd_tfr_plan_create": (_i, [C.POINTER(_p), _i, _pi, _pd, _i]),
     "isd_tfr_plan_destroy": (_i, [_p]),
     "isd_tfr_plan_out_len": (_i64, [_p, _i64]),

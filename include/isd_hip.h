@@ -376,6 +376,27 @@ int isd_envcorr_f64(const double* z, double* out, int64_t n, int64_t C, int64_t 
                     void* stream);
 
 /* ------------------------------------------------------------------------
+ * Phase-amplitude coupling with circular-shift surrogates (csrc/pac.hip; isd_amd.phase_amplitude_coupling).
+ * pha [rows][P][T] phases in [-pi, pi], amp [rows][A][T] amplitudes >= 0, shifts int32 [1 + S] on the device with
+ * shifts[0] = 0 (the estimate) and 0 <= shifts[i] < T (the surrogates: amp read at (t + shift) mod T).  The phase bin
+ * is min(n_bins - 1, max(0, floor((double(pha) + pi) * c))), c = n_bins / (2 pi) formed by the caller, in fp64 in both
+ * entries.  out [rows][A][P][3][4]: per method (0 mean vector length, 1 modulation index, 2 heights ratio) the value
+ * at shift 0, the mean and the population std of the S surrogate values (fp64 sums of the values as rounded to the
+ * output type) and the number of surrogates >= the value.  surr, if not null, [rows][A][P][3][S]: every surrogate
+ * value.  With S = 0 mean and std are NaN and the count is 0.  Every sum runs in a fixed order with no atomics: bitwise
+ * repeatable.  A shift outside [0, T - 1] is clamped, and shift 0 is read as 0.
+ * `work`: isd_pac_work_bytes bytes (the bin-sorted (cos, sin, t) records of pha: 3 x its size in fp32, 2.5 x in fp64),
+ * 256-byte aligned; every array needs its element's alignment.  No call synchronises with the host.  rows == 0 returns
+ * 0 with nothing touched.  Envelope: 1 <= T <= 4096, 2 <= n_bins <= 64, 0 <= S <= 4095, P, A >= 1,
+ * rows * A * P < 2^31; outside it ISD_ERR_UNSUPPORTED.
+ * ---------------------------------------------------------------------- */
+int64_t isd_pac_work_bytes(int64_t rows, int64_t P, int64_t A, int64_t T, int is_f64);   /* negative = error code */
+int isd_pac_f32(const float* pha, const float* amp, const int32_t* shifts, float* out, float* surr, int64_t rows,
+                int64_t P, int64_t A, int64_t T, int64_t S, int n_bins, double c, void* work, void* stream);
+int isd_pac_f64(const double* pha, const double* amp, const int32_t* shifts, double* out, double* surr, int64_t rows,
+                int64_t P, int64_t A, int64_t T, int64_t S, int n_bins, double c, void* work, void* stream);
+
+/* ------------------------------------------------------------------------
  * Complex FIR bank with decimation: the data-sized step of a time-frequency transform
  * (isd_amd.tfr_array_morlet, the counterpart of mne.time_frequency.tfr_array_morlet; isd_amd.tfr.cwt).  The library
  * knows nothing about wavelets: the plan takes n_freqs complex tap vectors of odd lengths and
