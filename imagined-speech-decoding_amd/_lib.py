@@ -245,6 +245,15 @@ def workspace(nbytes, device):
     return torch.empty(int(nbytes), dtype=torch.uint8, device=device)
 
 
+def typed(stem, dtype):
+    """The entry point of a float32 / float64 pair for ``dtype``: ``lib().<stem>_f32`` or ``lib().<stem>_f64``."""
+    return getattr(lib(), stem + {torch.float32: "_f32", torch.float64: "_f64"}[dtype])
+
+
+def _names(dtypes):
+    return " or ".join(str(d).replace("torch.", "") for d in dtypes)
+
+
 def check_array(x, name, dtypes=(torch.float32, torch.float64)):
     """The type rules of an array argument, none of which needs a GPU -> (x, is_tensor): a CUDA tensor of one of
     ``dtypes`` as it is, anything else as a floating-point ndarray.  Rank and shape are the caller's."""
@@ -252,12 +261,26 @@ def check_array(x, name, dtypes=(torch.float32, torch.float64)):
         if not x.is_cuda:
             raise TypeError("tensor input must live on the GPU (there is no CPU fallback)")
         if x.dtype not in dtypes:
-            raise TypeError(f"{name} must be {' or '.join(str(d).replace('torch.', '') for d in dtypes)}")
+            raise TypeError(f"{name} must be {_names(dtypes)}")
         return x, True
     x = np.asarray(x)
     if x.dtype.kind != "f":
         raise TypeError(f"{name} must be floating point")
     return x, False
+
+
+def check_cuda(x, name, max_channels, dtypes=(torch.float32, torch.float64), square=False):
+    """The argument of a kernel wrapper: a CUDA tensor [n, C, T] (``square``: [n, C, C]) of one of ``dtypes`` with
+    1 <= C <= ``max_channels`` and T >= 1 -> x, contiguous."""
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype in dtypes):
+        raise TypeError(f"{name} must be a {_names(dtypes)} CUDA tensor")
+    shape = "[n, C, C]" if square else "[n, C, T]"
+    if x.ndim != 3 or (square and x.shape[1] != x.shape[2]):
+        raise ValueError(f"{name} must be {shape}, got {tuple(x.shape)}")
+    if not 1 <= x.shape[1] <= max_channels or x.shape[2] < 1:
+        raise ValueError(f"{name} {shape} needs 1 <= C <= {max_channels}{'' if square else ' and T >= 1'}, "
+                         f"got {tuple(x.shape)}")
+    return x.contiguous()
 
 
 def to_device(x, is_tensor, who, dtype=np.float64, device=None):

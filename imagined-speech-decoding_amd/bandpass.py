@@ -41,7 +41,7 @@ class FirFilter(_lib.Handle):
             raise ValueError("in-place filtering is not supported")
         if rows == 0:
             return out
-        fn = _lib.lib().isd_fir_zero_phase_f32 if x.dtype == torch.float32 else _lib.lib().isd_fir_zero_phase_f64
+        fn = _lib.typed("isd_fir_zero_phase", x.dtype)
         with torch.cuda.device(x.device):
             _lib.check(fn(self._h, x.data_ptr(), out.data_ptr(), rows, T, _lib.stream()))
         return out

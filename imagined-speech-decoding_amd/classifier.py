@@ -13,6 +13,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._estimator import Estimator, NotFittedError  # noqa: F401  (NotFittedError: this module's public name)
 from .constants import BANDS_9, BANDS_40, CLASSES, ELECTRODES, ZONES
 from .features import FeatureExtractor
 from .nn import (FAST, EEGNet_Encoder, FeatureCNN, TSception, _bn_sync_world, _FlatParamMixin,
@@ -510,14 +511,8 @@ def _to_device(X, device):
     return torch.as_tensor(np.ascontiguousarray(X, dtype=np.float32)).to(device)
 
 
-class NotFittedError(ValueError, AttributeError):
-    """Same base classes as ``sklearn.exceptions.NotFittedError`` (raised by predict before fit)."""
-
-
-class _Estimator:
-    """sklearn estimator protocol: constructor arguments are stored verbatim under their own names
-    (``get_params`` / ``set_params`` / ``sklearn.base.clone`` work), ``fit`` starts from scratch unless
-    ``warm_start=True``, fitted state lives in trailing-underscore attributes."""
+class _Estimator(Estimator):
+    """The trained classifiers: ``fit`` starts from scratch unless ``warm_start=True``."""
     classes_ = np.arange(len(CLASSES))
     class_names_ = list(CLASSES)
     _param_names = ("max_epochs", "batch_size", "lr", "weight_decay", "warmup_epochs", "seed", "device", "shuffle",
@@ -536,20 +531,8 @@ class _Estimator:
         self.trainer_ = None
         self.history_ = []
 
-    def get_params(self, deep=True):
-        return {k: getattr(self, k) for k in self._param_names}
-
-    def set_params(self, **params):
-        for k, v in params.items():
-            if k not in self._param_names:
-                raise ValueError(f"invalid parameter {k!r} for {type(self).__name__}")
-            setattr(self, k, v)
-        return self
-
     def _fitted_model(self):
-        if self.model_ is None:
-            raise NotFittedError(f"this {type(self).__name__} instance is not fitted yet: call fit(X, y) (or load a "
-                                 "state dict) before predict / decision_function")
+        self._require_fitted("model_", "fit(X, y) (or load a state dict) before predict / decision_function")
         return self.model_
 
     def _device(self):

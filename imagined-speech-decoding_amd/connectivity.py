@@ -110,7 +110,7 @@ def csd_launch(plan, x, over_trials, unit_modulus=False, out=None):
     L.isd_csd_chunk_bytes(0 if CSD_CHUNK_BYTES is None else int(CSD_CHUNK_BYTES))
     work = _lib.workspace(L.isd_csd_work_bytes(plan._h, n, Cc, T, int(bool(over_trials)), int(f64)), x.device)
     with torch.cuda.device(x.device):
-        fn = L.isd_csd_welch_f64 if f64 else L.isd_csd_welch_f32
+        fn = _lib.typed("isd_csd_welch", x.dtype)
         _lib.check(fn(plan._h, x.data_ptr(), out.data_ptr(), n, Cc, T, int(bool(over_trials)),
                       int(bool(unit_modulus)), work.data_ptr(), _lib.stream()))
     return out
@@ -264,7 +264,7 @@ def envcorr_launch(z, flags, out=None):
         return out
     work = _lib.workspace(L.isd_envcorr_work_bytes(n, Cc, T, int(f64)), z.device)
     with torch.cuda.device(z.device):
-        fn = L.isd_envcorr_f64 if f64 else L.isd_envcorr_f32
+        fn = _lib.typed("isd_envcorr", rdtype)
         _lib.check(fn(torch.view_as_real(z).data_ptr(), out.data_ptr(), n, Cc, T, int(flags), work.data_ptr(),
                       _lib.stream()))
     return out

@@ -16,31 +16,21 @@ import numpy as np
 import torch
 
 from . import _lib
-from .classifier import NotFittedError
+from ._estimator import Estimator, cat_like, check_trials, chunks, transformer_tags
 
 MAX_COMPONENTS = 16                  # isd_csp_power_*: 1 <= m <= 16
 MAX_CHANNELS = 128                   # isd_trial_cov_*: 1 <= C <= 128
 COV_CHUNK_BYTES = 256 << 20          # bound on the [chunk, C, C] covariance buffer of fit
 
 
-def _check_x(x):
-    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype in (torch.float32, torch.float64)):
-        raise TypeError("x must be a float32 or float64 CUDA tensor")
-    if x.ndim != 3:
-        raise ValueError(f"x must be [n, C, T], got {tuple(x.shape)}")
-    if not 1 <= x.shape[1] <= MAX_CHANNELS or x.shape[2] < 1:
-        raise ValueError(f"x [n, C, T] needs 1 <= C <= {MAX_CHANNELS} and T >= 1, got {tuple(x.shape)}")
-    return x.contiguous()
-
-
 def trial_covariances(x):
     """x CUDA tensor [n, C, T], float32 or float64 -> [n, C, C] of the same dtype: X_i X_iᵀ / T (no mean removal),
     exactly symmetric."""
-    x = _check_x(x)
+    x = _lib.check_cuda(x, "x", MAX_CHANNELS)
     n, Cc, T = x.shape
     cov = torch.empty(n, Cc, Cc, dtype=x.dtype, device=x.device)
     if n:
-        fn = _lib.lib().isd_trial_cov_f32 if x.dtype == torch.float32 else _lib.lib().isd_trial_cov_f64
+        fn = _lib.typed("isd_trial_cov", x.dtype)
         with torch.cuda.device(x.device):
             _lib.check(fn(x.data_ptr(), cov.data_ptr(), n, Cc, T, _lib.stream()))
     return cov
@@ -75,17 +65,29 @@ def cov_group_mean(cov, idx, offs, norm_trace=False):
 def csp_power(x, w, log=True):
     """x CUDA [n, C, T]; w [m, C] (1 <= m <= 16; tensor or array, cast to x's dtype) -> [n, m] of x's dtype:
     mean_t (w_j · x_i[:, t])², its log if ``log``.  The projected signal is never materialised."""
-    x = _check_x(x)
+    x = _lib.check_cuda(x, "x", MAX_CHANNELS)
     n, Cc, T = x.shape
     w = torch.as_tensor(w).to(device=x.device, dtype=x.dtype).contiguous()
     if w.ndim != 2 or w.shape[1] != Cc or not 1 <= w.shape[0] <= MAX_COMPONENTS:
         raise ValueError(f"w must be [m, {Cc}] with 1 <= m <= {MAX_COMPONENTS}, got {tuple(w.shape)}")
     out = torch.empty(n, w.shape[0], dtype=x.dtype, device=x.device)
     if n:
-        fn = _lib.lib().isd_csp_power_f32 if x.dtype == torch.float32 else _lib.lib().isd_csp_power_f64
+        fn = _lib.typed("isd_csp_power", x.dtype)
         with torch.cuda.device(x.device):
             _lib.check(fn(x.data_ptr(), w.data_ptr(), out.data_ptr(), n, Cc, T, w.shape[0], int(bool(log)), _lib.stream()))
     return out
+
+
+def band_major_groups(yc, K, nb):
+    """Group index of a chunk for ``cov_group_mean`` on the [chunk · nb, C, C] view of its [chunk, nb, C, C]
+    covariances.  yc [chunk] class indices in [0, K) -> (idx, offs): group b · K + k lists the rows i · nb + b of the
+    chunk's trials i of class k, in trial order; offs [nb · K + 1]."""
+    yc = np.asarray(yc, dtype=np.int64).reshape(-1)
+    order = np.argsort(yc, kind="stable")                        # the chunk's trials sorted by class
+    cnt = np.bincount(yc, minlength=K)
+    idx = (order[None, :] * nb + np.arange(nb, dtype=np.int64)[:, None]).reshape(-1)
+    offs = np.concatenate([[0], np.cumsum(np.tile(cnt, nb))]).astype(np.int64)
+    return idx, offs
 
 
 # ------------------------------------------------------------------------------------------- host decomposition
@@ -157,7 +159,112 @@ def decompose(covs, weights):
 
 
 # --------------------------------------------------------------------------------------------------- estimator
-class CSP:
+class BandedCSP(Estimator):
+    """The fit and transform that ``CSP`` and ``FBCSP`` share: one CSP per band of [n, C, T] trials, ``CSP`` being
+    the case of one band.  A subclass sets ``_upload`` (the dtype an ndarray chunk is uploaded as; its size bounds the
+    rows of a chunk), ``_dtypes`` (those of a tensor X) and ``_keep_bands`` (whether ``filters_``, ``scores_``,
+    ``patterns_`` and ``covs_`` keep the leading band axis), extends ``_check_params`` and supplies
+
+    ``_chunk_bytes()``           its module's COV_CHUNK_BYTES, read at call time;
+    ``_start_fit(checked)``      called by fit once X and y have passed their checks, with what ``_check_params``
+                                 returned; may store fitted state; -> n_bands;
+    ``_chunk_covs(xc)``          xc CUDA [chunk, C, T] -> CUDA [chunk · n_bands, C, C], trial-major;
+    ``_chunk_power(xc, w, log)`` w [n_bands, m, C] of dtype ``_upload`` -> CUDA, chunk · n_bands · m numbers in that
+                                 order."""
+    _upload, _dtypes, _keep_bands = np.float64, (torch.float32, torch.float64), False
+
+    def __sklearn_tags__(self):
+        return transformer_tags(required_y=True)
+
+    def _check_params(self):
+        if self.log is not None and not isinstance(self.log, (bool, np.bool_)):
+            raise ValueError(f"log={self.log!r} (need None, True or False)")
+        m = self.n_components
+        if not isinstance(m, (int, np.integer)) or isinstance(m, bool) or m < 1:
+            raise ValueError(f"n_components={m!r} (need a positive int)")
+        if m > MAX_COMPONENTS:
+            raise NotImplementedError(f"n_components={m}: at most {MAX_COMPONENTS} are provided")
+
+    def _banded(self, a):
+        """A fitted [n_bands, ...] array as the estimator publishes it: ``CSP`` drops the band axis."""
+        return a if self._keep_bands else a[0]
+
+    def _chunks(self, X, elements):
+        """The chunks of X that keep a buffer of ``elements`` numbers a trial under ``_chunk_bytes()``."""
+        rows = max(1, self._chunk_bytes() // (elements * np.dtype(self._upload).itemsize))
+        return chunks(X, rows, type(self).__name__, self._upload)
+
+    def _power(self, X, log):
+        """[n, n_bands · m] average power of the picked components, band-major, in X's kind (ndarray -> float64
+        ndarray)."""
+        filters = self.filters_ if self._keep_bands else self.filters_[None]
+        w = np.ascontiguousarray(filters[:, :self.n_components], dtype=self._upload)
+        parts = [self._chunk_power(xc, w, log) for _, xc in self._chunks(X, X.shape[1] * X.shape[2])]
+        return cat_like(parts, X, w.shape[:2]).reshape(X.shape[0], w.shape[0] * w.shape[1])
+
+    def fit(self, X, y):
+        """X [n, C, T] (ndarray, or CUDA tensor of one of ``_dtypes``), y [n] labels of at least two classes.
+        Returns self."""
+        checked = self._check_params()
+        X = check_trials(X, self._dtypes)
+        y = y.detach().cpu().numpy() if isinstance(y, torch.Tensor) else np.asarray(y)
+        if y.ndim != 1 or len(y) != X.shape[0]:
+            raise ValueError(f"X has {X.shape[0]} trials, y has shape {y.shape}")
+        classes, yi = np.unique(y, return_inverse=True)
+        K = len(classes)
+        if K < 2:
+            raise ValueError(f"{type(self).__name__} needs at least two classes")
+        n, C_, T = X.shape
+        if self.n_components > C_:
+            raise ValueError(f"n_components={self.n_components} exceeds the {C_} channels")
+        if C_ > MAX_CHANNELS:
+            raise NotImplementedError(f"{C_} channels: at most {MAX_CHANNELS} are provided")
+        if T < 1:
+            raise ValueError("X has no samples")
+        nb = self._start_fit(checked)
+        counts = np.bincount(yi, minlength=K)
+        # CSP's cov_est: with trials of equal length, 'concat' (covariance of the class's concatenated trials) and
+        # 'epoch' (mean of the trial covariances) are the same number unless each trial is first divided by its trace
+        covs = np.zeros((nb, K, C_, C_))
+        for s, xc in self._chunks(X, nb * C_ * max(C_, T)):
+            yc = yi[s:s + xc.shape[0]]
+            idx, offs = band_major_groups(yc, K, nb)             # nb == 1: the chunk's trials sorted by class
+            part = cov_group_mean(self._chunk_covs(xc), idx, offs, self.norm_trace).cpu().numpy()
+            cnt = np.bincount(yc, minlength=K)
+            covs += part.reshape(nb, K, C_, C_) * (cnt / counts)[None, :, None, None]     # chunks in order, fp64
+        filters, scores = zip(*(decompose(covs[b], counts) for b in range(nb)))
+        patterns = [np.linalg.pinv(f.T) for f in filters]
+        self.classes_, self.covs_ = classes, self._banded(covs)
+        self.filters_, self.scores_ = self._banded(np.stack(filters)), self._banded(np.stack(scores))
+        self.patterns_ = self._banded(np.stack(patterns))
+        self.n_channels_ = C_
+        power = self._power(X, False)
+        power = power.double().cpu().numpy() if isinstance(power, torch.Tensor) else power
+        self.mean_, self.std_ = power.mean(0), power.std(0)
+        return self
+
+    def transform(self, X):
+        """X [n, C, T] -> [n, n_bands · n_components]: log average power (``log`` None / True) or the z-scored
+        average power ``(power − mean_) / std_`` (``log=False``)."""
+        self._require_fitted("filters_", "fit(X, y) before transform")
+        self._check_params()
+        X = check_trials(X, self._dtypes)
+        if X.shape[1] != self.n_channels_:
+            raise ValueError(f"X has {X.shape[1]} channels, fit saw {self.n_channels_}")
+        log = True if self.log is None else bool(self.log)
+        power = self._power(X, log)
+        if not log:
+            if isinstance(power, torch.Tensor):
+                power = (power - torch.as_tensor(self.mean_).to(power)) / torch.as_tensor(self.std_).to(power)
+            else:
+                power = (power - self.mean_) / self.std_
+        return power
+
+    def fit_transform(self, X, y=None, **fit_params):
+        return self.fit(X, y).transform(X)
+
+
+class CSP(BandedCSP):
     """Drop-in for ``mne.decoding.CSP`` inside an sklearn ``Pipeline`` (same argument order and defaults).
     ``log=None`` means True for 'average_power'.  ``reg``, ``rank``, ``cov_method_params``,
     ``transform_into='csp_space'``, another ``component_order`` and more than 16 components are not provided and
@@ -172,25 +279,6 @@ class CSP:
         self.transform_into, self.norm_trace, self.cov_method_params = transform_into, norm_trace, cov_method_params
         self.rank, self.component_order = rank, component_order
 
-    def get_params(self, deep=True):
-        return {k: getattr(self, k) for k in self._param_names}
-
-    def set_params(self, **params):
-        for k, v in params.items():
-            if k not in self._param_names:
-                raise ValueError(f"invalid parameter {k!r} for {type(self).__name__}")
-            setattr(self, k, v)
-        return self
-
-    def __sklearn_tags__(self):
-        """Called by sklearn only (Pipeline, clone, checks), so sklearn is imported here and nowhere else."""
-        from sklearn.utils import InputTags, Tags, TargetTags, TransformerTags
-        return Tags(estimator_type=None, target_tags=TargetTags(required=True), transformer_tags=TransformerTags(),
-                    input_tags=InputTags(three_d_array=True))
-
-    def __repr__(self):
-        return f"CSP({', '.join(f'{k}={getattr(self, k)!r}' for k in self._param_names)})"
-
     def _check_params(self):
         for name in ("reg", "rank", "cov_method_params"):
             if getattr(self, name) is not None:
@@ -203,97 +291,16 @@ class CSP:
             raise NotImplementedError(f"component_order={self.component_order!r}: only 'mutual_info' is provided")
         if self.cov_est not in ("concat", "epoch"):
             raise ValueError(f"cov_est={self.cov_est!r} (need 'concat' or 'epoch')")
-        if self.log is not None and not isinstance(self.log, (bool, np.bool_)):
-            raise ValueError(f"log={self.log!r} (need None, True or False)")
-        m = self.n_components
-        if not isinstance(m, (int, np.integer)) or isinstance(m, bool) or m < 1:
-            raise ValueError(f"n_components={m!r} (need a positive int)")
-        if m > MAX_COMPONENTS:
-            raise NotImplementedError(f"n_components={m}: at most {MAX_COMPONENTS} are provided")
+        super()._check_params()
 
-    @staticmethod
-    def _check_X(X):
-        X, _ = _lib.check_array(X, "X")
-        if X.ndim != 3:
-            raise ValueError(f"X must be [n, C, T], got {tuple(X.shape)}")
-        return X
+    def _chunk_bytes(self):
+        return COV_CHUNK_BYTES
 
-    @staticmethod
-    def _chunks(X, rows):
-        """CUDA [<= rows, C, T] slices of X in order; an ndarray is uploaded slice by slice as float64."""
-        is_tensor = isinstance(X, torch.Tensor)
-        for s in range(0, X.shape[0], rows):
-            yield s, _lib.to_device(X[s:s + rows], is_tensor, "CSP")
+    def _start_fit(self, checked):
+        return 1
 
-    def _power(self, X, log):
-        """[n, m] average power of the picked components, in X's kind (ndarray -> float64 ndarray)."""
-        C_, T = X.shape[1], X.shape[2]
-        rows = max(1, COV_CHUNK_BYTES // (C_ * T * 8))
-        w = self.filters_[:self.n_components]
-        parts = [csp_power(xc, w, log) for _, xc in self._chunks(X, rows)]
-        if isinstance(X, torch.Tensor):
-            return torch.cat(parts) if parts else torch.empty(0, len(w), dtype=X.dtype, device=X.device)
-        return torch.cat(parts).cpu().numpy() if parts else np.empty((0, len(w)))
+    def _chunk_covs(self, xc):
+        return trial_covariances(xc)
 
-    def fit(self, X, y):
-        """X [n, C, T] (ndarray, or f32 / f64 CUDA tensor), y [n] labels of at least two classes.  Returns self."""
-        self._check_params()
-        X = self._check_X(X)
-        y = y.detach().cpu().numpy() if isinstance(y, torch.Tensor) else np.asarray(y)
-        if y.ndim != 1 or len(y) != X.shape[0]:
-            raise ValueError(f"X has {X.shape[0]} trials, y has shape {y.shape}")
-        classes, yi = np.unique(y, return_inverse=True)
-        K = len(classes)
-        if K < 2:
-            raise ValueError("CSP needs at least two classes")
-        n, C_, T = X.shape
-        if self.n_components > C_:
-            raise ValueError(f"n_components={self.n_components} exceeds the {C_} channels")
-        if C_ > MAX_CHANNELS:
-            raise NotImplementedError(f"{C_} channels: at most {MAX_CHANNELS} are provided")
-        if T < 1:
-            raise ValueError("X has no samples")
-        counts = np.bincount(yi, minlength=K)
-        # with trials of equal length, 'concat' (covariance of the class's concatenated trials) and 'epoch' (mean of
-        # the trial covariances) are the same number unless each trial is first divided by its trace
-        covs = np.zeros((K, C_, C_))
-        rows = max(1, COV_CHUNK_BYTES // (C_ * max(C_, T) * 8))
-        for s, xc in self._chunks(X, rows):
-            yc = yi[s:s + xc.shape[0]]
-            idx = np.argsort(yc, kind="stable")                  # the chunk's trials sorted by class
-            cnt = np.bincount(yc, minlength=K)
-            offs = np.concatenate([[0], np.cumsum(cnt)])
-            part = cov_group_mean(trial_covariances(xc), idx, offs, self.norm_trace).cpu().numpy()
-            covs += part * (cnt / counts)[:, None, None]         # chunks in order, fp64
-        filters, scores = decompose(covs, counts)
-        self.classes_, self.covs_ = classes, covs
-        self.filters_, self.scores_ = filters, scores
-        self.patterns_ = np.linalg.pinv(filters.T)
-        power = self._power(X, False)
-        power = power.double().cpu().numpy() if isinstance(power, torch.Tensor) else power
-        self.mean_, self.std_ = power.mean(0), power.std(0)
-        self.n_channels_ = C_
-        return self
-
-    def transform(self, X):
-        """X [n, C, T] -> [n, n_components]: log average power (``log`` None / True) or the z-scored average power
-        ``(power − mean_) / std_`` (``log=False``)."""
-        if not hasattr(self, "filters_"):
-            raise NotFittedError("this CSP instance is not fitted yet: call fit(X, y) before transform")
-        self._check_params()
-        X = self._check_X(X)
-        if X.shape[1] != self.n_channels_:
-            raise ValueError(f"X has {X.shape[1]} channels, fit saw {self.n_channels_}")
-        log = True if self.log is None else bool(self.log)
-        power = self._power(X, log)
-        if not log:
-            if isinstance(power, torch.Tensor):
-                mean = torch.as_tensor(self.mean_).to(power)
-                std = torch.as_tensor(self.std_).to(power)
-                power = (power - mean) / std
-            else:
-                power = (power - self.mean_) / self.std_
-        return power
-
-    def fit_transform(self, X, y=None, **fit_params):
-        return self.fit(X, y).transform(X)
+    def _chunk_power(self, xc, w, log):
+        return csp_power(xc, w[0], log)

@@ -18,22 +18,12 @@ import numpy as np
 import torch
 
 from . import _lib
-from .classifier import NotFittedError
+from ._estimator import Estimator, check_trials
 from .csp import COV_CHUNK_BYTES, cov_group_mean, trial_covariances
 
 MAX_COMPONENTS = 64                  # isd_ica_step_*: 1 <= m <= 64
 MAX_CHANNELS = 128                   # 1 <= C <= 128
 MAX_ROWS = 128                       # isd_spatial_apply_*: 1 <= R <= 128
-
-
-def _check_x(x):
-    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype in (torch.float32, torch.float64)):
-        raise TypeError("x must be a float32 or float64 CUDA tensor")
-    if x.ndim != 3:
-        raise ValueError(f"x must be [n, C, T], got {tuple(x.shape)}")
-    if not 1 <= x.shape[1] <= MAX_CHANNELS or x.shape[2] < 1:
-        raise ValueError(f"x [n, C, T] needs 1 <= C <= {MAX_CHANNELS} and T >= 1, got {tuple(x.shape)}")
-    return x.contiguous()
 
 
 def _like(a, x, shape, what):
@@ -48,7 +38,7 @@ def ica_step(x, U, b, work=None):
     (P [m, C], s [m], q [m]) as float64 CUDA tensors: with G = tanh(U x − b) per sample, P = Σ G xᵀ, s = Σ G,
     q = Σ (1 − G²) over all n·T samples.  One pass over x; bitwise repeatable.  ``work``: an optional uint8 CUDA
     scratch tensor to reuse between calls (``ica_step_work_bytes`` bytes)."""
-    x = _check_x(x)
+    x = _lib.check_cuda(x, "x", MAX_CHANNELS)
     n, Cc, T = x.shape
     U = torch.as_tensor(U)
     if U.ndim != 2 or U.shape[1] != Cc or not 1 <= U.shape[0] <= MAX_COMPONENTS:
@@ -65,7 +55,7 @@ def ica_step(x, U, b, work=None):
     P = torch.empty(m, Cc, dtype=torch.float64, device=x.device)
     s = torch.empty(m, dtype=torch.float64, device=x.device)
     q = torch.empty(m, dtype=torch.float64, device=x.device)
-    fn = _lib.lib().isd_ica_step_f32 if x.dtype == torch.float32 else _lib.lib().isd_ica_step_f64
+    fn = _lib.typed("isd_ica_step", x.dtype)
     with torch.cuda.device(x.device):
         _lib.check(fn(x.data_ptr(), U.data_ptr(), b.data_ptr(), P.data_ptr(), s.data_ptr(), q.data_ptr(),
                       work.data_ptr(), work.numel(), n, Cc, T, m, _lib.stream()))
@@ -83,7 +73,7 @@ def spatial_apply(x, M, bias=None, out=None):
     """x CUDA [n, C, T] (f32 / f64); M [R, C] (1 <= R <= 128), bias [R] or None (cast to x's dtype) -> [n, R, T] of
     x's dtype: out_i = M x_i + bias[:, None].  ``out``: an optional contiguous result tensor; it must not share memory
     with x (the kernel does not work in place)."""
-    x = _check_x(x)
+    x = _lib.check_cuda(x, "x", MAX_CHANNELS)
     n, Cc, T = x.shape
     M = torch.as_tensor(M)
     if M.ndim != 2 or M.shape[1] != Cc or not 1 <= M.shape[0] <= MAX_ROWS:
@@ -102,7 +92,7 @@ def spatial_apply(x, M, bias=None, out=None):
         if x0 < o0 + nbytes_o and o0 < x0 + nbytes_x:
             raise ValueError("out shares memory with x: spatial_apply does not work in place")
     if n:
-        fn = _lib.lib().isd_spatial_apply_f32 if x.dtype == torch.float32 else _lib.lib().isd_spatial_apply_f64
+        fn = _lib.typed("isd_spatial_apply", x.dtype)
         with torch.cuda.device(x.device):
             _lib.check(fn(x.data_ptr(), M.data_ptr(), None if bias is None else bias.data_ptr(), out.data_ptr(), n, Cc,
                           T, R, _lib.stream()))
@@ -166,7 +156,7 @@ def fastica(step, mean, scatter, N, m, w_init, tol=1e-4, max_iter=1000):
 
 
 # --------------------------------------------------------------------------------------------------- estimator
-class ICA:
+class ICA(Estimator):
     """FastICA for artifact removal with the argument names of ``mne.preprocessing.ICA``: fit on [n, C, T] trials,
     ``get_sources`` for the component time courses, ``apply`` to subtract the components in ``exclude``.
     ``n_components=None`` means every channel, ``max_iter='auto'`` 1000; ``fit_params`` takes ``tol`` (1e-4),
@@ -180,19 +170,6 @@ class ICA:
                  exclude=()):
         self.n_components, self.random_state, self.method = n_components, random_state, method
         self.fit_params, self.max_iter, self.exclude = fit_params, max_iter, exclude
-
-    def get_params(self, deep=True):
-        return {k: getattr(self, k) for k in self._param_names}
-
-    def set_params(self, **params):
-        for k, v in params.items():
-            if k not in self._param_names:
-                raise ValueError(f"invalid parameter {k!r} for {type(self).__name__}")
-            setattr(self, k, v)
-        return self
-
-    def __repr__(self):
-        return f"ICA({', '.join(f'{k}={getattr(self, k)!r}' for k in self._param_names)})"
 
     def _check_params(self):
         """-> (tol, w_init or None, max_iter)"""
@@ -233,13 +210,6 @@ class ICA:
         return tol, fp.get("w_init"), max_iter
 
     @staticmethod
-    def _check_X(X):
-        X, _ = _lib.check_array(X, "X")
-        if X.ndim != 3:
-            raise ValueError(f"X must be [n, C, T], got {tuple(X.shape)}")
-        return X
-
-    @staticmethod
     def _device(X):
         """X on the GPU: a CUDA tensor as it is (contiguous), an ndarray uploaded as float64."""
         return _lib.to_device(X, isinstance(X, torch.Tensor), "ICA")
@@ -258,7 +228,7 @@ class ICA:
     def fit(self, X, y=None):
         """X [n, C, T] (ndarray, or f32 / f64 CUDA tensor).  Returns self."""
         tol, w_init, max_iter = self._check_params()
-        X = self._check_X(X)
+        X = check_trials(X)
         n, C_, T = X.shape
         if n < 1 or T < 1:
             raise ValueError("X has no samples")
@@ -297,9 +267,8 @@ class ICA:
         return self
 
     def _fitted_X(self, X, what):
-        if not hasattr(self, "unmixing_"):
-            raise NotFittedError(f"this ICA instance is not fitted yet: call fit(X) before {what}")
-        X = self._check_X(X)
+        self._require_fitted("unmixing_", f"fit(X) before {what}")
+        X = check_trials(X)
         if X.shape[1] != self.n_channels_:
             raise ValueError(f"X has {X.shape[1]} channels, fit saw {self.n_channels_}")
         return X

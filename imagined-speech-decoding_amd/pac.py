@@ -132,7 +132,7 @@ def pac_launch(pha, amp, shifts, n_bins=18, surrogates_out=False):
         f64 = pha.dtype == torch.float64
         work = _lib.workspace(L.isd_pac_work_bytes(rows, P, A, T, int(f64)), pha.device)
         with torch.cuda.device(pha.device):
-            fn = L.isd_pac_f64 if f64 else L.isd_pac_f32
+            fn = _lib.typed("isd_pac", pha.dtype)
             _lib.check(fn(pha.data_ptr(), amp.data_ptr(), sd.data_ptr(), out.data_ptr(),
                           surr.data_ptr() if surrogates_out and S else None, rows, P, A, T, S, n_bins,
                           n_bins / (2.0 * np.pi), work.data_ptr(), _lib.stream()))

@@ -106,7 +106,7 @@ class WelchPlan(_lib.Handle):
             return out
         work = _lib.workspace(L.isd_psd_work_bytes(self._h, rows, T, int(f64)), x.device)
         with torch.cuda.device(x.device):
-            fn = L.isd_psd_welch_f64 if f64 else L.isd_psd_welch_f32
+            fn = _lib.typed("isd_psd_welch", x.dtype)
             _lib.check(fn(self._h, x.data_ptr(), out.data_ptr(), rows, T, int(bool(per_segment)), work.data_ptr(),
                           _lib.stream()))
         return out

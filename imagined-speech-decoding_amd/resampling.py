@@ -153,7 +153,7 @@ class Resampler(_lib.Handle):
         x2 = x.reshape(rows, T)
         with torch.cuda.device(x.device):
             bg = _background(x2, stat)
-            fn = _lib.lib().isd_resample_poly_f32 if x.dtype == torch.float32 else _lib.lib().isd_resample_poly_f64
+            fn = _lib.typed("isd_resample_poly", x.dtype)
             try:
                 _lib.check(fn(self._h, x2.data_ptr(), out.data_ptr(), rows, T, mode, cval,
                               bg.data_ptr() if bg is not None else None, _lib.stream()))

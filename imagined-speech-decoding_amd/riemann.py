@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .classifier import NotFittedError
+from ._estimator import Estimator, cat_like, check_trials, chunks, like, transformer_tags
 from .csp import COV_CHUNK_BYTES, MAX_CHANNELS, cov_group_mean, trial_covariances
 
 SPD_LOG, SPD_SQRT, SPD_INVSQRT, SPD_INV, SPD_NONE = range(5)     # ISD_SPD_* of include/isd_hip.h
@@ -26,28 +26,18 @@ _OUT = {"full": SPD_FULL, "tangent": SPD_TANGENT}
 
 
 # ----------------------------------------------------------------------------------------------------- low level
-def _check_stack(a, name):
-    if not (isinstance(a, torch.Tensor) and a.is_cuda and a.dtype in (torch.float32, torch.float64)):
-        raise TypeError(f"{name} must be a float32 or float64 CUDA tensor")
-    if a.ndim != 3 or a.shape[1] != a.shape[2]:
-        raise ValueError(f"{name} must be [n, C, C], got {tuple(a.shape)}")
-    if not 1 <= a.shape[1] <= MAX_CHANNELS:
-        raise ValueError(f"{name} [n, C, C] needs 1 <= C <= {MAX_CHANNELS}, got {tuple(a.shape)}")
-    return a.contiguous()
-
-
 def _device_stack(a, name="covs"):
     """[n, C, C] ndarray (uploaded as float64) or CUDA tensor -> checked contiguous CUDA tensor."""
     a, is_tensor = _lib.check_array(a, name)
     if a.ndim != 3 or a.shape[1] != a.shape[2]:
         raise ValueError(f"{name} must be [n, C, C], got {tuple(a.shape)}")
-    return _check_stack(_lib.to_device(a, is_tensor, "riemann"), name)
+    return _lib.check_cuda(_lib.to_device(a, is_tensor, "riemann"), name, MAX_CHANNELS, square=True)
 
 
 def congruence(cov, W, widx=None):
     """cov CUDA [n, C, C] (f32 / f64); W [K, C, C] or [C, C] (tensor or array, used as float64); widx [n] ints in
     [0, K) or None (then W[0] for every matrix) -> CUDA float64 [n, C, C]: W_k cov_i W_kᵀ, exactly symmetric."""
-    cov = _check_stack(cov, "cov")
+    cov = _lib.check_cuda(cov, "cov", MAX_CHANNELS, square=True)
     n, Cc, _ = cov.shape
     W = torch.as_tensor(W).to(device=cov.device, dtype=torch.float64)
     if W.ndim == 2:
@@ -113,7 +103,7 @@ def spd_function(a, fn, out="full", return_info=False):
         raise ValueError(f"fn={fn!r} (need one of {sorted(_FN)})")
     if out not in _OUT:
         raise ValueError(f"out={out!r} (need 'full' or 'tangent')")
-    a = _check_stack(a, "a").double()
+    a = _lib.check_cuda(a, "a", MAX_CHANNELS, square=True).double()
     res, _, info = _eigfun(a, _FN[fn], _OUT[out], False)
     if return_info:
         return res, info
@@ -124,7 +114,7 @@ def spd_function(a, fn, out="full", return_info=False):
 def spd_eigvalsh(a):
     """Eigenvalues of every matrix of a CUDA [n, C, C] stack of symmetric positive semi-definite matrices ->
     CUDA float64 [n, C], ascending."""
-    a = _check_stack(a, "a").double()
+    a = _lib.check_cuda(a, "a", MAX_CHANNELS, square=True).double()
     _, eig, info = _eigfun(a, SPD_NONE, SPD_NOOUT, True)
     _raise_on_failure(info)
     return torch.sort(eig, dim=1).values
@@ -274,49 +264,21 @@ def mean_riemann(covs, tol=1e-8, maxiter=50, init=None, sample_weight=None, grou
 
 
 # --------------------------------------------------------------------------------------------------- estimators
-class _Estimator:
-    """get_params / set_params / repr of the sklearn protocol over ``_param_names`` (the pattern of ``CSP``)."""
-    _param_names = ()
-
-    def get_params(self, deep=True):
-        return {k: getattr(self, k) for k in self._param_names}
-
-    def set_params(self, **params):
-        for k, v in params.items():
-            if k not in self._param_names:
-                raise ValueError(f"invalid parameter {k!r} for {type(self).__name__}")
-            setattr(self, k, v)
-        return self
-
-    def __repr__(self):
-        return f"{type(self).__name__}({', '.join(f'{k}={getattr(self, k)!r}' for k in self._param_names)})"
+class _Estimator(Estimator):
+    """What the estimators on [n, C, C] covariance stacks share beyond the protocol of ``Estimator``."""
 
     def _fitted(self, attr):
-        if not hasattr(self, attr):
-            raise NotFittedError(f"this {type(self).__name__} instance is not fitted yet: call fit before using it")
+        self._require_fitted(attr, "fit before using it")
 
     @staticmethod
     def _check_covs(X):
         """[n, C, C] ndarray or CUDA f32 / f64 tensor, checked but not moved."""
-        if isinstance(X, torch.Tensor):
-            if not X.is_cuda:
-                raise TypeError("tensor input must live on the GPU (there is no CPU fallback)")
-            if X.dtype not in (torch.float32, torch.float64):
-                raise TypeError("X must be float32 or float64")
-        else:
-            X = np.asarray(X)
-            if X.dtype.kind != "f":
-                raise TypeError("X must be floating point")
+        X, _ = _lib.check_array(X, "X")
         if X.ndim != 3 or X.shape[1] != X.shape[2]:
             raise ValueError(f"X must be [n, C, C], got {tuple(X.shape)}")
         if X.shape[1] > MAX_CHANNELS:
             raise NotImplementedError(f"{X.shape[1]} channels: at most {MAX_CHANNELS} are provided")
         return X
-
-    @staticmethod
-    def _like(res, X):
-        """A CUDA float64 result in X's kind: ndarray -> float64 ndarray, CUDA tensor -> tensor of X's dtype."""
-        return res.to(X.dtype) if isinstance(X, torch.Tensor) else res.cpu().numpy()
 
 
 class Covariances(_Estimator):
@@ -330,9 +292,7 @@ class Covariances(_Estimator):
         self.estimator = estimator
 
     def __sklearn_tags__(self):
-        from sklearn.utils import InputTags, Tags, TargetTags, TransformerTags
-        return Tags(estimator_type=None, target_tags=TargetTags(required=False), transformer_tags=TransformerTags(),
-                    input_tags=InputTags(three_d_array=True), requires_fit=False)
+        return transformer_tags(required_y=False, requires_fit=False)
 
     def _check_params(self):
         if self.estimator != "scm":
@@ -345,19 +305,15 @@ class Covariances(_Estimator):
         return self
 
     def transform(self, X):
-        from .csp import CSP
         self._check_params()
-        X = CSP._check_X(X)
+        X = check_trials(X)
         n, C_, T = X.shape
         if C_ > MAX_CHANNELS:
             raise NotImplementedError(f"{C_} channels: at most {MAX_CHANNELS} are provided")
         if C_ < 1 or T < 1:
             raise ValueError(f"X [n, C, T] needs C >= 1 and T >= 1, got {tuple(X.shape)}")
         rows = max(1, COV_CHUNK_BYTES // (C_ * max(C_, T) * 8))
-        parts = [trial_covariances(xc) for _, xc in CSP._chunks(X, rows)]
-        if isinstance(X, torch.Tensor):
-            return torch.cat(parts) if parts else torch.empty(0, C_, C_, dtype=X.dtype, device=X.device)
-        return torch.cat(parts).cpu().numpy() if parts else np.empty((0, C_, C_))
+        return cat_like([trial_covariances(xc) for _, xc in chunks(X, rows, "Covariances")], X, (C_, C_))
 
     def fit_transform(self, X, y=None, **fit_params):
         return self.fit(X, y).transform(X)
@@ -381,8 +337,7 @@ class CoSpectra(_Estimator):
 
     def transform(self, X):
         from .connectivity import csd_array_welch
-        from .csp import CSP
-        X = CSP._check_X(X)
+        X = check_trials(X)
         window = int(self.window)
         if not 0 <= self.overlap < 1:
             raise ValueError(f"overlap={self.overlap!r} (need 0 <= overlap < 1)")
@@ -408,9 +363,7 @@ class TangentSpace(_Estimator):
         self.metric, self.tsupdate = metric, tsupdate
 
     def __sklearn_tags__(self):
-        from sklearn.utils import InputTags, Tags, TargetTags, TransformerTags
-        return Tags(estimator_type=None, target_tags=TargetTags(required=False), transformer_tags=TransformerTags(),
-                    input_tags=InputTags(three_d_array=True))
+        return transformer_tags(required_y=False)
 
     def _check_params(self):
         if self.metric != "riemann":
@@ -430,7 +383,7 @@ class TangentSpace(_Estimator):
         X = self._check_covs(X)
         if X.shape[1] != self.reference_.shape[0]:
             raise ValueError(f"X has {X.shape[1]} channels, fit saw {self.reference_.shape[0]}")
-        return self._like(tangent_space(X, self.reference_), X)
+        return like(tangent_space(X, self.reference_), X)
 
     def fit_transform(self, X, y=None, sample_weight=None):
         return self.fit(X, y, sample_weight=sample_weight).transform(X)
@@ -497,7 +450,7 @@ class MDM(_Estimator):
 
     def transform(self, X):
         d, X = self._distances(X)
-        return self._like(d, X)
+        return like(d, X)
 
     def fit_transform(self, X, y, sample_weight=None):
         return self.fit(X, y, sample_weight=sample_weight).transform(X)
@@ -508,7 +461,7 @@ class MDM(_Estimator):
 
     def predict_proba(self, X):
         d, X = self._distances(X)
-        return self._like(torch.softmax(-d.square(), dim=1), X)
+        return like(torch.softmax(-d.square(), dim=1), X)
 
     def score(self, X, y, sample_weight=None):
         y = y.detach().cpu().numpy() if isinstance(y, torch.Tensor) else np.asarray(y)

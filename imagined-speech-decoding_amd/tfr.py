@@ -153,7 +153,7 @@ class TfrPlan(_lib.Handle):
             return out
         work = _lib.workspace(L.isd_tfr_work_bytes(self._h, n, Cn, T, m, int(f64)), x.device)
         with torch.cuda.device(x.device):
-            fn = L.isd_tfr_cwt_f64 if f64 else L.isd_tfr_cwt_f32
+            fn = _lib.typed("isd_tfr_cwt", x.dtype)
             _lib.check(fn(self._h, x.data_ptr(), out.data_ptr(), n, Cn, T, m, work.data_ptr(), _lib.stream()))
         return out
 
