@@ -44,6 +44,40 @@ bool zone_batch_open();             // a zone batch is recording on this thread 
 
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+#if defined(__HIPCC__)
+#define ISD_HOST_DEVICE __host__ __device__
+#else
+#define ISD_HOST_DEVICE
+#endif
+
+// Carver hands out the regions of one allocation front to back: a region starts where the one before it ended, rounded
+// up to `align` (a power of two), so two regions cannot overlap, and slack is a `take` of its own.  It counts whatever
+// unit its caller counts.  Every allocation with more than one region has ONE `*_layout` function that carves it: the
+// size that is asked for is that function's `end`, and every pointer into the allocation comes from the same struct.
+//   LdsCarver   dynamic LDS of a kernel (conv.hip): floats; the kernel and its host launch share the constexpr layout
+//   WorkCarver  a global workspace, host side: floats with align = 64 in the heads and conv.hip, bytes with
+//               align = 256 in the signal transforms.  The size query (`*_work_bytes`, `*_workspace_bytes`) returns
+//               `end`; the launch, which receives a bare pointer, addresses nothing else.
+template <typename I>
+struct Carver {
+  I end = 0;
+  ISD_HOST_DEVICE constexpr I take(I n, I align = 1) {
+    const I at = (end + align - 1) & ~(align - 1);
+    end = at + n;
+    return at;
+  }
+};
+using LdsCarver = Carver<int>;
+using WorkCarver = Carver<int64_t>;
+
+constexpr bool work_carver_ok() {   // disjoint, aligned, `end` as expected; empty regions take no room; 64-bit offsets
+  WorkCarver c, big{(int64_t)5 << 32};
+  const int64_t a = c.take(1, 256), b = c.take(257, 256), none = c.take(0, 256), slack = c.take(256);
+  return a == 0 && b == 256 && none == 768 && slack == 768 && c.end == 1024 && c.take(5) == 1024 && c.end == 1029 &&
+         big.take(3, 64) == ((int64_t)5 << 32) && big.take(1, 64) == ((int64_t)5 << 32) + 64;
+}
+static_assert(work_carver_ok(), "WorkCarver: a region starts at the aligned end of the one before it");
+
 // ------------------------------------------------------------------ device side
 #if defined(__HIPCC__)
 

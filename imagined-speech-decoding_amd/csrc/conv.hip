@@ -35,17 +35,9 @@ struct ZoneDesc {
 // Dynamic LDS.  Every kernel of this file that takes a dynamic allocation has ONE constexpr `*_layout` function: the
 // kernel takes its pointers and LDS addresses from the struct it returns, the host takes the allocation's size from the
 // same struct's `end`, and static_asserts (in front of choose_route) check it for every shape the kernel's route admits.
-// LdsCarver hands out the regions front to back: a region starts where the one before it ended (rounded up to `align`,
-// a power of two: the mask is the `(x + 3) & ~3` the kernels always used), so two regions cannot overlap, and slack is
-// a `take` of its own.
-struct LdsCarver {
-  int end = 0;
-  __host__ __device__ constexpr int take(int n, int align = 1) {
-    const int at = (end + align - 1) & ~(align - 1);
-    end = at + n;
-    return at;
-  }
-};
+// LdsCarver (common.h) hands out the regions front to back: a region starts where the one before it ended (rounded up
+// to `align`, a power of two: the mask is the `(x + 3) & ~3` the kernels always used), so two regions cannot overlap,
+// and slack is a `take` of its own.
 constexpr int kLdsWorkgroup = 160 * 1024;   // what the CU has, and the most one workgroup can take
 constexpr int kLdsRoute = 150 * 1024;       // what the large-tile routes allow themselves of it
 constexpr int kLdsTwoPerCu = 80 * 1024;     // half of the CU: two workgroups fit side by side
@@ -3974,6 +3966,20 @@ enum class Route { kLayerwise, kFusedF32, kFusedBf16 };
 // 25.6 ms/step, 16 waves 25.6, 4 waves 28.3)
 constexpr int kFusedNW = 8;
 
+// The fused backward's partial sums (floats), back to back from `at`: per workgroup four slabs for cnn4 and four for
+// cnn3 (the bf16 kernel's count; the fp32 kernel fills two of each), then one Weff slab per wave (the fp32 kernel fills
+// four).  make_geo reserves this at the most workgroups a zone can get and cuts it again at the route's own count.
+struct FusedBwdParts { int64_t part4, part3, part0, end; };
+FusedBwdParts fused_bwd_layout(int64_t at, int64_t per_zone, int64_t slab1, int64_t slab0) {
+  WorkCarver c{at};
+  FusedBwdParts l;
+  l.part4 = c.take(per_zone * 4 * slab1);
+  l.part3 = c.take(per_zone * 4 * slab1);
+  l.part0 = c.take(per_zone * kFusedNW * slab0);
+  l.end = c.end;
+  return l;
+}
+
 struct Geo {           // derived sizes for one call
   int N, T1, TT, IPW, RS_a, RS_b, lin0, CK;
   int64_t items, act;  // act = floats of one activation tensor
@@ -3981,6 +3987,7 @@ struct Geo {           // derived sizes for one call
   int64_t o_eff, o_eff16, o_beff, o_w3, o_w3t, o_w4, o_w4t, o_a2, o_a3, o_a4, o_s, o_wg, o_wg34, o_part, total;
   int ipw0, ipw1, ns0, ns1, cw0, cw1, grp0, grp1;   // wgrad: items per wg, slabs (incl. wave groups), channels per wg
   int64_t slab0, slab1;
+  FusedBwdParts bwd_part = {};              // fused routes: the cut of o_part
   Route route = Route::kLayerwise;
   int fwd_per_zone = 0, bwd_per_zone = 0;   // fused routes: workgroups per zone
   size_t fwd_lds = 0, bwd_lds = 0;          // fused routes: dynamic LDS bytes
@@ -4181,19 +4188,20 @@ int make_geo(const isd_conv4_plan* p, int64_t B, int64_t T, Geo& g) {
     int64_t want = occ < min_ipw ? min_ipw : occ;
     if (g.IPW > want) g.IPW = (int)want;
   }
-  int64_t o = 0;
-  g.o_eff = o;  o += align_up(p->eff_size, 64);
-  g.o_eff16 = o; o += align_up(p->eff_size / kTaps * 4, 64);      // bf16 tap-window fragments: 16 bytes per (cg, gt, lane)
-  g.o_beff = o; o += align_up((int64_t)p->Z * p->F, 64);
-  const int64_t cw = align_up(p->conv_zstride * p->Z, 64);
-  g.o_w3 = o; o += cw; g.o_w3t = o; o += cw; g.o_w4 = o; o += cw; g.o_w4t = o; o += cw;
-  g.o_a2 = o; o += align_up(g.act, 64);
-  g.o_a3 = o; o += align_up(g.act, 64);
-  g.o_a4 = o; o += align_up(g.act, 64);
-  g.o_s = o;  o += align_up(g.act, 64);
-  g.o_wg = o; o += align_up(p->wg_size, 64);
+  WorkCarver c;                                                   // floats; every region on a 256-byte line
+  auto take = [&](int64_t n) { return c.take(n, 64); };
+  g.o_eff = take(p->eff_size);
+  g.o_eff16 = take(p->eff_size / kTaps * 4);                      // bf16 tap-window fragments: 16 bytes per (cg, gt, lane)
+  g.o_beff = take((int64_t)p->Z * p->F);
+  const int64_t cw = p->conv_zstride * p->Z;
+  g.o_w3 = take(cw); g.o_w3t = take(cw); g.o_w4 = take(cw); g.o_w4t = take(cw);
+  g.o_a2 = take(g.act);
+  g.o_a3 = take(g.act);
+  g.o_a4 = take(g.act);
+  g.o_s = take(g.act);
+  g.o_wg = take(p->wg_size);
   g.slab1 = (int64_t)p->Z * p->F * p->F * kTaps;
-  g.o_wg34 = o; o += align_up(g.slab1, 64);
+  g.o_wg34 = take(g.slab1);
   // wgrad slabs: ~1024 workgroups over (item ranges) x zones x channel groups
   auto plan_wg = [&](int cin_max, int& cw, int& ipw, int& ns, int& grp) {
     cw = cin_max >= 64 ? 64 : (int)align_up(cin_max, 16);
@@ -4212,11 +4220,18 @@ int make_geo(const isd_conv4_plan* p, int64_t B, int64_t T, Geo& g) {
   const int64_t pa = (int64_t)g.ns0 * g.slab0, pb = (p->n_layers == 4) ? (int64_t)g.ns1 * g.slab1 : 0;
   // fused backward (reference-native shape): one workgroup row of max(1, 256/Z) per zone, 4 + 4 + 8 slabs each
   const int64_t rz = 256 / p->Z > 1 ? 256 / p->Z : 1;
-  const int64_t pf = (p->n_layers == 4) ? rz * (8 * g.slab1 + 8 * g.slab0) : 0;
+  const int64_t pf = (p->n_layers == 4) ? fused_bwd_layout(0, rz, g.slab1, g.slab0).end : 0;
   const int64_t pmax = pa > pb ? pa : pb;
-  g.o_part = o; o += align_up(pmax > pf ? pmax : pf, 64);
-  g.total = o;
-  return choose_route(p, g);
+  g.o_part = take(pmax > pf ? pmax : pf);
+  take(0);                                                        // the size counts whole lines
+  g.total = c.end;
+  if (int rc = choose_route(p, g)) return rc;
+  if (g.route != Route::kLayerwise) {   // the route's own workgroup count: its slabs are cut from o_part and end inside it
+    g.bwd_part = fused_bwd_layout(g.o_part, g.bwd_per_zone, g.slab1, g.slab0);
+    ISD_CHECK_ARG(g.bwd_part.end <= g.total, "conv4: the fused backward's slabs need %lld floats, %lld are reserved",
+                  (long long)(g.bwd_part.end - g.o_part), (long long)(g.total - g.o_part));
+  }
+  return ISD_OK;
 }
 
 // the geometry fields that ConvArgs, WgradArgs, FusedFwdArgs and FusedBwdArgs share under the same names
@@ -4253,17 +4268,13 @@ FusedFwdArgs make_fused_fwd_args(const isd_conv4_plan* p, const Geo& g, const fl
   fa.store = g.keep_dgelu ? 2 : 1;
   return fa;
 }
-// the partial sums lie back to back: part4 and part3 in four slabs per workgroup (the bf16 kernel's count; the fp32
-// kernel fills two of them), then part0
 FusedBwdArgs make_fused_bwd_args(const isd_conv4_plan* p, const Geo& g, const float* x, const float* dfeat, float* ws,
                                  int64_t T) {
   FusedBwdArgs fb = {};
   fill_fused_geometry(fb, p, g, T);
   fb.x = x; fb.dfeat = dfeat; fb.a2 = ws + g.o_a2; fb.a3 = ws + g.o_a3; fb.a4 = ws + g.o_a4;
   fb.w3t = ws + g.o_w3t; fb.w4t = ws + g.o_w4t;
-  fb.part4 = ws + g.o_part;
-  fb.part3 = fb.part4 + (int64_t)g.bwd_per_zone * 4 * g.slab1;
-  fb.part0 = fb.part3 + (int64_t)g.bwd_per_zone * 4 * g.slab1;
+  fb.part4 = ws + g.bwd_part.part4; fb.part3 = ws + g.bwd_part.part3; fb.part0 = ws + g.bwd_part.part0;
   fb.slab1 = g.slab1; fb.slab0 = g.slab0;
   return fb;
 }

@@ -298,7 +298,7 @@ namespace {
 
 struct CsdLayout {
   int64_t S_, nc;                // segments per trial; trials per chunk
-  int64_t means_b, z_b, part_b, acc_b;
+  int64_t means, z, part, acc, slack, end;   // byte offsets into the workspace; part and acc are empty without over_trials
   int zr_max;                    // over_trials: ranges of a full chunk, the most any chunk has ...
   int64_t per;                   // ... because every chunk is cut into ranges of this many pairs
 };
@@ -319,22 +319,30 @@ CsdSplit csd_split(int K, int C, int64_t P) {
 }
 
 CsdLayout csd_layout(const isd_psd_plan* p, int64_t n, int64_t C, int64_t T, int over_trials, int is_f64) {
-  CsdLayout L;
+  CsdLayout L = {};
+  WorkCarver c;
   const int64_t el = is_f64 ? 8 : 4;
   L.S_ = psd_segments(p, T);
+  if (n == 0 || L.S_ == 0) {
+    L.slack = c.take(256);                                       // never a zero-byte buffer
+    L.end = c.end;
+    return L;
+  }
   const int64_t per_trial = C * L.S_ * 8 + (int64_t)p->K * 2 * L.S_ * C * el;
   L.nc = std::max<int64_t>(1, std::min<int64_t>(n, g_csd_chunk_bytes / std::max<int64_t>(per_trial, 1)));
   L.nc = std::min<int64_t>(L.nc, (1LL << 30) / std::max<int64_t>(1, std::max<int64_t>(C, 2 * L.S_)));
-  L.means_b = psd_align(L.nc * C * L.S_ * 8);
-  L.z_b = psd_align((int64_t)p->K * L.nc * 2 * L.S_ * C * el);
+  L.means = c.take(L.nc * C * L.S_ * 8, 256);
+  L.z = c.take((int64_t)p->K * L.nc * 2 * L.S_ * C * el, 256);
   const int64_t E = (int64_t)p->K * C * C * 2;
   // The split is taken once, from a full chunk, and a shorter last chunk is cut into ranges of the same length: it
   // then has no more ranges than `part` holds (a split of its own can have more: the count is not monotone in P).
   const CsdSplit full = csd_split(p->K, (int)C, L.nc * L.S_);
   L.zr_max = over_trials ? full.Zr : 0;
   L.per = full.per;
-  L.part_b = over_trials ? psd_align(L.zr_max * E * el) : 0;
-  L.acc_b = over_trials ? psd_align(E * el) : 0;
+  L.part = c.take(over_trials ? L.zr_max * E * el : 0, 256);
+  L.acc = c.take(over_trials ? E * el : 0, 256);
+  L.slack = c.take(256, 256);
+  L.end = c.end;
   return L;
 }
 
@@ -356,10 +364,10 @@ int csd_launch(const isd_psd_plan* p, const S* x, S* out, int64_t n, int64_t C, 
   const S* scale = f64 ? (const S*)p->d_scale64 : (const S*)p->d_scale32;
   const int np = f64 ? p->np64 : p->np32;
   char* wb = static_cast<char*>(work);
-  double* means = reinterpret_cast<double*>(wb);
-  S* Z = reinterpret_cast<S*>(wb + L.means_b);
-  S* part = reinterpret_cast<S*>(wb + L.means_b + L.z_b);
-  S* acc = reinterpret_cast<S*>(wb + L.means_b + L.z_b + L.part_b);
+  double* means = reinterpret_cast<double*>(wb + L.means);
+  S* Z = reinterpret_cast<S*>(wb + L.z);
+  S* part = reinterpret_cast<S*>(wb + L.part);
+  S* acc = reinterpret_cast<S*>(wb + L.acc);
   const int K = p->K, Ci = (int)C;
   const int nct = (Ci + 15) / 16, ntp = nct * (nct + 1) / 2;
   const int64_t E = (int64_t)K * C * C * 2;
@@ -431,9 +439,7 @@ extern "C" int64_t isd_csd_work_bytes(const isd_psd_plan* p, int64_t n, int64_t 
     set_error("isd_csd_work_bytes: null plan, n=%lld or C=%lld", (long long)n, (long long)C);
     return ISD_ERR_INVALID;
   }
-  if (n == 0 || psd_segments(p, T) == 0) return 256;             // never a zero-byte buffer
-  const CsdLayout L = csd_layout(p, n, C, T, over_trials, is_f64);
-  return L.means_b + L.z_b + L.part_b + L.acc_b + 256;
+  return csd_layout(p, n, C, T, over_trials, is_f64).end;
 }
 
 extern "C" int isd_csd_welch_f32(const isd_psd_plan* plan, const float* x, float* out, int64_t n, int64_t C, int64_t T,

@@ -1728,8 +1728,6 @@ struct isd_eegnet_plan {
   int xdt;         // element type of x: ISD_ACT_F32 or ISD_ACT_BF16 (isd_eegnet_plan_set_input_dtype)
 };
 
-static inline int64_t al64(int64_t v) { return (v + 63) / 64 * 64; }
-
 static int eeg_plan_create(isd_eegnet_plan** out, int in_channels, int feature_dim, int kernel_length, int T, int cv);
 
 extern "C" int isd_eegnet_plan_create(isd_eegnet_plan** out, int in_channels, int feature_dim, int kernel_length,
@@ -1809,28 +1807,29 @@ struct EegWs {          // float offsets into the workspace
 };
 EegWs eeg_layout(const isd_eegnet_plan* p, int64_t B) {
   EegWs w;
-  int64_t o = 0;
-  w.stats = o; o += al64((int64_t)(sizeof(EegStats) + 3) / 4);
-  w.coef = o; o += al64((int64_t)(sizeof(EegCoef) + 3) / 4);
-  w.z = o; o += al64(B * kF2 * p->T);
-  w.u = o; o += al64(B * kF2 * p->Tp);
-  w.p2 = o; o += al64(B * kF2 * p->T2);
-  w.a4 = o; o += al64(B * kF2 * p->T2p);
+  WorkCarver c;
+  auto take = [&](int64_t n) { return c.take(n, 64); };           // every region on a 256-byte line
+  w.stats = take((int64_t)(sizeof(EegStats) + 3) / 4);
+  w.coef = take((int64_t)(sizeof(EegCoef) + 3) / 4);
+  w.z = take(B * kF2 * p->T);
+  w.u = take(B * kF2 * p->Tp);
+  w.p2 = take(B * kF2 * p->T2);
+  w.a4 = take(B * kF2 * p->T2p);
   const int64_t npool = B * kF2 * (p->cv ? p->T3 : 1);
-  w.pooled = o; o += al64(npool);
-  w.dpooled = o; o += al64(npool);
-  w.a3 = o; o += al64(B * kF2 * p->T2p);
-  w.da4 = o; o += al64(B * kF2 * p->T2p);
-  w.da3 = o; o += al64(B * kF2 * p->T2p);
-  w.dy2 = o; o += al64(B * kF2 * p->Tp);
-  w.v = o; o += al64(B * kF2 * p->T);
+  w.pooled = take(npool);
+  w.dpooled = take(npool);
+  w.a3 = take(B * kF2 * p->T2p);
+  w.da4 = take(B * kF2 * p->T2p);
+  w.da3 = take(B * kF2 * p->T2p);
+  w.dy2 = take(B * kF2 * p->Tp);
+  w.v = take(B * kF2 * p->T);
   w.n_slabs = 1024;
   const int64_t slab = p->cv && kF2 * kK2 > p->C ? kF2 * kF2 * kK2 : kF2 * p->C;
-  w.part = o; o += al64((int64_t)w.n_slabs * slab);
-  w.lin = o; o += al64(isd_linear_workspace_bytes(B, kF2 * (p->cv ? p->T3 : 1), p->F) / 4 + 64);
-  w.w3f = o; o += p->cv ? kF2 * kF2 * kK2 : 0;
-  w.w3b = o; o += p->cv ? kF2 * kF2 * kK2 : 0;
-  w.total = o;
+  w.part = take((int64_t)w.n_slabs * slab);
+  w.lin = take(isd_linear_workspace_bytes(B, kF2 * (p->cv ? p->T3 : 1), p->F) / 4 + 64);   // the query's floats and 64 of slack
+  w.w3f = take(p->cv ? kF2 * kF2 * kK2 : 0);                      // empty, and still whole lines, without conv3
+  w.w3b = take(p->cv ? kF2 * kF2 * kK2 : 0);
+  w.total = c.end;
   return w;
 }
 }  // namespace

@@ -246,7 +246,17 @@ using namespace isd;
 
 namespace {
 
-int64_t env_stats_bytes(int64_t n, int64_t C) { return cdiv(n * C * 2 * 8, 256) * 256; }
+// The workspace in bytes: two fp64 statistics per row, then the prepass's W (two values per sample).
+struct EnvWs { int64_t stats, W, slack, end; };
+EnvWs env_layout(int64_t n, int64_t C, int64_t T, int64_t el) {
+  EnvWs l;
+  WorkCarver c;
+  l.stats = c.take(n * C * 2 * 8, 256);
+  l.W = c.take(n * C * T * 2 * el, 256);
+  l.slack = c.take(256);                                          // never a zero-byte buffer
+  l.end = c.end;
+  return l;
+}
 
 template <typename S>
 int envcorr_launch(const S* z, S* out, int64_t n, int64_t C, int64_t T, int flags, void* work, void* stream,
@@ -263,8 +273,9 @@ int envcorr_launch(const S* z, S* out, int64_t n, int64_t C, int64_t T, int flag
                       "%s: n=%lld trials of %lld channels are more workgroups than one launch holds", who,
                       (long long)n, (long long)C);
   hipStream_t st = (hipStream_t)stream;
-  double* stats = static_cast<double*>(work);
-  S* W = reinterpret_cast<S*>(static_cast<char*>(work) + env_stats_bytes(n, C));
+  const EnvWs l = env_layout(n, C, T, sizeof(S));
+  double* stats = reinterpret_cast<double*>(static_cast<char*>(work) + l.stats);
+  S* W = reinterpret_cast<S*>(static_cast<char*>(work) + l.W);
   const int64_t rows = n * C;
   const dim3 rgrid((unsigned)cdiv(rows, kEnvRowWaves)), rblock(64 * kEnvRowWaves);
   if (flags & kEnvLog)
@@ -294,7 +305,7 @@ extern "C" int64_t isd_envcorr_work_bytes(int64_t n, int64_t C, int64_t T, int i
     set_error("isd_envcorr_work_bytes: n=%lld, C=%lld or T=%lld", (long long)n, (long long)C, (long long)T);
     return ISD_ERR_INVALID;
   }
-  return env_stats_bytes(n, C) + n * C * T * 2 * (is_f64 ? 8 : 4) + 256;   // never a zero-byte buffer
+  return env_layout(n, C, T, is_f64 ? 8 : 4).end;
 }
 
 extern "C" int isd_envcorr_f32(const float* z, float* out, int64_t n, int64_t C, int64_t T, int flags, void* work,

@@ -322,11 +322,23 @@ static int wgrad_slabs(int64_t M, int* m_per_wg) {
   return (int)cdiv(M, per);
 }
 
+// The workspace of isd_linear_backward, in floats.  The documented size is M*N + slabs*N*(K+1) + 64 floats: up to 63 of
+// the 64 are the padding in front of `part`, the rest is slack (never a zero-byte buffer).
+struct LinearWs { int64_t dpre, part, slack, end; int slabs, m_per_wg; };
+static LinearWs linear_layout(int64_t M, int K, int N) {
+  LinearWs l;
+  l.slabs = wgrad_slabs(M > 0 ? M : 1, &l.m_per_wg);
+  WorkCarver c;
+  l.dpre = c.take(M * N, 64);
+  l.part = c.take((int64_t)l.slabs * N * (K + 1), 64);
+  l.slack = c.take(64 - (l.part - M * N));
+  l.end = c.end;
+  return l;
+}
+
 extern "C" int64_t isd_linear_workspace_bytes(int64_t M, int K, int N) {
   if (M < 0 || K < 1 || N < 1) return ISD_ERR_INVALID;
-  int mp;
-  const int slabs = wgrad_slabs(M > 0 ? M : 1, &mp);
-  return 4 * (M * N + (int64_t)slabs * N * (K + 1)) + 256;
+  return linear_layout(M, K, N).end * 4;
 }
 
 extern "C" int isd_linear_backward(const float* x, const float* w, const float* dy, const float* pre, float* dx,
@@ -342,8 +354,9 @@ extern "C" int isd_linear_backward(const float* x, const float* w, const float* 
     return ISD_OK;
   }
   ISD_CHECK_ARG(x && w && dy && workspace, "isd_linear_backward: null argument");
-  float* dpre = (float*)workspace;
-  float* part = dpre + ((M * N + 63) / 64) * 64;
+  const LinearWs l = linear_layout(M, K, N);
+  float* dpre = (float*)workspace + l.dpre;
+  float* part = (float*)workspace + l.part;
   const float* dsrc = dy;
   if (act) {
     ISD_ZLAUNCH(act_bwd_kernel, dim3((unsigned)(cdiv(M * N, 256) < 4096 ? cdiv(M * N, 256) : 4096)), dim3(256), 0,
@@ -355,8 +368,7 @@ extern "C" int isd_linear_backward(const float* x, const float* w, const float* 
     int rc = launch_linear(dsrc, w, nullptr, dx, nullptr, M, N, K, 1, K, 0, st);
     if (rc) return rc;
   }
-  int mp;
-  const int slabs = wgrad_slabs(M, &mp);
+  const int slabs = l.slabs, mp = l.m_per_wg;
   ISD_ZLAUNCH(linear_wgrad_kernel, dim3(slabs, (unsigned)cdiv(K + 1, 64), (unsigned)cdiv(N, 64)), dim3(256), 0,
                      st, dsrc, x, part, M, K, N, mp);
   {
@@ -375,9 +387,21 @@ extern "C" int isd_linear_backward(const float* x, const float* w, const float* 
   return ISD_OK;
 }
 
+// The workspace of isd_softmax_ce's loss reduction, in bytes: the arrival ticket on a line of its own, then one partial
+// sum per workgroup.
+struct SoftmaxCeWs { int64_t ticket, part, end; };
+static SoftmaxCeWs softmax_ce_layout(int64_t B) {
+  SoftmaxCeWs l;
+  WorkCarver c;
+  l.ticket = c.take(256);
+  l.part = c.take(4 * cdiv(B > 0 ? B : 1, 256), 256);
+  l.end = c.end;
+  return l;
+}
+
 extern "C" int64_t isd_softmax_ce_workspace_bytes(int64_t B) {
   if (B < 0) return ISD_ERR_INVALID;
-  return 256 + 4 * cdiv(B > 0 ? B : 1, 256);
+  return softmax_ce_layout(B).end;
 }
 
 extern "C" int isd_softmax_ce(const float* logits_tok, const void* labels, int label_bytes, float* logits_mean,
@@ -395,13 +419,15 @@ extern "C" int isd_softmax_ce(const float* logits_tok, const void* labels, int l
     if (want_loss) ISD_HIP_TRY(zone_clear(loss, sizeof(float), st));
     return ISD_OK;
   }
-  float* scratch = want_loss ? (float*)workspace : nullptr;
+  const SoftmaxCeWs l = softmax_ce_layout(B);
+  unsigned int* ticket = want_loss ? reinterpret_cast<unsigned int*>((char*)workspace + l.ticket) : nullptr;
+  float* part = want_loss ? reinterpret_cast<float*>((char*)workspace + l.part) : nullptr;
   // arrival ticket of the cross-workgroup loss sum (a single workgroup needs none: at the reference's batch of 64 the
   // clear was a 5-us node of the replayed step)
-  if (scratch && cdiv(B, 256) > 1) ISD_HIP_TRY(zone_clear(scratch, sizeof(unsigned int), st));
+  if (ticket && cdiv(B, 256) > 1) ISD_HIP_TRY(zone_clear(ticket, sizeof(unsigned int), st));
   ISD_ZLAUNCH(softmax_ce_kernel, dim3((unsigned)cdiv(B, 256)), dim3(256), 0, st, logits_tok, labels, label_bytes,
                      logits_mean, want_loss ? loss : nullptr, labels ? dlogits_tok : nullptr, pred, B, n_tok, n_cls,
-                     grad_scale, scratch ? scratch + 64 : nullptr, reinterpret_cast<unsigned int*>(scratch));
+                     grad_scale, part, ticket);
   ISD_LAUNCH_CHECK();
   return ISD_OK;
 }

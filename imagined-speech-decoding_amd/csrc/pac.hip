@@ -297,12 +297,22 @@ using namespace isd;
 
 namespace {
 
-int64_t pac_align(int64_t b) { return cdiv(b, 256) * 256; }
 int64_t pac_padded(int64_t T) { return cdiv(T, kPacBlock) * kPacBlock; }
-int64_t pac_cs_bytes(int64_t n_rp, int64_t T, int f64) { return pac_align(n_rp * pac_padded(T) * 2 * (f64 ? 8 : 4)); }
-int64_t pac_ti_bytes(int64_t n_rp, int64_t T) { return pac_align(n_rp * pac_padded(T) * 4); }
-int64_t pac_off_bytes(int64_t n_rp) { return pac_align(n_rp * (kPacMaxBins + 1) * 4); }
-int64_t pac_order_bytes() { return pac_align((kPacMaxSurr + 1) * 4); }
+
+// The workspace in bytes: per (row, p) the ranked (cos, sin) records, their sample indices and the bin offsets; then the
+// surrogates' order, whose whole lines also keep the buffer from being empty.
+struct PacWs { int64_t cs, ti, off, order, end; };
+PacWs pac_layout(int64_t n_rp, int64_t T, int64_t el) {
+  static_assert((kPacMaxSurr + 1) * 4 % 256 == 0, "`order` ends on a line: the size is in whole lines");
+  PacWs l;
+  WorkCarver c;
+  l.cs = c.take(n_rp * pac_padded(T) * 2 * el, 256);
+  l.ti = c.take(n_rp * pac_padded(T) * 4, 256);
+  l.off = c.take(n_rp * (kPacMaxBins + 1) * 4, 256);
+  l.order = c.take((kPacMaxSurr + 1) * 4, 256);
+  l.end = c.end;
+  return l;
+}
 
 template <typename S>
 int pac_launch(const S* pha, const S* amp, const int32_t* shifts, S* out, S* surr, int64_t rows, int64_t P, int64_t A,
@@ -324,12 +334,12 @@ int pac_launch(const S* pha, const S* amp, const int32_t* shifts, S* out, S* sur
   ISD_CHECK_ARG(pha && amp && shifts && out && work, "%s: null argument", who);
   hipStream_t st = (hipStream_t)stream;
   const int64_t n_rp = rows * P;
-  const int f64 = sizeof(S) == 8;
+  const PacWs l = pac_layout(n_rp, T, sizeof(S));
   char* w = static_cast<char*>(work);
-  S* cs = reinterpret_cast<S*>(w);
-  int* ti = reinterpret_cast<int*>(w += pac_cs_bytes(n_rp, T, f64));
-  int* off = reinterpret_cast<int*>(w += pac_ti_bytes(n_rp, T));
-  int* order = reinterpret_cast<int*>(w += pac_off_bytes(n_rp));
+  S* cs = reinterpret_cast<S*>(w + l.cs);
+  int* ti = reinterpret_cast<int*>(w + l.ti);
+  int* off = reinterpret_cast<int*>(w + l.off);
+  int* order = reinterpret_cast<int*>(w + l.order);
   const int Tp = (int)pac_padded(T);
   hipLaunchKernelGGL((pac_sort_kernel<S>), dim3((unsigned)cdiv(n_rp, kPacSortWaves)), dim3(64 * kPacSortWaves), 0, st,
                      pha, cs, ti, off, n_rp, (int)T, Tp, n_bins, c);
@@ -350,8 +360,7 @@ extern "C" int64_t isd_pac_work_bytes(int64_t rows, int64_t P, int64_t A, int64_
               (long long)T);
     return T > kPacMaxT ? ISD_ERR_UNSUPPORTED : ISD_ERR_INVALID;
   }
-  const int64_t n_rp = rows * P;
-  return pac_cs_bytes(n_rp, T, is_f64) + pac_ti_bytes(n_rp, T) + pac_off_bytes(n_rp) + pac_order_bytes();
+  return pac_layout(rows * P, T, is_f64 ? 8 : 4).end;
 }
 
 extern "C" int isd_pac_f32(const float* pha, const float* amp, const int32_t* shifts, float* out, float* surr,

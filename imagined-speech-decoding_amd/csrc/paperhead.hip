@@ -420,8 +420,6 @@ struct isd_paperhead_plan {
   PhGeo g;
 };
 
-static inline int64_t ph_al64(int64_t v) { return (v + 63) / 64 * 64; }
-
 extern "C" int isd_paperhead_plan_create(isd_paperhead_plan** out, int in_channels, int feature_dim, int T) {
   ISD_CHECK_ARG(out, "isd_paperhead_plan_create: null argument");
   ISD_CHECK_ARG(in_channels >= 1 && in_channels <= 4096, "isd_paperhead_plan_create: in_channels=%d", in_channels);
@@ -483,26 +481,27 @@ struct PhWs {
 };
 PhWs ph_layout(const PhGeo& g, int64_t B) {
   PhWs w;
-  int64_t o = 0;
-  w.stats = o; o += ph_al64((int64_t)(sizeof(PhStats) + 3) / 4);
-  w.coef = o; o += ph_al64((int64_t)(sizeof(PhCoef) + 3) / 4);
-  w.beff = o; o += 64;
+  WorkCarver c;
+  auto take = [&](int64_t n) { return c.take(n, 64); };           // every region on a 256-byte line
+  w.stats = take((int64_t)(sizeof(PhStats) + 3) / 4);
+  w.coef = take((int64_t)(sizeof(PhCoef) + 3) / 4);
+  w.beff = take(64);
   int64_t max_w = 0;
   for (int l = 0; l < 4; ++l) {
-    w.wf[l] = o; o += ph_al64((int64_t)g.Ci[l] * 3 * g.Fp[l]);
-    w.wb[l] = o; o += ph_al64((int64_t)g.Fo[l] * 3 * g.Cp[l]);
-    w.y[l] = o; o += ph_al64(B * g.Fo[l] * g.To[l]);
-    w.a[l] = o; o += ph_al64(B * g.Fo[l] * g.Tp[l]);
-    w.dy[l] = o; o += ph_al64(B * g.Fo[l] * g.To[l]);
-    w.da[l] = o; o += ph_al64(B * g.Fo[l] * g.Tp[l]);
+    w.wf[l] = take((int64_t)g.Ci[l] * 3 * g.Fp[l]);
+    w.wb[l] = take((int64_t)g.Fo[l] * 3 * g.Cp[l]);
+    w.y[l] = take(B * g.Fo[l] * g.To[l]);
+    w.a[l] = take(B * g.Fo[l] * g.Tp[l]);
+    w.dy[l] = take(B * g.Fo[l] * g.To[l]);
+    w.da[l] = take(B * g.Fo[l] * g.Tp[l]);
     const int64_t nw = (int64_t)g.Fo[l] * g.Ci[l] * 3;
     if (nw > max_w) max_w = nw;
   }
-  w.part = o; o += ph_al64((int64_t)kPhSlabs * max_w);
-  w.pbias = o; o += ph_al64((int64_t)kPhSlabs * kPhMaxF);
-  w.dweff = o; o += ph_al64((int64_t)g.Fo[0] * g.C * 3);
-  w.dbeff = o; o += 64;
-  w.total = o;
+  w.part = take((int64_t)kPhSlabs * max_w);
+  w.pbias = take((int64_t)kPhSlabs * kPhMaxF);
+  w.dweff = take((int64_t)g.Fo[0] * g.C * 3);
+  w.dbeff = take(64);
+  w.total = c.end;
   return w;
 }
 }  // namespace

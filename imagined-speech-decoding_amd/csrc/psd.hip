@@ -201,6 +201,26 @@ PsdSplit psd_split(const isd_psd_plan* p, int64_t rows, int64_t S_) {
   return sp;
 }
 
+// The workspace in bytes: the fp64 segment means, then (when the segments are split over z) each z's partial spectra.
+struct PsdWs {
+  int64_t means, part, slack, end;
+  PsdSplit sp;
+};
+PsdWs psd_layout(const isd_psd_plan* p, int64_t rows, int64_t S_, int64_t el) {
+  PsdWs l = {};
+  WorkCarver c;
+  if (rows == 0 || S_ == 0) {
+    l.slack = c.take(256);                                       // never a zero-byte buffer
+  } else {
+    l.sp = psd_split(p, rows, S_);
+    l.means = c.take(rows * S_ * 8, 256);
+    l.part = c.take(l.sp.Z > 1 ? (int64_t)l.sp.Z * rows * p->K * el : 0, 256);
+    l.slack = c.take(l.sp.Z > 1 ? 0 : 256, 256);                 // whole lines; a line of slack where there is no `part`
+  }
+  l.end = c.end;
+  return l;
+}
+
 template <typename S>
 int psd_launch(const isd_psd_plan* p, const S* x, S* out, int64_t rows, int64_t T, int per_segment, void* work,
                void* stream, const char* who) {
@@ -211,7 +231,8 @@ int psd_launch(const isd_psd_plan* p, const S* x, S* out, int64_t rows, int64_t 
   const int64_t S_ = psd_segments(p, T);
   ISD_CHECK_SUPPORTED(S_ <= 2147483647LL, "%s: %lld segments (at most 2^31 - 1)", who, (long long)S_);
   ISD_CHECK_ARG(x && out && work, "%s: null argument", who);
-  const PsdSplit sp = psd_split(p, rows, S_);
+  const PsdWs l = psd_layout(p, rows, S_, sizeof(S));
+  const PsdSplit& sp = l.sp;
   ISD_CHECK_SUPPORTED(sp.row_tiles <= 2147483647LL, "%s: rows=%lld", who, (long long)rows);
   hipStream_t st = (hipStream_t)stream;
   const bool f64 = sizeof(S) == 8;
@@ -220,7 +241,7 @@ int psd_launch(const isd_psd_plan* p, const S* x, S* out, int64_t rows, int64_t 
   const int np = f64 ? p->np64 : p->np32;
   double* means = nullptr;
   if (p->remove_dc) {
-    means = static_cast<double*>(work);
+    means = reinterpret_cast<double*>(static_cast<char*>(work) + l.means);
     const int64_t units = rows * S_;
     const unsigned g = (unsigned)std::min<int64_t>(cdiv(units, 4), 256 * 16);
     hipLaunchKernelGGL((psd_mean_kernel<S>), dim3(g), dim3(kPsdThreads), 0, st, x, means, units, S_, T, p->n_per_seg,
@@ -228,7 +249,7 @@ int psd_launch(const isd_psd_plan* p, const S* x, S* out, int64_t rows, int64_t 
     ISD_LAUNCH_CHECK();
   }
   const int partial = !per_segment && sp.Z > 1;
-  S* part = reinterpret_cast<S*>(static_cast<char*>(work) + psd_align(rows * S_ * (int64_t)sizeof(double)));
+  S* part = reinterpret_cast<S*>(static_cast<char*>(work) + l.part);
   const dim3 grid((unsigned)sp.row_tiles, (unsigned)sp.bin_tiles, (unsigned)sp.Z);
   hipLaunchKernelGGL((psd_welch_kernel<S>), grid, dim3(kPsdThreads), 0, st, x, tab, scale, (const double*)means,
                      partial ? part : out, rows, T, S_, sp.seg_per_z, p->n_per_seg, p->step, np, p->K, p->Kp,
@@ -334,11 +355,7 @@ extern "C" int64_t isd_psd_work_bytes(const isd_psd_plan* p, int64_t rows, int64
     set_error("isd_psd_work_bytes: null plan or rows=%lld", (long long)rows);
     return ISD_ERR_INVALID;
   }
-  const int64_t S_ = psd_segments(p, T);
-  if (rows == 0 || S_ == 0) return 256;                          // never a zero-byte buffer
-  const PsdSplit sp = psd_split(p, rows, S_);
-  const int64_t el = is_f64 ? 8 : 4;
-  return psd_align(rows * S_ * 8) + (sp.Z > 1 ? psd_align((int64_t)sp.Z * rows * p->K * el) : 256);
+  return psd_layout(p, rows, psd_segments(p, T), is_f64 ? 8 : 4).end;
 }
 
 extern "C" int isd_psd_welch_f32(const isd_psd_plan* plan, const float* x, float* out, int64_t rows, int64_t T,

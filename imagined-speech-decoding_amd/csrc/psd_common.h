@@ -115,6 +115,4 @@ static inline int64_t psd_segments(const isd_psd_plan* p, int64_t T) {
   return T < p->n_per_seg ? 0 : (T - p->n_per_seg) / p->step + 1;
 }
 
-static inline int64_t psd_align(int64_t b) { return (b + 255) / 256 * 256; }
-
 }  // namespace isd

@@ -703,12 +703,10 @@ struct TsWs {
 constexpr int kAccFwd = 3 * 32, kAccAll = 6 * 32;                   // ExactAcc: per BatchNorm 16 + 16, forward then backward
 constexpr int kCoefStride = 80;                                    // floats per coefficient block (65 used)
 
-inline int64_t al64(int64_t v) { return (v + 63) / 64 * 64; }
-
 TsWs ts_layout(const TsGeo& g, int64_t B) {
   TsWs w;
-  int64_t o = 0;
-  auto take = [&](int64_t n) { int64_t at = o; o += al64(n); return at; };
+  WorkCarver c;
+  auto take = [&](int64_t n) { return c.take(n, 64); };           // every region on a 256-byte line
   w.acc = take((int64_t)kAccAll * (sizeof(ExactAcc) / 4));
   w.coef = take(6 * kCoefStride);                                  // BN_t, BN_s, BN_f forward; then backward
   w.P = take(B * g.F * g.C * g.L);
@@ -746,7 +744,8 @@ TsWs ts_layout(const TsGeo& g, int64_t B) {
   w.part3 = take(w.nchunkO * n3);
   red += nS + nF + n0 + n3;                                        // at most kRedGroup chunks: one row each
   w.red = take(red);
-  w.total = o;
+  take(0);                                                         // the size counts whole lines
+  w.total = c.end;
   return w;
 }
 

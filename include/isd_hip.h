@@ -13,7 +13,11 @@
  *     threads inside a *_forward / *_backward call (graph-capturable);
  *   - return 0 on success, a negative ISD_ERR_* otherwise; the message of the
  *     last failure on the calling thread is isd_last_error();
- *   - plans are opaque, immutable after create, shareable across streams.
+ *   - plans are opaque, immutable after create, shareable across streams;
+ *   - a launch receives its workspace as a bare pointer.  The matching size query
+ *     (*_work_bytes, *_workspace_bytes) answers exactly what the launch addresses
+ *     plus the slack its comment names: both read one layout (csrc/common.h,
+ *     WorkCarver).  A negative answer is an ISD_ERR_* code.
  */
 #ifndef ISD_HIP_H
 #define ISD_HIP_H
@@ -325,6 +329,8 @@ int isd_psd_plan_create(isd_psd_plan** out, int n_fft, int n_per_seg, int n_over
 int isd_psd_plan_destroy(isd_psd_plan* plan);
 int isd_psd_plan_bins(const isd_psd_plan* plan);                    /* K */
 int64_t isd_psd_plan_segments(const isd_psd_plan* plan, int64_t T); /* S, 0 if T < n_per_seg */
+/* exactly what the launch addresses: the fp64 segment means, then each z's partial spectra in whole 256-byte lines when
+ * the segments are split over z, one line of slack when they are not (256 for rows == 0 or T < n_per_seg) */
 int64_t isd_psd_work_bytes(const isd_psd_plan* plan, int64_t rows, int64_t T, int is_f64);
 int isd_psd_welch_f32(const isd_psd_plan* plan, const float* x, float* out, int64_t rows, int64_t T, int per_segment,
                       void* work, void* stream);
@@ -348,6 +354,8 @@ int isd_psd_welch_f64(const isd_psd_plan* plan, const double* x, double* out, in
  * ISD_ERR_UNSUPPORTED.
  * ---------------------------------------------------------------------- */
 int64_t isd_csd_chunk_bytes(int64_t bytes);
+/* exactly what the launch addresses (means, one chunk's spectra, with over_trials the range sums and the accumulator,
+ * each from a 256-byte line) plus one line of slack: never 0 */
 int64_t isd_csd_work_bytes(const isd_psd_plan* plan, int64_t n, int64_t C, int64_t T, int over_trials, int is_f64);
 int isd_csd_welch_f32(const isd_psd_plan* plan, const float* x, float* out, int64_t n, int64_t C, int64_t T,
                       int over_trials, int unit_modulus, void* work, void* stream);
@@ -369,7 +377,9 @@ int isd_csd_welch_f64(const isd_psd_plan* plan, const double* x, double* out, in
  * complex / one real element.  No call synchronises with the host.  n == 0 returns 0 with nothing touched;
  * C outside 1..128 is ISD_ERR_UNSUPPORTED; a null pointer, T < 1 with n > 0 or an unknown flag is ISD_ERR_INVALID.
  * ---------------------------------------------------------------------- */
-int64_t isd_envcorr_work_bytes(int64_t n, int64_t C, int64_t T, int is_f64);      /* never 0; negative = error code */
+/* exactly what the launch addresses (row statistics, then W from a 256-byte line) plus 256 bytes of slack: never 0;
+ * negative = error code */
+int64_t isd_envcorr_work_bytes(int64_t n, int64_t C, int64_t T, int is_f64);
 int isd_envcorr_f32(const float* z /* [n][C][T][2] */, float* out /* [n][C][C] */, int64_t n, int64_t C, int64_t T,
                     int flags /* 1 log | 2 absolute | 4 plain */, void* work, void* stream);
 int isd_envcorr_f64(const double* z, double* out, int64_t n, int64_t C, int64_t T, int flags, void* work,
@@ -390,7 +400,9 @@ int isd_envcorr_f64(const double* z, double* out, int64_t n, int64_t C, int64_t 
  * 0 with nothing touched.  Envelope: 1 <= T <= 4096, 2 <= n_bins <= 64, 0 <= S <= 4095, P, A >= 1,
  * rows * A * P < 2^31; outside it ISD_ERR_UNSUPPORTED.
  * ---------------------------------------------------------------------- */
-int64_t isd_pac_work_bytes(int64_t rows, int64_t P, int64_t A, int64_t T, int is_f64);   /* negative = error code */
+/* exactly what the launch addresses (ranked records, sample indices, bin offsets, the surrogates' order, each from a
+ * 256-byte line; the last is there for rows == 0 too: never 0); negative = error code */
+int64_t isd_pac_work_bytes(int64_t rows, int64_t P, int64_t A, int64_t T, int is_f64);
 int isd_pac_f32(const float* pha, const float* amp, const int32_t* shifts, float* out, float* surr, int64_t rows,
                 int64_t P, int64_t A, int64_t T, int64_t S, int n_bins, double c, void* work, void* stream);
 int isd_pac_f64(const double* pha, const double* amp, const int32_t* shifts, double* out, double* surr, int64_t rows,
@@ -502,6 +514,7 @@ int64_t isd_conv4_param_count(const isd_conv4_plan* plan);
 /* which: 0 cnn1.weight, 1 cnn1.bias, 2 cnn2.weight, 3 cnn3.weight, 4 cnn4.weight -> offset in floats */
 int64_t isd_conv4_param_offset(const isd_conv4_plan* plan, int zone, int which);
 int isd_conv4_windows(const isd_conv4_plan* plan, int64_t T);
+/* exactly what the calls on this plan address at (B, T), in whole 256-byte lines; every route's slabs fit the last region */
 int64_t isd_conv4_workspace_bytes(const isd_conv4_plan* plan, int64_t B, int64_t T);
 
 /* forward keeps the activations the backward needs inside `workspace` (caller-owned,
@@ -531,6 +544,8 @@ int isd_linear_forward(const float* x, const float* w, const float* bias, float*
 /* y = x . w^T + bias + res   (residual connection fused in the epilogue; fast.py:24-25) */
 int isd_linear_residual_forward(const float* x, const float* w, const float* bias, const float* res, float* y,
                                 int64_t M, int K, int N, void* stream);
+/* isd_linear_backward's workspace: 4 (M N + slabs N (K + 1) + 64) bytes -- exactly the activation gradient, the weight
+ * gradient slabs from the next 256-byte line, and what is left of the 64 floats as slack */
 int64_t isd_linear_workspace_bytes(int64_t M, int K, int N);
 /* dx nullable; db nullable */
 int isd_linear_backward(const float* x, const float* w, const float* dy, const float* pre, float* dx,
@@ -548,6 +563,7 @@ int isd_linear_backward(const float* x, const float* w, const float* dy, const f
  * workspace: isd_softmax_ce_workspace_bytes(B) bytes of scratch (per-block partial sums + an
  * arrival ticket; contents need not be initialised); only needed when the loss is requested.
  * ---------------------------------------------------------------------- */
+/* exactly what the launch addresses: the ticket's 256-byte line, then one float per 256 trials */
 int64_t isd_softmax_ce_workspace_bytes(int64_t B);
 int isd_softmax_ce(const float* logits_tok, const void* labels, int label_bytes, float* logits_mean,
                    float* loss, float* dlogits_tok, int64_t* pred, int64_t B, int n_tok, int n_cls,
@@ -590,6 +606,8 @@ int isd_eegnet_plan_set_input_dtype(isd_eegnet_plan* plan, int dtype);
 int isd_eegnet_plan_destroy(isd_eegnet_plan* plan);
 int64_t isd_eegnet_param_count(const isd_eegnet_plan* plan);
 int64_t isd_eegnet_buffer_count(const isd_eegnet_plan* plan);
+/* exactly what the passes address, every region from a 256-byte line; the linear layer's region is
+ * isd_linear_workspace_bytes and 64 floats of slack */
 int64_t isd_eegnet_workspace_bytes(const isd_eegnet_plan* plan, int64_t B);
 int isd_eegnet_forward(const isd_eegnet_plan* plan, const float* x, const float* params, float* buffers,
                        float* out, void* workspace, int64_t B, int training, float momentum, float eps,
@@ -752,7 +770,7 @@ int isd_paperhead_plan_create(isd_paperhead_plan** out, int in_channels, int fea
 int isd_paperhead_plan_destroy(isd_paperhead_plan* plan);
 int64_t isd_paperhead_param_count(const isd_paperhead_plan* plan);
 int64_t isd_paperhead_buffer_count(const isd_paperhead_plan* plan);
-int64_t isd_paperhead_workspace_bytes(const isd_paperhead_plan* plan, int64_t B);
+int64_t isd_paperhead_workspace_bytes(const isd_paperhead_plan* plan, int64_t B);   /* exactly what the passes address */
 int isd_paperhead_forward(const isd_paperhead_plan* plan, const float* x, const float* params, float* buffers,
                           float* out, void* workspace, int64_t B, int training, float momentum, float eps, void* stream);
 int isd_paperhead_backward(const isd_paperhead_plan* plan, const float* x, const float* params, const float* dout,
@@ -819,6 +837,7 @@ int isd_tsception_plan_create(isd_tsception_plan** out, int in_channels, int T, 
 int isd_tsception_plan_destroy(isd_tsception_plan* plan);
 int64_t isd_tsception_param_count(const isd_tsception_plan* plan);
 int64_t isd_tsception_buffer_count(const isd_tsception_plan* plan);
+/* exactly what the passes address, in whole 256-byte lines */
 int64_t isd_tsception_workspace_bytes(const isd_tsception_plan* plan, int64_t B);
 int isd_tsception_forward(const isd_tsception_plan* plan, const float* x, const float* params, float* buffers,
                           float* logits, void* workspace, int64_t B, int training, float momentum, float eps,
