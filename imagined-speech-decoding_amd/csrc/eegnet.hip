@@ -16,8 +16,17 @@
 //                                                       with exact edge corrections for the zero padding).
 // The parameter gradients of stage 1 are assembled from the same quantities (dWt needs G and the
 // cross-correlation of da2 with z; dWs is one GEMM of x with the back-filtered da2).  Statistics and
-// cross-batch reductions accumulate in fp64.  Dropout: inference / p = 0 only (train-mode dropout would
-// break parity with any reference RNG stream).
+// cross-batch reductions accumulate in fp64.
+//
+// Dropout (train mode, p > 0; eval mode and p = 0 multiply by 1): two sites, one after each average pool, with
+// counter-based masks (drop_scale below: keep-scale 1/(1-p) in fp32, or 0) -- the library's own stream, statistically
+// nn.Dropout and not the bits of any torch generator.  Per pass s1 = seed + 0xD1342543DE82EF95 * step counter
+// (the device word of isd_eegnet_plan_set_seed_counter; 0 without one):
+//     site 1: stream s1,               element [b,g,v] of [B,16,T2] at index (b*16+g)*T2 + v
+//     site 2: stream s1 ^ 0x5bd1e995,  element [b,h,v] of [B,16,T3] at index (b*16+h)*T3 + v
+// (T2, T3: the pooled widths of the plan; CVBlock's site 2 is the flattened projector input).  The forward kernels
+// (eeg_pool2, eeg_pool3, cv_pool3) and the backward kernels (eeg_bwd3_sums, eeg_bwd_sep, eeg_bwd_pool2, cv_dy3)
+// re-evaluate the mask from these indices; tests/bnhead_dropout_ref.py restates them on the host.
 #include "common.h"
 #include "zonebatch.h"
 #include "exact.h"
