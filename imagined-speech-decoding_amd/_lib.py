@@ -57,6 +57,7 @@ SIGNATURES = {
     "isd_features_fused": (_i, [_p, _p, _p, _p, _i64, _i64, _pi, _pi, _i, _f, _p]),
     "isd_features_fused_bf16": (_i, [_p, _p, _p, _p, _i64, _i64, _pi, _pi, _i, _f, _p]),
     "isd_features_fused_last_path": (_i, []),
+    "isd_features_fused_last_serial_waves": (_i, []),
     "isd_features_backward_workspace_bytes": (_i64, [_p, _p, _i64, _i64, _pi, _pi]),
     "isd_features_backward": (_i, [_p, _p, _p, _p, _p, _p, _i64, _i64, _pi, _pi, _i, _f, _p]),
     "isd_attr_mix": (_i, [_p, _p, _p, _p, _p, _i64, _i64, _i, _i64, _i, _p]),

@@ -22,6 +22,7 @@
 #include <string.h>
 #include <type_traits>
 #include <atomic>
+#include <algorithm>
 
 namespace isd {
 
@@ -1520,8 +1521,18 @@ constexpr int kSerBins = 4;                  // a band's bins plus its two neigh
 constexpr int kSerMaxGroups = 4;             // row groups (of 64 rows) per workgroup
 
 constexpr int kSerMaxWaves = 12;
+// The flat layout, instance BPW = 0.  Every wave owns ONE (row group, band) slot, numbered flat across workgroups: slot
+// s = W blockIdx.x + wave (W waves per workgroup, 16 or 8), row group s / nb, band s % nb, so that a workgroup is W waves
+// whatever the band count -- two workgroups per CU at W = 8 (the default), one at W = 16: four waves on every SIMD, which
+// no grouped shape reaches at nine bands (its 9-, 10- and 12-wave workgroups fit once per CU).  Its slots touch row groups
+// floor(W blockIdx.x / nb) .. floor((W blockIdx.x + W - 1) / nb), at most ceil((W - 1) / nb) + 1 of them; it holds one
+// double-buffered tile for each, and a row group that straddles two workgroups is fetched by both.  The tiles' 1 KiB
+// pieces are dealt round-robin over all W waves, whichever row group a wave computes.  Waves whose slot lies past the
+// last row group fetch and keep the barriers, nothing else.  The chunk body is the grouped instances', one band per wave.
+constexpr int kSerFlatMaxWaves = 16;
 template <int BPW, bool MAG>
-__global__ __launch_bounds__(64 * kSerMaxWaves) __attribute__((amdgpu_waves_per_eu(BPW == 1 ? 5 : BPW == 2 ? 4 : 3)))
+__global__ __launch_bounds__(64 * (BPW ? kSerMaxWaves : kSerFlatMaxWaves))
+__attribute__((amdgpu_waves_per_eu(BPW == 1 ? 5 : BPW == 3 ? 3 : 4)))
 void fused_serial_kernel(const SerSec* __restrict__ secs, const FbBand* __restrict__ bands,
                          const float2* __restrict__ sym, const float* __restrict__ x, float* __restrict__ feat,
                          int R, int C, int T, int nb, int J, float scale2, FusedBands fbnd, int mode, float eps,
@@ -1534,9 +1545,23 @@ void fused_serial_kernel(const SerSec* __restrict__ secs, const FbBand* __restri
   extern __shared__ __attribute__((aligned(16))) float ring_raw[];   // [G][2][64 * 32]: two tiles per row group
   const int lane = threadIdx.x & 63;
   const int wave_all = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int grp = wave_all / NW, wave = wave_all - grp * NW;        // row group of this wave, its index in the group
+  constexpr bool FLAT = BPW == 0;
+  constexpr int NBW = FLAT ? 1 : BPW;                                // bands a wave carries
+  int grp, wave, row0, flat_pieces = 0;
+  if constexpr (FLAT) {
+    const int W = (int)(blockDim.x >> 6), slot0 = W * (int)blockIdx.x, n_groups = (R + kSerRows - 1) / kSerRows;
+    const int g0 = slot0 / nb, g1 = min((slot0 + W - 1) / nb, n_groups - 1);   // the workgroup's row groups (with rows)
+    const int g = (slot0 + wave_all) / nb;
+    wave = slot0 + wave_all - g * nb;                                // this wave's band, or nb: a slot past the end
+    if (g >= n_groups) wave = nb;
+    grp = min(g, g1) - g0;                                           // its tile
+    row0 = g * kSerRows;
+    flat_pieces = 8 * (g1 - g0 + 1);
+  } else {
+    grp = wave_all / NW, wave = wave_all - grp * NW;                 // row group of this wave, its index in the group
+    row0 = (blockIdx.x * (int)(blockDim.x >> 6) / NW + grp) * kSerRows;   // first row of the group
+  }
   float* const ring = ring_raw + grp * (2 * kSerRows * kL);
-  const int row0 = (blockIdx.x * (int)(blockDim.x >> 6) / NW + grp) * kSerRows;   // first row of the group
   const int row = row0 + lane;
   const bool row_ok = row < R;
   const int rowc = row_ok ? row : R - 1;                             // a missing row recomputes the last one
@@ -1555,6 +1580,18 @@ void fused_serial_kernel(const SerSec* __restrict__ secs, const FbBand* __restri
   const unsigned ring_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) float*)ring;
   auto fetch_tile = [&](int c) {                                     // chunk c of the group's 64 rows -> ring[c & 1]
     if (c >= n_chunks) return;
+    if constexpr (FLAT) {                                            // piece p: rows 8 (p & 7) .. + 7 of tile p >> 3
+      const int W = (int)(blockDim.x >> 6), first = W * (int)blockIdx.x / nb * kSerRows;
+      for (int p = wave_all; p < flat_pieces; p += W) {
+        const int r = 8 * (p & 7) + (lane >> 3);
+        int gr = first + (p >> 3) * kSerRows + r;
+        gr = gr < R ? gr : R - 1;
+        const float* src = x + (int64_t)gr * T + c * kL + 4 * ((lane & 7) ^ ((r >> 1) & 7));
+        const unsigned all_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) float*)ring_raw;
+        ser_dma16(src, all_base + (unsigned)(((2 * (p >> 3) + (c & 1)) * kSerRows * kL) * 4 + (p & 7) * 1024));
+      }
+      return;
+    }
     for (int i = wave; i < 8; i += NW) {
       const int r = 8 * i + (lane >> 3);
       int gr = row0 + r;
@@ -1565,11 +1602,11 @@ void fused_serial_kernel(const SerSec* __restrict__ secs, const FbBand* __restri
   };
   const int rbase = lane * kL, rswz = (lane >> 1) & 7;
 
-  double S[BPW][NS][2];
-  f2 prevU[BPW][kSerBins];
-  float ob[BPW][4];                                                  // the band's last frames, waiting for their store
+  double S[NBW][NS][2];
+  f2 prevU[NBW][kSerBins];
+  float ob[NBW][4];                                                  // the band's last frames, waiting for their store
 #pragma unroll
-  for (int i = 0; i < BPW; ++i) {
+  for (int i = 0; i < NBW; ++i) {
     ob[i][0] = ob[i][1] = ob[i][2] = ob[i][3] = 0.f;
 #pragma unroll
     for (int s = 0; s < NS; ++s) S[i][s][0] = S[i][s][1] = 0.0;
@@ -1598,8 +1635,8 @@ void fused_serial_kernel(const SerSec* __restrict__ secs, const FbBand* __restri
     fetch_tile(c + 1);
     pend = 0;
 #pragma unroll
-    for (int i = 0; i < BPW; ++i) {
-      const int b = wave + i * NW;
+    for (int i = 0; i < NBW; ++i) {
+      const int b = FLAT ? wave : wave + i * NW;
       if (b < nb) {
         const int klo = fbnd.klo[b], khi = fbnd.khi[b];
         const int k0 = klo - 1, nbin = khi - klo + 1;
@@ -1730,6 +1767,15 @@ static bool env_rows4_lds_carry() { static const bool v = getenv("ISD_ROWS4_LDS_
 static bool env_fused_serial() { const char* e = getenv("ISD_FUSED_SERIAL"); return !(e && e[0] == '0'); }
 static int env_serial_bpw() { const char* e = getenv("ISD_SERIAL_BPW"); return e ? atoi(e) : 0; }
 static int env_serial_groups() { const char* e = getenv("ISD_SERIAL_GROUPS"); return e ? atoi(e) : 0; }
+// ISD_SERIAL_FLAT: waves per workgroup of the serial family's flat layout, 8 or 16; 0 keeps the grouped layout; unset
+// (or anything else) is the default.  8 -- two workgroups per CU, a smaller barrier, two tiles at nine bands -- is the
+// one that cleared the bar at the headline shape (profiles/r24_serial_flat_ab.txt); 16 did not.
+constexpr int kSerFlatDefault = 8;
+static int env_serial_flat() {
+  const char* e = getenv("ISD_SERIAL_FLAT");
+  const int v = e ? atoi(e) : kSerFlatDefault;
+  return v == 0 || v == 8 || v == 16 ? v : kSerFlatDefault;
+}
 // Per plan -- ISD_FB_AUTO_LIMIT replaces the AUTO threshold on the round-off amplification estimate: a positive number,
 // or the call fails (atof("") = 0 would silently send every band to the fp64 kernels)
 static int env_fb_auto_limit(double* limit) {
@@ -1933,9 +1979,10 @@ struct Route {
   // Template selectors.  f64: VT double (the plan's fp64 set) or float | gpr: GPR, 16-lane groups per row | full: FULL,
   // whole waves of whole segments | mag: MAG | vec: VEC and the kernels' `vec` argument, float4 row accesses | kb: KB,
   // bin slots (blocksum_plan) | carry_n: NS of fused_rows4_kernel, 4 = carried states in registers, 0 = in LDS | bpw:
-  // BPW, bands per wave of the serial kernel | fullq: FULLQ, every quad of rows is whole
+  // BPW, bands per wave of the serial kernel | fullq: FULLQ, every quad of rows is whole | flat: the serial family's flat
+  // layout with that many waves per workgroup (fused_serial_kernel<0, MAG>), 0 = the grouped layout
   bool f64, full, mag, fullq;
-  int gpr, vec, kb, carry_n, bpw;
+  int gpr, vec, kb, carry_n, bpw, flat;
   int share_n, nw, groups, log2_nblk;   // scalar launch arguments derived from the shape
 };
 
@@ -2025,8 +2072,13 @@ static FusedBands set_bands(const isd_fb_plan* fb, int k, const FusedBands& all)
 // fused_serial_kernel, 3 long rows); assigned once per call, in features_fused_impl
 static thread_local int g_fused_path = 0;
 extern "C" int isd_features_fused_last_path(void) { return g_fused_path; }
+// What isd_features_fused_last_serial_waves() reports: the waves per workgroup of the flat layout if the fp32 set's
+// launch took the flat layout, else 0; assigned beside g_fused_path
+static thread_local int g_serial_waves = 0;
+extern "C" int isd_features_fused_last_serial_waves(void) { return g_serial_waves; }
 
-static constexpr decltype(&fused_serial_kernel<1, false>) kSerialKernels[3][2] = {   // [bpw - 1][mag]
+static constexpr decltype(&fused_serial_kernel<1, false>) kSerialKernels[4][2] = {   // [bpw, 0 = flat][mag]
+    {fused_serial_kernel<0, false>, fused_serial_kernel<0, true>},
     {fused_serial_kernel<1, false>, fused_serial_kernel<1, true>},
     {fused_serial_kernel<2, false>, fused_serial_kernel<2, true>},
     {fused_serial_kernel<3, false>, fused_serial_kernel<3, true>}};
@@ -2107,6 +2159,19 @@ static int choose_fused_route(const isd_fb_plan* fb, int k, const isd_stft_plan*
     r.grid = dim3((unsigned)cdiv(R, (int64_t)kSerRows * r.groups));
     r.block = dim3(64 * r.nw * r.groups);
     r.lds = fused_serial_lds(r.groups);
+    // The flat layout (one band per wave, W waves per workgroup whatever the band count) unless a grouped geometry was
+    // asked for: a workgroup's slots touch at most ceil((W - 1) / nb) + 1 row groups, one double-buffered tile each
+    const int W = env_serial_flat();
+    const int64_t n_groups = cdiv(R, kSerRows);
+    const int64_t tiles = cdiv(W - 1, fs.nb) + 1;
+    if (W && !want && !g && tiles <= kSerMaxGroups) {
+      r.flat = W;
+      r.bpw = 1;
+      r.groups = (int)std::min(tiles, n_groups);
+      r.grid = dim3((unsigned)cdiv(n_groups * fs.nb, W));
+      r.block = dim3(64 * W);
+      r.lds = fused_serial_lds(r.groups);
+    }
   } else {
     r.family = kDirect16;
     r.gpr = st->T > kSeg ? 2 : 1;                                         // rows of 513..1024 samples: two 16-lane groups
@@ -2125,8 +2190,8 @@ static int fused_launch(const isd_fb_plan* fb, int k, const isd_stft_plan* st, c
   switch (r.family) {
     case kSerial: {
       if (r.lds > 48 * 1024) serial_lds_limit();      // not launch_lds: it would raise the limit before every launch
-      hipLaunchKernelGGL(kSerialKernels[r.bpw - 1][r.mag], r.grid, r.block, r.lds, s, fs.d_ser, fs.d_band, st->d_sym, x, feat,
-                         (int)R, C, st->T, fs.nb, st->J, scale2, fbnd, mode, eps, fs.d_map, fb->n_bands, out16, r.nw);
+      hipLaunchKernelGGL(kSerialKernels[r.flat ? 0 : r.bpw][r.mag], r.grid, r.block, r.lds, s, fs.d_ser, fs.d_band, st->d_sym,
+                         x, feat, (int)R, C, st->T, fs.nb, st->J, scale2, fbnd, mode, eps, fs.d_map, fb->n_bands, out16, r.nw);
       ISD_LAUNCH_CHECK();
       return ISD_OK;
     }
@@ -2193,6 +2258,7 @@ static int features_fused_impl(const isd_fb_plan* fb, const isd_stft_plan* st, c
   for (int k = 0; k < 2 && rc == ISD_OK; ++k)
     if (fb->set[k].nb) rc = choose_fused_route(fb, k, st, x, R, (int)C, all, mode, route[k]);
   g_fused_path = !fused_short_rows(st) ? 3 : route[0].family == kSerial ? 2 : 1;
+  g_serial_waves = g_fused_path == 2 ? route[0].flat : 0;
   for (int k = 0; k < 2 && rc == ISD_OK; ++k)
     if (fb->set[k].nb)
       rc = fused_launch(fb, k, st, route[k], x, feat, R, (int)C, set_bands(fb, k, all), mode, eps, (hipStream_t)stream,

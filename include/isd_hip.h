@@ -138,6 +138,11 @@ int isd_features_fused_bf16(const isd_fb_plan* fb, const isd_stft_plan* st, cons
  *   block-sum kernels.
  * A plan without fp32 bands reports the family of its fp64 bands: 1 on short rows (fused_kernel), 3 on long rows. */
 int isd_features_fused_last_path(void);
+/* Within family 2: the waves per workgroup (16 or 8) if that call took the flat layout -- one band per wave, slots
+ * numbered across workgroups; the default, with 8 waves, for three bands and more; ISD_SERIAL_FLAT=0 / 8 / 16 in the
+ * environment overrides it -- and 0 after the grouped layout (ISD_SERIAL_BPW / ISD_SERIAL_GROUPS set, fewer bands) or any other
+ * family. */
+int isd_features_fused_last_serial_waves(void);
 
 /* Input gradient of the extractor (spec S backward): dx = d<dfeat, feat(x)>/dx for the feature map that
  * isd_features_fused / isd_fb_forward + isd_stft_bandpower compute from x with the same plans, bins, mode and eps --
