@@ -95,6 +95,8 @@ SIGNATURES = {
     "isd_envcorr_work_bytes": (_i64, [_i64, _i64, _i64, _i]),
     "isd_envcorr_f32": (_i, [_p, _p, _i64, _i64, _i64, _i, _p, _p]),
     "isd_envcorr_f64": (_i, [_p, _p, _i64, _i64, _i64, _i, _p, _p]),
+    "isd_contime_f32": (_i, [_p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i, _i, _p]),
+    "isd_contime_f64": (_i, [_p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i, _i, _p]),
     "isd_pac_work_bytes": (_i64, [_i64, _i64, _i64, _i64, _i]),
     "isd_pac_f32": (_i, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i, C.c_double, _p, _p]),
     "isd_pac_f64": (_i, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i, C.c_double, _p, _p]),

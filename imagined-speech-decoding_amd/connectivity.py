@@ -20,9 +20,19 @@ the N (trial, segment) pairs averaged,
 
 The names and formulas follow the documentation of mne-connectivity (``spectral_connectivity_epochs``); that library is
 not installed here and **parity with it is unpinned**: the tests pin the formulas above against a NumPy restatement and
-scipy (``scipy.signal.csd`` / ``coherence``).  Measures that are not Hermitian products of segment spectra ('pli',
-'dpli', 'wpli', 'wpli2_debiased'), multitaper and wavelet modes and ``indices=`` are not provided and raise
-NotImplementedError by name.
+scipy (``scipy.signal.csd`` / ``coherence``).  Multitaper and wavelet modes and ``indices=`` are not provided here
+and raise NotImplementedError by name, and so do the phase-lag measures ('pli', 'dpli', 'wpli', 'wpli2_debiased'):
+they are sums over samples of sign(Im s), |Im s| and (Im s)^2 per channel pair, not Hermitian products of segment
+spectra, so the Welch route cannot form them.  They live in ``spectral_connectivity_time`` below.
+
+``spectral_connectivity_time(data, freqs, method=..., sfreq=...)`` -> ``(con, freqs)`` is the time-resolved estimate,
+one [F, C, C] map PER TRIAL from the Morlet cross-spectrum averaged over the trial's samples (hundreds of them, where a
+trial has three to five Welch segments): 'coh', 'imcoh', 'plv', 'ciplv' and the phase-lag family 'pli', 'dpli', 'wpli',
+'wpli2_debiased'.  The complex map comes from ``tfr``'s plan in trial chunks of at most CONTIME_CHUNK_BYTES and one
+fused kernel (csrc/contime.hip) turns each chunk into the measures: one pass over the map per pair of channel tiles,
+a compensated cross product for Im s (the sign of a nearly in-phase pair is what pli and dpli are made of), fp64
+sums.  In torch ops it is a [chunk, F, C, C, T] complex intermediate and five or six passes over it.  The names follow
+``mne_connectivity.spectral_connectivity_time``; **parity with it is unpinned** as well.
 
 The segment bookkeeping, the window and the argument checks are ``psd.welch_design``; the data-sized work runs in
 libisd_hip.so (csrc/csd.hip: segment spectra as a dense product on the plan's tables, then a Hermitian product per
@@ -51,6 +61,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import tfr as _tfr
 from .analytic import hilbert_device
 from .constants import BANDS_5, band_edges
 from .psd import MAX_N_FFT, _cached_design, _cached_plan
@@ -313,3 +324,170 @@ def envelope_correlation(data, orthogonalize="pairwise", log=False, absolute=Tru
     if squeeze:
         out = out[0]
     return out if is_tensor else out.cpu().numpy()
+
+
+# --------------------------------------------------------------------------------- time-resolved spectral connectivity
+CONTIME_CHUNK_BYTES = 256 << 20      # spectral_connectivity_time: bound on the complex map [chunk, C, F, T_out] alive
+CONTIME_METHODS = ("coh", "imcoh", "plv", "ciplv", "pli", "dpli", "wpli", "wpli2_debiased")   # bit m of methods_mask
+CONTIME_MULTIVARIATE = ("cacoh", "mic", "mim", "gc", "gc_tr")
+
+
+def contime_mask(names):
+    """The methods_mask of a list of CONTIME_METHODS names; the library stores the measures in bit order."""
+    mask = 0
+    for m in names:
+        mask |= 1 << CONTIME_METHODS.index(m)
+    return mask
+
+
+def contime_launch(z, methods_mask, t0, t1, out=None, average=False):
+    """One library call: z contiguous complex CUDA [n, C, F, T_out] -> real [M, n, F, C, C] ([M, F, C, C] with
+    ``average``): the M measures of ``methods_mask`` (bit m = CONTIME_METHODS[m]) in bit order over the samples
+    t0 <= t < t1; ``out`` (a contiguous real tensor of that shape) receives the result if given."""
+    if not (isinstance(z, torch.Tensor) and z.is_cuda and z.dtype in _REAL_OF and z.ndim == 4 and z.is_contiguous()):
+        raise ValueError("z must be a contiguous complex64 / complex128 CUDA tensor [n, C, F, T_out]")
+    n, Cc, F, T = z.shape
+    rdtype = _REAL_OF[z.dtype]
+    M = bin(int(methods_mask) & 0xFF).count("1")
+    shape = (M, F, Cc, Cc) if average else (M, n, F, Cc, Cc)
+    if out is None:
+        out = torch.empty(shape, dtype=rdtype, device=z.device)
+    elif tuple(out.shape) != shape or out.dtype != rdtype or not out.is_contiguous() or out.device != z.device:
+        raise ValueError(f"out must be a contiguous {rdtype} tensor of shape {shape} on {z.device}")
+    if n == 0 and not average:
+        return out
+    with torch.cuda.device(z.device):
+        fn = _lib.typed("isd_contime", rdtype)
+        _lib.check(fn(torch.view_as_real(z).data_ptr(), out.data_ptr(), n, Cc, F, T, int(t0), int(t1),
+                      int(methods_mask), int(bool(average)), _lib.stream()))
+    return out
+
+
+def check_time_methods(method):
+    """-> (list of names, whether a single name was given) for spectral_connectivity_time."""
+    single = isinstance(method, str)
+    names = [method] if single else list(method)
+    if not names:
+        raise ValueError("method is empty")
+    for m in names:
+        if m in CONTIME_MULTIVARIATE:
+            raise NotImplementedError(f"method={m!r}: the multivariate and Granger measures are not provided; "
+                                      f"provided: {', '.join(CONTIME_METHODS)}")
+        if m not in CONTIME_METHODS:
+            raise ValueError(f"method={m!r} (provided: {', '.join(CONTIME_METHODS)})")
+    return names, single
+
+
+def spectral_connectivity_time(data, freqs, method="coh", average=False, sfreq=None, faverage=False, bands=None,
+                               padding=0.0, mode="cwt_morlet", n_cycles=7.0, decim=1, zero_mean=True, sm_times=0,
+                               sm_freqs=1, indices=None):
+    """Time-resolved connectivity of data [n, C, T] ([C, T] is n = 1) between every pair of channels, one map per
+    trial -> (con, freqs): con real [n, F, C, C], or [F, C, C] with ``average=True`` (the mean over the trials of the
+    per-trial measure, summed in fp64 in trial order on the device).
+
+    With w_i(t) the complex Morlet coefficient of channel i at one frequency (``tfr_array_morlet(output='complex')``
+    with these ``freqs``, ``n_cycles``, ``zero_mean`` and ``decim``), s = w_i conj(w_j), u = s / |s| (0 where
+    |s| = 0) and <.> the mean over the kept samples of the trial:
+
+        'coh'   |<s>| / sqrt(<|w_i|^2> <|w_j|^2>)          'pli'   |<sign Im s>|
+        'imcoh' Im <s> / sqrt(<|w_i|^2> <|w_j|^2>)         'dpli'  <H(Im s)>, H(0) = 1/2
+        'plv'   |<u>|                                      'wpli'  |<Im s>| / <|Im s|>
+        'ciplv' |Im <u>| / sqrt((1 - |Re <u>|)(1 + |Re <u>|))
+        'wpli2_debiased'  ((sum Im s)^2 - sum (Im s)^2) / ((sum |Im s|)^2 - sum (Im s)^2)
+
+    ``method`` is one name or a list (a list returns a list; all entries share one pass over the map).  ``padding``
+    (seconds) drops round(padding * sfreq / decim) output samples from each end before averaging; at least one must
+    remain.  ``faverage=True`` averages each measure over the frequencies of each band of ``bands`` (default BANDS_5;
+    both ends inclusive): con [..., n_bands, C, C] and freqs the bands' mean frequencies; a band without a frequency
+    is an error.  Both triangles are filled: 'imcoh' and 'dpli' are antisymmetric (imcoh[j, i] = -imcoh[i, j],
+    dpli[j, i] = 1 - dpli[i, j], exactly so in the output's arithmetic for i > j), the other six symmetric bit for bit.
+    The diagonal is set, not computed: 1 for 'coh' and 'plv', 0 for 'imcoh' and 'pli', 1/2 for 'dpli' and NaN
+    (0 / 0) for 'ciplv', 'wpli' and 'wpli2_debiased'.  A dead (all-zero) channel gives, off the diagonal of its row and
+    column, NaN for 'coh', 'imcoh', 'wpli' and 'wpli2_debiased' (0 / 0), 0 for 'plv', 'ciplv' and 'pli' and 1/2 for
+    'dpli'; no other entry changes.  The results are bitwise repeatable and do not depend on CONTIME_CHUNK_BYTES, the
+    bound on the complex map alive at a time (trials are transformed and consumed in chunks).
+
+    ndarray in -> the fp64 route -> float64 ndarray out; float32 / float64 CUDA tensor in -> a tensor of that dtype
+    out, float32 with the transform and the products in fp32 and the sums in fp64 -- unless 'ciplv' is asked for: then
+    the whole call runs the fp64 route and is rounded at the end (its denominator amplifies the rounding of <u>, as
+    in ``spectral_connectivity``).  There is no CPU fallback.  Not provided (NotImplementedError): mode='multitaper',
+    smoothing (``sm_times``, ``sm_freqs``), ``indices=``, the multivariate and Granger methods, more than MAX_CHANNELS
+    channels.  Names and formulas follow mne-connectivity (``spectral_connectivity_time`` with no smoothing; 'dpli',
+    'imcoh' and 'wpli2_debiased' as ``spectral_connectivity_epochs`` documents them, with time as the averaged axis);
+    parity with that library is unpinned (it is not installed here)."""
+    names, single = check_time_methods(method)
+    if mode == "multitaper":
+        raise NotImplementedError("mode='multitaper' is not provided: only 'cwt_morlet'")
+    if mode != "cwt_morlet":
+        raise ValueError(f"mode={mode!r} (need 'cwt_morlet')")
+    if sm_times != 0 or sm_freqs != 1:
+        raise NotImplementedError(f"sm_times={sm_times!r}, sm_freqs={sm_freqs!r}: smoothing of the cross-spectrum is "
+                                  "not provided (need sm_times=0, sm_freqs=1)")
+    if indices is not None:
+        raise NotImplementedError("indices= is not provided: every pair of channels is computed")
+    if sfreq is None:
+        raise ValueError("sfreq is required")
+    data, is_tensor = _lib.check_array(data, "data")
+    if data.ndim not in (2, 3):
+        raise ValueError(f"data must be [n, C, T] or [C, T], got {tuple(data.shape)}")
+    if data.ndim == 2:
+        data = data[None]
+    n, Cc, T = (int(v) for v in data.shape)
+    if not 1 <= Cc <= MAX_CHANNELS:
+        raise NotImplementedError(f"{Cc} channels: 1 to {MAX_CHANNELS} are provided")
+    decim = _tfr._check_decim(decim)
+    sfreq, freqs, n_cycles = _tfr._freqs_cycles(sfreq, freqs, n_cycles)
+    n_taps, taps_bytes = _tfr._cached_morlet(sfreq, freqs.tobytes(), n_cycles.tobytes(), bool(zero_mean))
+    _tfr._check_taps(n_taps, T)
+    padding = float(padding)
+    if not padding >= 0:
+        raise ValueError(f"padding={padding!r} (need >= 0 seconds)")
+    T_out = _tfr.out_len(T, decim)
+    t0 = int(round(padding * sfreq / decim))
+    t1 = T_out - t0
+    if t1 <= t0:
+        raise ValueError(f"padding={padding:g} s drops {t0} of the {T_out} output samples from each end: none remains")
+    if average and n == 0:
+        raise ValueError("average=True over n=0 trials")
+    F = int(freqs.size)
+    out_freqs, bins = freqs.copy(), None
+    if faverage:
+        bands = BANDS_5 if bands is None else bands
+        bins = band_bins(freqs, bands)
+        for b, band in zip(bins, bands):
+            if b.size == 0:
+                raise ValueError(f"band {band!r} holds no frequency of freqs")
+        out_freqs = np.array([freqs[b].mean() for b in bins])
+
+    xd = _lib.to_device(data, is_tensor, "connectivity")
+    out_dtype = xd.dtype
+    if "ciplv" in names:
+        xd = xd.double()
+    f64 = xd.dtype == torch.float64
+    order = sorted(set(names), key=CONTIME_METHODS.index)
+    mask = contime_mask(order)
+    plan = _tfr._cached_plan(n_taps, taps_bytes, decim, xd.device.index)
+    per_trial = Cc * F * T_out * (16 if f64 else 8)
+    step = max(1, min(max(n, 1), int(CONTIME_CHUNK_BYTES) // per_trial))
+    zbuf = torch.empty((step, Cc, F, T_out), dtype=torch.complex128 if f64 else torch.complex64, device=xd.device)
+    parts = []
+    for s in range(0, n, step):
+        c = min(step, n - s)
+        z = plan(xd[s:s + c], "complex", out=zbuf[:c])
+        part = contime_launch(z, mask, t0, t1, average=bool(average))
+        parts.append(part.double() * c if average else part)
+    if average:                                                   # chunk sums, added in chunk order in fp64
+        res = parts[0]
+        for p in parts[1:]:
+            res = res + p
+        res = (res / n).to(xd.dtype)
+    elif parts:
+        res = parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
+    else:
+        res = torch.empty((len(order), 0, F, Cc, Cc), dtype=xd.dtype, device=xd.device)
+    vals = [res[order.index(m)].to(out_dtype) for m in names]
+    if faverage:
+        vals = [_band_mean(v, bins) for v in vals]
+    if not is_tensor:
+        vals = [v.cpu().numpy() for v in vals]
+    return (vals[0] if single else vals), out_freqs

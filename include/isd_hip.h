@@ -391,6 +391,35 @@ int isd_envcorr_f64(const double* z, double* out, int64_t n, int64_t C, int64_t 
                     void* stream);
 
 /* ------------------------------------------------------------------------
+ * Time-resolved spectral connectivity (csrc/contime.hip; isd_amd.connectivity.spectral_connectivity_time).
+ * z [n][C][F][T_out][2] is the complex wavelet map of n trials, (re, im) interleaved (isd_tfr_cwt_*, mode 0); the
+ * samples t0 <= t < t1 are averaged, N = t1 - t0.  Per (trial, frequency, channels i, j), s = w_i conj(w_j),
+ * u = s / |s| (0 where |s| = 0; formed as u_i conj(u_j) from each channel's w / |w|), <.> the mean over the samples:
+ *   bit 0 coh    |<s>| / sqrt(<|w_i|^2> <|w_j|^2>)          bit 4 pli    |<sign Im s>|
+ *   bit 1 imcoh  Im <s> / sqrt(<|w_i|^2> <|w_j|^2>)         bit 5 dpli   <H(Im s)>, H(0) = 1/2
+ *   bit 2 plv    |<u>|                                      bit 6 wpli   |<Im s>| / <|Im s|>
+ *   bit 3 ciplv  |Im <u>| / sqrt((1 - |Re <u>|)(1 + |Re <u>|))
+ *   bit 7 wpli2_debiased  ((sum Im s)^2 - sum (Im s)^2) / ((sum |Im s|)^2 - sum (Im s)^2)
+ * out real, the M measures of methods_mask in bit order: average == 0: [M][n][F][C][C]; average != 0: [M][F][C][C],
+ * the mean over the n trials of the per-trial measure, added in fp64 in trial order by the one wave that owns the
+ * (frequency, tile pair): no workspace, and F x (tile pairs) waves of parallelism only.  Im s is a compensated cross
+ * product (its sign is that of the exact Im s of the stored values unless |Im s| is below about 2^-47 |w_i| |w_j|
+ * in fp32, 2^-105 in fp64, where a plain difference of two products loses it at 2^-24 / 2^-53); every sum over t is fp64 or
+ * an integer count, in sample order, with no atomics: bitwise repeatable.  Both triangles are written: the same bits
+ * for the six symmetric measures, out[j][i] = -out[i][j] (imcoh) and 1 - out[i][j] (dpli) in the output's arithmetic
+ * for i > j.  The diagonal is set, not computed: 1 (coh, plv), 0 (imcoh, pli), 1/2 (dpli), NaN (ciplv, wpli,
+ * wpli2_debiased: 0 / 0).  A channel that is zero over [t0, t1) gives, off the diagonal of its row and column, NaN
+ * for coh, imcoh, wpli and wpli2_debiased, 0 for plv, ciplv and pli and 1/2 for dpli, and changes no other entry.
+ * z and out need the alignment of one complex / one real element.  No call synchronises with the host.  n == 0
+ * returns 0 with nothing touched (ISD_ERR_INVALID with average); C outside 1..128 is ISD_ERR_UNSUPPORTED; a null
+ * pointer, an empty or unknown methods_mask, F < 1 or not 0 <= t0 < t1 <= T_out is ISD_ERR_INVALID.
+ * ---------------------------------------------------------------------- */
+int isd_contime_f32(const float* z /* [n][C][F][T_out][2] */, float* out, int64_t n, int64_t C, int64_t F,
+                    int64_t T_out, int64_t t0, int64_t t1, int methods_mask, int average, void* stream);
+int isd_contime_f64(const double* z, double* out, int64_t n, int64_t C, int64_t F, int64_t T_out, int64_t t0,
+                    int64_t t1, int methods_mask, int average, void* stream);
+
+/* ------------------------------------------------------------------------
  * Phase-amplitude coupling with circular-shift surrogates (csrc/pac.hip; isd_amd.phase_amplitude_coupling).
  * pha [rows][P][T] phases in [-pi, pi], amp [rows][A][T] amplitudes >= 0, shifts int32 [1 + S] on the device with
  * shifts[0] = 0 (the estimate) and 0 <= shifts[i] < T (the surrogates: amp read at (t + shift) mod T).  The phase bin
