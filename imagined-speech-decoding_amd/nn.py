@@ -907,15 +907,28 @@ class _BNStackMixin(_FlatParamMixin):
             for plan in self._plans.values():
                 plan.set_seed_counter(counter)
 
+    def _bn_hyper(self):
+        """(momentum, eps) of the head: a pass takes one pair for all its BatchNorm layers, so layers that disagree are
+        refused, and so is ``momentum=None`` (torch's cumulative average, which the kernels do not implement)."""
+        bns = self._bns()
+        if any(bn.momentum is None for bn in bns):
+            raise ValueError(f"{type(self).__name__}: a BatchNorm layer has momentum=None (the cumulative moving "
+                             "average); the kernels implement the exponential average only: set a momentum")
+        pairs = {(float(bn.momentum), float(bn.eps)) for bn in bns}
+        if len(pairs) != 1:
+            raise ValueError(f"{type(self).__name__}: its BatchNorm layers disagree in (momentum, eps): "
+                             f"{sorted(pairs)}; a pass takes one pair for all of them")
+        return pairs.pop()
+
     def _head_call(self, T, dtype=torch.float32, training=None):
         """One forward's bookkeeping (call counter, ``num_batches_tracked``) and its ``_HeadCall`` record: what
         ``_BNHeadFn`` runs, what ``Head`` hands to the zone-batched ``_BNZonesFn`` (always float32 there), and what the
         autograd-free ``classifier.EEGNetPath`` drives -- which decides ``training`` itself."""
         kind = self._kind
-        plan = self._plan_for(T, dtype)                 # (refuses a dtype before any counter moves)
+        momentum, eps = self._bn_hyper()                # (refuses, like a dtype below, before any counter moves)
+        plan = self._plan_for(T, dtype)
         theta = self.packed_theta()
         training = self.training if training is None else bool(training)
-        bn = self._bns()[0]
         p, seed = 0.0, 0
         if kind.dropout:
             self._calls += 1
@@ -923,8 +936,7 @@ class _BNStackMixin(_FlatParamMixin):
         if training:
             for b in self._bns():
                 b.num_batches_tracked += 1
-        return _HeadCall(kind, theta, self.flat_buffers(), plan, training,
-                         0.1 if bn.momentum is None else float(bn.momentum), float(bn.eps), p, seed,
+        return _HeadCall(kind, theta, self.flat_buffers(), plan, training, momentum, eps, p, seed,
                          getattr(self, "sync_bn", True))
 
     def _run(self, x):

@@ -77,6 +77,28 @@ def test_input_gradient_matches_float64_autograd(isd, T, fs, nperseg, noverlap, 
         assert err <= tol, (i, err, fx.fb.precision)
 
 
+def test_input_gradient_beyond_one_wave(isd):
+    """135 rows: three workgroups of features_grad_kernel, the last with 7 live lanes, and a row stride of 192 (the
+    cases above have at most 48 rows, one partly filled wave).  Every row against float64, each on its own scale, and
+    one trial of the batch against the same trial run alone.  Measured on an MI355X (mixed plan, bound 2e-4): worst
+    row 1.9e-5, worst trial 1.7e-5."""
+    B, Cc, T, fs, bands, nperseg, noverlap = 5, 27, 250, 250.0, odsp.BANDS_5, 64, 32
+    X = _trials(B, Cc, T, fs, seed=B * Cc + T)
+    h = band_impulse_responses(fs, bands, T)
+    loud = _loud(X, fs, bands, nperseg, noverlap, h)
+    g = np.random.default_rng(T).standard_normal(loud.shape) * loud
+    fx, _, dx = _grad_gpu(isd, X, fs, bands, nperseg, noverlap, "logpower", "auto", g)
+    _, ref = _grad_ref(X, fs, bands, nperseg, noverlap, "logpower", g, h)
+    tol = 2e-5 if fx.fb.precision == "f64" else 2e-4
+    assert dx.shape == ref.shape == (B, Cc, T)
+    err = np.abs(dx - ref).max(-1) / np.abs(ref).max(-1)                      # [B, Cc]: row by row
+    print(f"beyond one wave ({fx.fb.precision}): worst row {err.max():.3e}, worst trial "
+          f"{max(np.abs(dx[i] - ref[i]).max() / np.abs(ref[i]).max() for i in range(B)):.3e}")
+    assert (err <= tol).all(), (np.argwhere(err > tol), err.max(), fx.fb.precision)
+    _, _, alone = _grad_gpu(isd, X[3:4], fs, bands, nperseg, noverlap, "logpower", "auto", g[3:4])
+    assert np.array_equal(alone[0], dx[3])
+
+
 # Near-silent frames (the last frames of a short trial: P orders below the row's median) amplify the fp32 noise of P
 # through 1 / (P + eps).  Unrestricted random cotangent; measured worst error over the case below: 9.2e-7 relative to
 # the trial's largest gradient (MI355X), bound 5e-6.
