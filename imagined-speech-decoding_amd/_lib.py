@@ -54,6 +54,7 @@ SIGNATURES = {
     "isd_stft_plan_bins": (_i, [_p]),
     "isd_stft_forward": (_i, [_p, _p, _p, _i64, _p]),
     "isd_stft_bandpower": (_i, [_p, _p, _p, _i64, _i64, _i, _i, _pi, _pi, _i, _f, _p]),
+    "isd_stft_bandpower_last_path": (_i, []),
     "isd_features_fused": (_i, [_p, _p, _p, _p, _i64, _i64, _pi, _pi, _i, _f, _p]),
     "isd_features_fused_bf16": (_i, [_p, _p, _p, _p, _i64, _i64, _pi, _pi, _i, _f, _p]),
     "isd_features_fused_last_path": (_i, []),

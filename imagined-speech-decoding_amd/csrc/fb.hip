@@ -2279,6 +2279,11 @@ extern "C" int isd_features_fused_bf16(const isd_fb_plan* fb, const isd_stft_pla
   return features_fused_impl(fb, st, x, reinterpret_cast<float*>(feat), B, C, klo, khi, mode, eps, stream, 1);
 }
 
+// whole waves of whole segments: the FULL instances' branch-free loads
+bool isd::bandpower_direct_full(const isd_stft_plan* st, const float* y, int64_t R) {
+  return vec_ok(st->T, y) && st->T == kSeg && R % 4 == 0;
+}
+
 int isd::bandpower_direct(const isd_stft_plan* st, const float* y, float* feat, int64_t R, int C, int nb,
                           const int* klo, const int* khi, int mode, float eps, hipStream_t stream) {
   FusedBands fbnd = {};
@@ -2286,7 +2291,7 @@ int isd::bandpower_direct(const isd_stft_plan* st, const float* y, float* feat, 
   const int64_t items = cdiv(R, 4);
   ISD_CHECK_ARG(R <= kMaxRows, "isd_stft_bandpower: too many rows (%lld)", (long long)R);
   const int vec = vec_ok(st->T, y);
-  const bool full = vec && st->T == kSeg && R % 4 == 0;        // whole waves of whole segments: branch-free loads
+  const bool full = bandpower_direct_full(st, y, R);
   static constexpr decltype(&bandpower_direct_kernel<false, false>) kern[2][2] = {   // [magnitude][full]
       {bandpower_direct_kernel<false, false>, bandpower_direct_kernel<false, true>},
       {bandpower_direct_kernel<true, false>, bandpower_direct_kernel<true, true>}};

@@ -332,6 +332,13 @@ int isd::fill_band_args(const isd_stft_plan* p, int n_bands, const int* klo, con
   return ISD_OK;
 }
 
+// What isd_stft_bandpower_last_path() reports: family + 16 * instance of the calling thread's last launch -- 1 / 17
+// bandpower_direct_kernel<*, FULL = false / true>, 2 + 16 KB (66, 82, 98, 130) bandpower_blocksum_kernel<hop, KB>,
+// 3 stft_kernel<1>; assigned once per call, in isd_stft_bandpower, where the kernel is chosen (a call that returns
+// before that -- bad arguments, B = 0 -- leaves the value)
+static thread_local int g_bandpower_path = 0;
+extern "C" int isd_stft_bandpower_last_path(void) { return g_bandpower_path; }
+
 extern "C" int isd_stft_bandpower(const isd_stft_plan* p, const float* y, float* feat, int64_t B, int64_t C,
                                   int n_bands_in, int n_bands, const int* klo, const int* khi, int mode, float eps,
                                   void* stream) {
@@ -344,23 +351,24 @@ extern "C" int isd_stft_bandpower(const isd_stft_plan* p, const float* y, float*
   int rc = fill_band_args(p, n_bands, klo, khi, ba.klo, ba.khi, "isd_stft_bandpower");
   if (rc) return rc;
   if (B == 0) return ISD_OK;
-  if (p->n == 64 && p->hop == 32 && p->T <= 512 && p->d_dft && n_bands_in == n_bands)
-    return bandpower_direct(p, y, feat, B * n_bands * C, (int)C, n_bands, ba.klo, ba.khi, mode, eps,
-                            (hipStream_t)stream);
-  if (p->d_blk && n_bands_in == n_bands) {
-    // per-band rows, every band 1..6 interior bins: block sums instead of one FFT per frame
-    int KB = 0, log2_nblk = 0;
-    const int64_t rows = B * n_bands * C;
-    if (blocksum_plan(p, ba.klo, ba.khi, n_bands, &KB, &log2_nblk) < 0 && rows <= 0x7fffffffLL) {
-      static constexpr decltype(&bandpower_blocksum_kernel<64, 4>) kern[2][4] = {   // [hop == 64 ? 0 : 1][KB: 4, 5, 6, 8]
-          {bandpower_blocksum_kernel<64, 4>, bandpower_blocksum_kernel<64, 5>, bandpower_blocksum_kernel<64, 6>,
-           bandpower_blocksum_kernel<64, 8>},
-          {bandpower_blocksum_kernel<32, 4>, bandpower_blocksum_kernel<32, 5>, bandpower_blocksum_kernel<32, 6>,
-           bandpower_blocksum_kernel<32, 8>}};
-      return launch_lds(kern[p->hop == 64 ? 0 : 1][KB == 8 ? 3 : KB - 4], dim3((unsigned)rows), dim3(64), 0,
-                        (hipStream_t)stream, p->d_blk, y, feat, rows, (int)C, p->T, n_bands, p->J, p->n, log2_nblk,
-                        p->scale * p->scale, ba, mode, eps);
-    }
+  const int64_t rows = B * n_bands * C;
+  int KB = 0, log2_nblk = 0;
+  const bool direct = p->n == 64 && p->hop == 32 && p->T <= 512 && p->d_dft && n_bands_in == n_bands;
+  // per-band rows, every band 1..6 interior bins: block sums instead of one FFT per frame
+  const bool blocksum = !direct && p->d_blk && n_bands_in == n_bands && rows <= 0x7fffffffLL &&
+                        blocksum_plan(p, ba.klo, ba.khi, n_bands, &KB, &log2_nblk) < 0;
+  g_bandpower_path = direct ? 1 + 16 * (int)bandpower_direct_full(p, y, rows) : blocksum ? 2 + 16 * KB : 3;
+  if (direct)
+    return bandpower_direct(p, y, feat, rows, (int)C, n_bands, ba.klo, ba.khi, mode, eps, (hipStream_t)stream);
+  if (blocksum) {
+    static constexpr decltype(&bandpower_blocksum_kernel<64, 4>) kern[2][4] = {   // [hop == 64 ? 0 : 1][KB: 4, 5, 6, 8]
+        {bandpower_blocksum_kernel<64, 4>, bandpower_blocksum_kernel<64, 5>, bandpower_blocksum_kernel<64, 6>,
+         bandpower_blocksum_kernel<64, 8>},
+        {bandpower_blocksum_kernel<32, 4>, bandpower_blocksum_kernel<32, 5>, bandpower_blocksum_kernel<32, 6>,
+         bandpower_blocksum_kernel<32, 8>}};
+    return launch_lds(kern[p->hop == 64 ? 0 : 1][KB == 8 ? 3 : KB - 4], dim3((unsigned)rows), dim3(64), 0,
+                      (hipStream_t)stream, p->d_blk, y, feat, rows, (int)C, p->T, n_bands, p->J, p->n, log2_nblk,
+                      p->scale * p->scale, ba, mode, eps);
   }
   return stft_launch(p, 1, y, feat, B * n_bands_in * C, (int)C, n_bands_in, n_bands, ba, mode, eps,
                      (hipStream_t)stream);

@@ -110,6 +110,8 @@ static inline int blocksum_plan(const isd_stft_plan* st, const int* klo, const i
 // direct-DFT band aggregation (fb.hip) for nperseg 64 / hop 32 / T <= 512, per-band input
 int bandpower_direct(const isd_stft_plan* st, const float* y, float* feat, int64_t R, int C, int nb, const int* klo,
                      const int* khi, int mode, float eps, hipStream_t stream);
+// whether that launch over R rows takes the kernel's FULL instances (isd_stft_bandpower_last_path reports it)
+bool bandpower_direct_full(const isd_stft_plan* st, const float* y, int64_t R);
 int fill_band_args(const isd_stft_plan* p, int n_bands, const int* klo, const int* khi, int* oklo, int* okhi,
                    const char* who);
 }  // namespace isd

@@ -116,6 +116,17 @@ enum {
 int isd_stft_bandpower(const isd_stft_plan* plan, const float* y, float* feat,
                        int64_t B, int64_t C, int n_bands_in, int n_bands,
                        const int* klo, const int* khi, int mode, float eps, void* stream);
+/* The kernel that the calling thread's last isd_stft_bandpower launched, as family + 16 * instance:
+ *   0 none yet;
+ *   1 / 17 the direct DFT (nperseg 64, hop 32, T <= 512, per-band input): bandpower_direct_kernel<MAG, FULL> with
+ *   FULL = false / true (MAG follows the mode);
+ *   2 + 16 KB = 66 / 82 / 98 / 130 the block sums (hop 32 or 64 = the plan's, nperseg = 2^a hop with 4..64 blocks per
+ *   frame, T <= 64 hop, every band 1..6 interior bins, per-band input): bandpower_blocksum_kernel<hop, KB>, KB = 4 / 5 /
+ *   6 / 8 slots for the widest band's 2 / 3 / 4 / 5..6 bins and their two Hann neighbours;
+ *   3 the radix-2 FFT with the band reduction (everything else, n_bands_in == 1 included).
+ * A call that fails its argument checks or has B == 0 leaves the value.  For tests: a fall-back to another kernel must
+ * not pass for the intended one. */
+int isd_stft_bandpower_last_path(void);
 
 /* Fused spec-S feature extractor: filterbank -> STFT -> log band power without
  * materialising the filtered signals.  x [B][C][T] -> feat [B][n_bands][C][J].

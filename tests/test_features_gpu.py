@@ -127,8 +127,18 @@ def test_overlapped_frames_bandpower_vs_oracle(isd, T, nperseg, noverlap, mode):
 
 
 @pytest.mark.parametrize("T,nperseg,noverlap", [(512, 64, 32), (500, 64, 32), (800, 64, 48), (100, 16, 4),
-                                                 (4096, 1024, 960), (37, 8, 0), (300, 256, 128)])
+                                                 (4096, 1024, 960), (37, 8, 0), (300, 256, 128),
+                                                 # the other radix-2 sizes, with hops that do not divide them; 7 rows
+                                                 # leave dead frames in the last workgroup (16 / 4 frames each at 32 /
+                                                 # 128); 512 is the first size with one frame per workgroup, 4096 asks
+                                                 # for exactly 64 KiB of dynamic LDS
+                                                 (120, 32, 9), (310, 128, 100), (1000, 512, 300), (3000, 2048, 1024),
+                                                 (5000, 4096, 3000), (4096, 4096, 4032),
+                                                 # hop 1 on a short row; rows shorter than half a window; one sample
+                                                 (20, 16, 15), (50, 128, 64), (1, 64, 32), (1, 4096, 0)])
 def test_stft_vs_oracle_param_sweep(isd, T, nperseg, noverlap):
+    """stft_kernel<0> against the oracle; the twiddles are fp64-rounded, so the expected error is about
+    log2(nperseg) 2^-24 of the largest magnitude, far inside the bound."""
     x = np.random.default_rng(T + nperseg).standard_normal((7, T)).astype(np.float32)
     st = isd.Stft(T, nperseg, noverlap)
     _, _, ref = odsp.stft(x, 256.0, nperseg, noverlap)
@@ -208,6 +218,44 @@ def test_fused_long_rows_vs_oracle_and_two_kernel_path(isd, T, fs, nperseg, nove
     for got in (a, b):
         assert (np.abs(got - ref) <= 1e-4 * np.maximum(1.0, np.abs(ref))).all()     # north-star gate: 1e-4 relative
     loud = ref > np.median(ref, axis=-1, keepdims=True) - np.log(1e4)
+    assert np.abs(a - ref)[loud].max() < TOL_FEAT and np.abs(a - b)[loud].max() < TOL_FEAT
+
+
+# fs 1024, nperseg 1024: 1-Hz bins.  Widest band 2 bins -> KB 4, 4 bins -> KB 6 (blocksum_plan); each set has bands on
+# both sides of the fp32 / fp64 split (below 14 Hz: fp64 recursion; above 36 Hz: fp32)
+BANDS_KB4 = [("a", 8.0, 9.9), ("b", 11.0, 12.9), ("c", 40.0, 41.9), ("d", 60.0, 61.9)]
+BANDS_KB6 = [("a", 6.0, 9.9), ("b", 10.0, 13.5), ("c", 40.0, 43.9), ("d", 50.0, 52.5)]
+
+
+@pytest.mark.parametrize("T,bands,kb", [
+    # choose_fused_route: whole 512-sample passes, at most 16 blocks per frame and KB <= 5 take four rows per wave
+    (1536, BANDS_KB4, 4),       # fused_rows4_kernel<float, 4, 4> and <double, 4, 0>
+    (1536, BANDS_KB6, 6),       # KB 6 has no rows4 instance: fused_long_kernel<float / double, 6, true>
+    (1500, BANDS_KB4, 4),       # ragged row: fused_long_kernel<float / double, 4, true>
+    (1500, BANDS_KB6, 6),       # fused_long_kernel<float / double, 6, true>, last pass and last block partial
+    (1501, BANDS_KB4, 4),       # T % 4 != 0, scalar loads: fused_long_kernel<float / double, 4, false>
+    (1501, BANDS_KB6, 6),       # fused_long_kernel<float / double, 6, false>
+])
+def test_fused_long_rows_kb4_kb6(isd, T, bands, kb):
+    """The long-row instances at KB 4 and 6, which no BANDS_40 slice reaches (three bins: KB 5): the fused extractor
+    against the two-kernel path (here bandpower_blocksum_kernel<64, KB>) and both against scipy."""
+    from isd_amd import _lib
+    fs, nperseg, noverlap = 1024.0, 1024, 960
+    X, _ = odsp.synth_trials(3, 5, T, fs, seed=T)
+    fx = isd.FeatureExtractor(T, fs, bands, nperseg=nperseg, noverlap=noverlap)
+    assert fx.can_fuse and fx.fb.precision == "mixed"
+    assert max(hi - lo + 1 for lo, hi in fx.bins) == kb - 2
+    a = fx(dev(X), fused=True).cpu().numpy().astype(np.float64)
+    assert _lib.lib().isd_features_fused_last_path() == 3
+    b = fx(dev(X), fused=False).cpu().numpy().astype(np.float64)
+    assert _lib.lib().isd_stft_bandpower_last_path() == 2 + 16 * kb
+    ref = odsp.extract_features_scipy(X, fs=fs, bands=bands, nperseg=nperseg, noverlap=noverlap).astype(np.float64)
+    assert a.shape == ref.shape
+    for got in (a, b):
+        assert (np.abs(got - ref) <= 1e-4 * np.maximum(1.0, np.abs(ref))).all()     # north-star gate: 1e-4 relative
+    loud = ref > np.median(ref, axis=-1, keepdims=True) - np.log(1e4)
+    print(f"FUSED_KB T={T} KB={kb}: fused {np.abs(a - ref)[loud].max():.3e}, two-kernel {np.abs(b - ref)[loud].max():.3e}, "
+          f"fused vs two-kernel {np.abs(a - b)[loud].max():.3e}")
     assert np.abs(a - ref)[loud].max() < TOL_FEAT and np.abs(a - b)[loud].max() < TOL_FEAT
 
 
